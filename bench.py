@@ -10,9 +10,18 @@ sessions every session has its own thread and issues its K calls back to back, l
 threads; the threads meet only before the first and after the last call.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--sessions S] [--batch B] [--model wav2lip|musetalk] [--fp8]
+                    [--dump-outputs DIR] [--full]
 
-Default (N=1): the timed line is BASELINE.json configs[1] (wav2lip256, 1 session, 16-frame batch, fp16).  Rank 0 then
-adds, OUTSIDE the timed region (each in its own subprocess, so `ms_per_step x steps` stays what was timed):
+Default (N=1): the timed line is BASELINE.json configs[1] (wav2lip256, 1 session, 16-frame batch, fp16).  A plain run does
+only what that line needs: set up, prime + W warm-up steps, K timed steps, the outputs (--dump-outputs), the JSON line.
+`--dump-outputs DIR` writes the frames the timed path returned in its last step (every session's `inference_batch` result,
+as rank 0 computed it) as DIR/frames.npy in float32; above 64 MB a fixed seeded sample of the frames is written instead,
+their flat (session, frame) indices in DIR/frames_index.npy.  The inputs are seeded: the same arguments give the same inputs.
+
+`--full` adds what the plain run leaves out (a plain run has `roofline` = null): behind the timed region the timed line's
+`roofline` (HIP-event device pass), its `sustained` twin (--sustain, default 2 s) and `pcie_inclusive`; for --model musetalk the
+Whisper step and the MuseTalk `cpu_baseline`; and at N=1 for wav2lip rank 0 then adds, OUTSIDE the timed region (each in its own
+subprocess, so `ms_per_step x steps` stays what was timed):
   also[]        configs[3]'s per-GPU share (16 wav2lip sessions on one GPU, saturating and paced at 25 fps),
                 configs[2] (MuseTalk + Whisper step) and configs[4]'s per-GPU share (4 MuseTalk sessions) in fp16 AND with the
                 fp8 conv path, each with its own PMC `roofline.traffic`
@@ -24,7 +33,8 @@ adds, OUTSIDE the timed region (each in its own subprocess, so `ms_per_step x st
   cpu_baseline  the reference's LipReal.inference_batch on the host cores (kind "reference" when a LiveTalking checkout
                 is importable, else the oracle port), B=16 and B=1 (configs[0]), median of 5
   roofline.traffic  HBM bytes per pass from two rocprofv3 --pmc passes (FETCH_SIZE x2, WRITE_SIZE) of the conv stack
-  pcie_inclusive    the same single session with host mel in and every composited frame copied back (paste_back_frame)
+where pcie_inclusive = the same single session with host mel in and every composited frame copied back (paste_back_frame).
+`--no-also`, `--no-traffic`, `--no-cpu-baseline`, `--no-whole-pass` trim a --full run.
 
 N>1: sessions are independent (app.py:62-63,99), so rank r owns its own engine, bank replica and sessions: no collective
 on the data path, xGMI unused.  Launched either by the driver (`python -m torch.distributed.run ... bench.py --gpus N`:
@@ -155,6 +165,8 @@ class SessionThreads:
         self.S = len(sessions)
         self.busy = [0.0] * self.S          # per session: seconds inside inference_batch (the reference's counttime)
         self.frames = [0] * self.S
+        self.keep_last = False              # --dump-outputs: keep every session's latest inference_batch result in `last`
+        self.last = [None] * self.S
         self._step = 0
         self._nsteps = 1
         self._err = None
@@ -174,6 +186,8 @@ class SessionThreads:
         pred = s.inference_batch(step * s.batch_size + self.stride * i, self.feats[i])
         self.busy[i] += time.perf_counter() - t
         self.frames[i] += len(pred)
+        if self.keep_last:
+            self.last[i] = pred
 
     def _run(self, i):
         while True:
@@ -208,6 +222,29 @@ class SessionThreads:
         if self.S > 1:
             self._stop = True
             self._go.wait()
+
+
+DUMP_BYTES = 64_000_000               # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what every session's last timed inference_batch call returned (S lists of B uint8 (256,256,3) device
+    tensors) as float32 DIR/frames.npy of shape (S, B, 256, 256, 3).  Above DUMP_BYTES a fixed seeded sample of the S*B frames
+    is written instead, (n, 256, 256, 3), with their flat indices (session * B + frame, float64) in DIR/frames_index.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    frames = torch.stack([torch.stack(list(p)) for p in last])           # (S, B, 256, 256, 3) uint8 on the device
+    S, B = frames.shape[:2]
+    per_frame = frames[0, 0].numel() * 4
+    if S * B * per_frame <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "frames.npy"), frames.cpu().numpy().astype(np.float32))
+        return
+    n = (DUMP_BYTES - 4096) // (per_frame + 8)
+    idx = np.sort(np.random.default_rng(0).choice(S * B, size=n, replace=False))
+    flat = frames.reshape(S * B, *frames.shape[2:])
+    np.save(os.path.join(out_dir, "frames.npy"), flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "frames_index.npy"), idx.astype(np.float64))
 
 
 def paced_sessions(drv: SessionThreads, first_step: int, periods: int, B: int, stagger: bool = False):
@@ -293,6 +330,7 @@ def run_wav2lip(args, ranks: Ranks):
         drv.step(i)
     for i in range(args.warmup):
         drv.step(PRIME + i)
+    drv.keep_last = bool(args.dump_outputs)
     ranks.barrier()
     t0 = time.perf_counter()
     drv.step(PRIME + args.warmup, nsteps=args.steps)
@@ -303,6 +341,10 @@ def run_wav2lip(args, ranks: Ranks):
     elapsed_max, _ = ranks.gather_max(elapsed)
     _, per_rank = ranks.gather_max(own)
     value = ranks.world * args.steps * frames_per_step / elapsed_max
+    drv.keep_last = False
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, drv.last)
+    full = args.full or bool(args.sub)                 # the legs behind the timed line (subprocess legs are parts of a --full run)
 
     # the sustained twin of the timed line: the SAME loop for >= `--sustain` seconds right behind the timed region (the first
     # launches of a process run up to ~20 % faster than the steady thermal state, and the default timed region is only ~30 ms)
@@ -325,7 +367,7 @@ def run_wav2lip(args, ranks: Ranks):
     # numpy arrays over, mel.py:34-67) and every frame comes back composited into its full frame as a host array, as
     # LipReal.paste_back_frame returns it (wav2lip_avatar.py:141-147): 82 KB up and B x H x W x 3 bytes down per step.
     pcie = None
-    if ranks.rank == 0 and S == 1:
+    if full and ranks.rank == 0 and S == 1:
         import numpy as np
         from livetalking_amd.hostshim import mirror_index
         s0 = sessions[0]
@@ -352,11 +394,11 @@ def run_wav2lip(args, ranks: Ranks):
     nf_pass = min(frames_per_step, 256)
     graphs_timed_run = eng.graph_count()            # > 0: the timed inference_batch calls above ran from captured graphs
     pf_stats = eng.prefetch_stats()                 # knob PREFETCH: how the session calls above actually ran
-    conv_ms, conv_macs = eng.time_convs(nf_pass, 10)
-    achieved = 2.0 * conv_macs / (conv_ms * 1e-3) / 1e12
+    conv_ms, conv_macs = eng.time_convs(nf_pass, 10) if full else (None, None)
+    achieved = 2.0 * conv_macs / (conv_ms * 1e-3) / 1e12 if full else None
     # the same pass with every call running the whole network on its own (knob PREFETCH off: rounds 1-4), for comparison
     conv_ms_whole = None
-    if pf_stats["issued"] > 0 and not args.no_whole_pass:
+    if full and pf_stats["issued"] > 0 and not args.no_whole_pass:
         from livetalking_amd.engine import Engine
         Engine.set_knob("PREFETCH", 0)
         try:
@@ -394,7 +436,7 @@ def run_wav2lip(args, ranks: Ranks):
                                           "stream; hits = calls that started at the decoder.  Every layer runs once per frame and step inside the timed "
                                           "region (the first call runs the whole pass, the last call's prefetch is extra work); frames byte-identical to "
                                           "the knob off (tests/test_wav2lip_gpu.py::test_prefetched_face_encoder_equals_whole_pass)"),
-                         "pass_ms_whole_pass_per_call": round(conv_ms_whole, 4) if conv_ms_whole else None},
+                         "pass_ms_whole_pass_per_call": round(conv_ms_whole, 4) if conv_ms_whole else None} if full else None,
             "per_rank_fps": [round(args.steps * frames_per_step / t, 1) for t in per_rank],
             "scheduler": sched,
         }
@@ -460,6 +502,7 @@ def run_musetalk(args, ranks: Ranks, shared=None):
         drv.step(i)
     for i in range(args.warmup):
         drv.step(PRIME + i)
+    drv.keep_last = bool(args.dump_outputs)
     ranks.barrier()
     t0 = time.perf_counter()
     drv.step(PRIME + args.warmup, nsteps=args.steps)
@@ -470,26 +513,31 @@ def run_musetalk(args, ranks: Ranks, shared=None):
     elapsed_max, _ = ranks.gather_max(elapsed)
     _, per_rank = ranks.gather_max(own)
     value = ranks.world * args.steps * fps_step / elapsed_max
+    drv.keep_last = False
+    if args.dump_outputs and ranks.rank == 0:
+        dump_outputs(args.dump_outputs, drv.last)
+    full = args.full or bool(args.sub)                 # the legs behind the timed line (subprocess legs are parts of a --full run)
     sched = dict(sessions[0]._sched.stats)
     drv.close()
     nt = min(fps_step, 64)
-    ms, macs = eng.musetalk_time(nt, 3)
-    achieved = 2.0 * macs / (ms * 1e-3) / 1e12
-    # roofline peak: MAC-weighted blend of the fp8 peak (layers on e4m3 operands) and the fp16 peak (everything else)
     f8 = macs_fp8 / macs_all if args.fp8 else 0.0
-    peak = 1.0 / (f8 / PEAK_FP8_TFLOPS + (1.0 - f8) / PEAK_F16_TFLOPS)
-    # WhisperASR.run_step's feature work (log-mel + whisper-tiny encoder + chunk slicing) for one session's 0.64-s step: the
-    # reference runs it on the render thread, outside inferfps (base_avatar.py:364-373 times inference_batch only)
-    pcm = synth.synthetic_audio(2.0)[: (20 + 2 * B) * 320]
-    d_chunks = torch.zeros(B, 50, 384, dtype=torch.float32, device="cuda")
-    for _ in range(2):
-        eng.whisper_step(pcm, B, first_row=10, d_out_ptr=d_chunks.data_ptr())
-    torch.cuda.synchronize()
-    tw = time.perf_counter()
-    for _ in range(5):
-        eng.whisper_step(pcm, B, first_row=10, d_out_ptr=d_chunks.data_ptr())
-    torch.cuda.synchronize()
-    whisper_ms = (time.perf_counter() - tw) / 5 * 1e3
+    if full:
+        ms, macs = eng.musetalk_time(nt, 3)
+        achieved = 2.0 * macs / (ms * 1e-3) / 1e12
+        # roofline peak: MAC-weighted blend of the fp8 peak (layers on e4m3 operands) and the fp16 peak (everything else)
+        peak = 1.0 / (f8 / PEAK_FP8_TFLOPS + (1.0 - f8) / PEAK_F16_TFLOPS)
+        # WhisperASR.run_step's feature work (log-mel + whisper-tiny encoder + chunk slicing) for one session's 0.64-s step: the
+        # reference runs it on the render thread, outside inferfps (base_avatar.py:364-373 times inference_batch only)
+        pcm = synth.synthetic_audio(2.0)[: (20 + 2 * B) * 320]
+        d_chunks = torch.zeros(B, 50, 384, dtype=torch.float32, device="cuda")
+        for _ in range(2):
+            eng.whisper_step(pcm, B, first_row=10, d_out_ptr=d_chunks.data_ptr())
+        torch.cuda.synchronize()
+        tw = time.perf_counter()
+        for _ in range(5):
+            eng.whisper_step(pcm, B, first_row=10, d_out_ptr=d_chunks.data_ptr())
+        torch.cuda.synchronize()
+        whisper_ms = (time.perf_counter() - tw) / 5 * 1e3
     out = None
     if ranks.rank == 0:
         out = {"metric": "inferfps", "value": round(value, 2), "unit": "frames/s", "n_gpus": ranks.world, "steps": args.steps,
@@ -504,13 +552,13 @@ def run_musetalk(args, ranks: Ranks, shared=None):
                             "frac": round(achieved / peak, 5), "traffic": None,
                             "peak_note": "MAC-weighted blend of 5 PF (fp8 layers) and 2.5 PF (fp16 layers)" if args.fp8 else "dense fp16 MFMA",
                             "kernel": "conv3_kernel / conv_mfma_kernel (U-Net + VAE conv and linear layers; attention excluded from the flop count)",
-                            "pass_ms": round(ms, 4), "frames_per_pass": nt, "flops_per_frame": 2.0 * macs / nt},
+                            "pass_ms": round(ms, 4), "frames_per_pass": nt, "flops_per_frame": 2.0 * macs / nt} if full else None,
                "sessions_25fps": {"per_gpu": int(value / ranks.world // 25), "note": "saturating rate / 25 fps"},
                "per_rank_fps": [round(args.steps * fps_step / t, 1) for t in per_rank],
                "scheduler": sched,
                "whisper": {"ms_per_session_step": round(whisper_ms, 3), "frames_per_step": B,
                            "note": "log-mel + whisper-tiny encoder (1500 tokens) + chunk slicing, host PCM in, device features out; not in `value`",
-                           "fps_incl_whisper": round(fps_step / (elapsed_max / args.steps + S * whisper_ms * 1e-3), 2)}}
+                           "fps_incl_whisper": round(fps_step / (elapsed_max / args.steps + S * whisper_ms * 1e-3), 2)} if full else None}
     for e in model.engines:
         e.close()
     return out
@@ -995,8 +1043,11 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="musetalk: BASELINE configs[4] fp8 conv path")
     ap.add_argument("--paced", type=int, default=0, help="after the timed run: N periods of B/25 s with every session paced at 25 fps")
     ap.add_argument("--paced-stagger", action="store_true", help="--paced with the sessions' request times spread evenly over the period (every request a call of its own)")
+    ap.add_argument("--full", action="store_true", help="behind the timed line: roofline, sustained twin, PCIe-inclusive rate, the other "
+                    "BASELINE configs, capacities, PMC traffic and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the frames of the last timed step as DIR/frames.npy (float32)")
     ap.add_argument("--sustain", type=float, default=None,
-                    help="seconds of the `sustained` twin behind the timed region (default 2.0 for the primary wav2lip line, 0 = off)")
+                    help="seconds of the `sustained` twin behind the timed region (default 2.0 for the primary line under --full, 0 = off)")
     ap.add_argument("--no-whole-pass", action="store_true", help="skip the comparison timing with knob PREFETCH off (profiler runs: the last pass of "
                     "the process is then a pipelined one)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1009,7 +1060,7 @@ def main():
     ap.add_argument("--sub", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.sustain is None:
-        args.sustain = 0.0 if (args.sub or args.dry_ranks) else 2.0
+        args.sustain = 2.0 if (args.full and not args.sub and not args.dry_ranks) else 0.0
 
     if args.sub == "convpasses":
         return sub_convpasses(args)
@@ -1057,7 +1108,7 @@ def main():
     if ranks.rank != 0 or out is None:
         return
     primary = not args.sub and not args.dry_ranks
-    if primary and ranks.world == 1 and args.model == "wav2lip":
+    if primary and args.full and ranks.world == 1 and args.model == "wav2lip":
         def add_traffic(rl, sub, extra, passes, conv_only, what):
             traffic, info = measure_traffic(sub, extra, passes, conv_only)
             rl["traffic"] = traffic
@@ -1107,7 +1158,7 @@ def main():
                                              "through the plugin's opt.egress = i420 path (watermarked I420 frames, half the PCIe bytes); per_gpu_kernel_capacity: "
                                              "engine level, frames stay on the device (paced bisection); at_16_sessions_per_gpu: 16 paced "
                                              "session threads through LipReal.inference_batch"}
-    if primary and ranks.world == 1 and not args.no_cpu_baseline:         # the CPU baseline is timed at N=1 only
+    if primary and args.full and ranks.world == 1 and not args.no_cpu_baseline:         # the CPU baseline is timed at N=1 only
         out["cpu_baseline"] = cpu_baseline(args.batch) if args.model == "wav2lip" else cpu_baseline_musetalk()
     print(json.dumps(out), flush=True)
 

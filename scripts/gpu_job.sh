@@ -26,10 +26,10 @@ profile)
   # ONLY="w2l": re-profile just the named workloads (no default bench run), e.g. after a change that touches one of them
   ONLY=${ONLY:-}
   want() { [ -z "$ONLY" ] || [[ " $ONLY " == *" $1 "* ]]; }
-  if [ -z "$ONLY" ]; then timeout 900 python bench.py --steps 50 --warmup 5 > $P/bench_default.json 2> $P/bench_default.err; head -c 400 $P/bench_default.json; echo; fi
+  if [ -z "$ONLY" ]; then timeout 900 python bench.py --full --steps 50 --warmup 5 > $P/bench_default.json 2> $P/bench_default.err; head -c 400 $P/bench_default.json; echo; fi
   cd /tmp && export TMPDIR=/tmp
   prof() {   # prof <name> <bench args...>: kernel trace + FETCH / WRITE / SQ / L2 counter passes, each its own run
-    local n=$1; shift; want $n || return 0; local CMD="python $R/bench.py $* --no-cpu-baseline --no-also --no-traffic"
+    local n=$1; shift; want $n || return 0; local CMD="python $R/bench.py --full $* --no-cpu-baseline --no-also --no-traffic"
     timeout 400 rocprofv3 --kernel-trace --stats -d $P/${n}_trace -o r -- $CMD > $P/${n}_trace.log 2>&1
     # counter passes: the same launches issued one by one (LTK_GRAPH=0), so every dispatch is a plain kernel packet for the profiler
     export LTK_GRAPH=0
@@ -45,12 +45,12 @@ profile)
   prof w2l256 --sessions 16 --steps 3 --warmup 1 --sustain 0
   prof mt --model musetalk --steps 2 --warmup 1
   prof mtfp8 --model musetalk --fp8 --sessions 4 --steps 2 --warmup 1
-  want mt12 && timeout 400 rocprofv3 --kernel-trace --stats -d $P/mt12_trace -o r -- python $R/bench.py --model musetalk --steps 11 --warmup 1 --no-cpu-baseline > $P/mt12_trace.log 2>&1
+  want mt12 && timeout 400 rocprofv3 --kernel-trace --stats -d $P/mt12_trace -o r -- python $R/bench.py --full --model musetalk --steps 11 --warmup 1 --no-cpu-baseline > $P/mt12_trace.log 2>&1
   cd $R; S=$O/${TAG}_summary; mkdir -p $S
-  want w2l && python scripts/make_profile_summary.py $P $S/$TAG --name w2l --frames 16 --cmd "bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-also --no-traffic  (wav2lip256, 1 session, 16-frame batch)" > /dev/null
-  want w2l256 && python scripts/make_profile_summary.py $P $S/$TAG --name w2l256 --frames 256 --cmd "bench.py --sessions 16 --steps 3 --warmup 1 --no-cpu-baseline --no-also --no-traffic  (16 sessions, 256-frame passes)" > /dev/null
-  want mt && python scripts/make_profile_summary.py $P $S/$TAG --name mt --all-kernels --frames 16 --cmd "bench.py --model musetalk --steps 2 --warmup 1 --no-cpu-baseline" > /dev/null
-  want mtfp8 && python scripts/make_profile_summary.py $P $S/$TAG --name mtfp8 --all-kernels --frames 64 --cmd "bench.py --model musetalk --fp8 --sessions 4 --steps 2 --warmup 1 --no-cpu-baseline" > /dev/null
+  want w2l && python scripts/make_profile_summary.py $P $S/$TAG --name w2l --frames 16 --cmd "bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-also --no-traffic  (wav2lip256, 1 session, 16-frame batch)" > /dev/null
+  want w2l256 && python scripts/make_profile_summary.py $P $S/$TAG --name w2l256 --frames 256 --cmd "bench.py --full --sessions 16 --steps 3 --warmup 1 --no-cpu-baseline --no-also --no-traffic  (16 sessions, 256-frame passes)" > /dev/null
+  want mt && python scripts/make_profile_summary.py $P $S/$TAG --name mt --all-kernels --frames 16 --cmd "bench.py --full --model musetalk --steps 2 --warmup 1 --no-cpu-baseline" > /dev/null
+  want mtfp8 && python scripts/make_profile_summary.py $P $S/$TAG --name mtfp8 --all-kernels --frames 64 --cmd "bench.py --full --model musetalk --fp8 --sessions 4 --steps 2 --warmup 1 --no-cpu-baseline" > /dev/null
   want mt12 && python scripts/prof_report.py $P/mt12_trace 2>/dev/null | grep -E "^kernel|amd_rocclr|gn_|conv3_kernel<1, 2, 4" | head -12 > $S/${TAG}_mt12_blits.txt
   [ -z "$ONLY" ] && cp $P/bench_default.json $S/${TAG}_bench_default.json
   rm -rf $P
@@ -92,8 +92,8 @@ r4a)  # round-4 job A: full GPU suite, graph / depth-first A/B, clock experiment
   ROUNDS=3 timeout 600 python scripts/layer_times.py "GRAPH=0" "GRAPH=1" "GRAPH=1,DF_FRAMES=4,DF_MIN=1" "GRAPH=1,DF_FRAMES=8,DF_MIN=1" "GRAPH=1,DF_FRAMES=16,DF_MIN=1" \
       "GRAPH=1,DF_FRAMES=4,DF_MIN=1,DF_BLOCK=7" "GRAPH=1,DF_FRAMES=8,DF_MIN=1,DF_BLOCK=5" -- 16 64 256 2>&1 | grep -E "^====|^sum|^conv stack" > $O/r4a_graph_df_ab.txt; cat $O/r4a_graph_df_ab.txt
   bash $0 clock c256@64 c64@256 > $O/r4a_clock.log 2>&1; cat $O/clock_report.txt
-  timeout 400 python bench.py --steps 50 --warmup 5 --no-also --no-cpu-baseline > $O/r4a_bench_s1.json 2> $O/r4a_bench_s1.err; head -c 1200 $O/r4a_bench_s1.json; echo
-  for IF in 1 2 1 2; do LTK_INFLIGHT=$IF timeout 300 python bench.py --sessions 16 --steps 10 --warmup 3 --no-also --no-cpu-baseline --no-traffic > $O/r4a_bench_s16_if$IF.json 2>> $O/r4a_bench_s16.err
+  timeout 400 python bench.py --full --steps 50 --warmup 5 --no-also --no-cpu-baseline > $O/r4a_bench_s1.json 2> $O/r4a_bench_s1.err; head -c 1200 $O/r4a_bench_s1.json; echo
+  for IF in 1 2 1 2; do LTK_INFLIGHT=$IF timeout 300 python bench.py --full --sessions 16 --steps 10 --warmup 3 --no-also --no-cpu-baseline --no-traffic > $O/r4a_bench_s16_if$IF.json 2>> $O/r4a_bench_s16.err
     python -c "import json,sys; d=json.load(open('$O/r4a_bench_s16_if$IF.json')); print('inflight $IF', d['value'], d['ms_per_step'], d['roofline']['frac'], d['scheduler'])"; done ;;
 r4b)  # round-4 job B: paste diagnostic, the whole GPU suite (no stop at the first failure), depth-first / stagger / rowconv A/Bs, graph A/B of the timed line
   timeout 200 python scripts/paste_diag.py 2>&1 | grep "paste-diag" > $O/r4b_paste_diag.txt; cat $O/r4b_paste_diag.txt
@@ -101,7 +101,7 @@ r4b)  # round-4 job B: paste diagnostic, the whole GPU suite (no stop at the fir
   ROUNDS=7 timeout 500 python scripts/pass_ab.py "DF_FRAMES=0" "DF_FRAMES=16,DF_MIN=1" "DF_FRAMES=12,DF_MIN=1" "DF_FRAMES=24,DF_MIN=1" "DF_FRAMES=32,DF_MIN=1" "DF_FRAMES=16,DF_MIN=1,DF_BLOCK=5" "DF_FRAMES=16,DF_MIN=1,DF_BLOCK=7" "DF_FRAMES=16,DF_MIN=1,DF_BLOCK=4" -- 32 48 64 128 256 > $O/r4b_df_ab.txt 2>&1; cat $O/r4b_df_ab.txt
   ROUNDS=7 timeout 500 python scripts/pass_ab.py "STAGGER=0" "STAGGER=3000" "STAGGER=8000" "STAGGER=16000" "STAGGER=30000" "STAGGER=8000,STAGGER_MODE=1" "STAGGER=16000,STAGGER_MODE=1" -- 16 64 256 > $O/r4b_stagger_ab.txt 2>&1; cat $O/r4b_stagger_ab.txt
   ROUNDS=7 timeout 300 python scripts/pass_ab.py "ROWCONV=1024" "ROWCONV=2048" "ROWCONV=0" -- 16 32 > $O/r4b_rowconv_ab.txt 2>&1; cat $O/r4b_rowconv_ab.txt
-  for G in 0 1 0 1; do LTK_GRAPH=$G timeout 300 python bench.py --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4b_bench_g$G.json 2>> $O/r4b_bench.err
+  for G in 0 1 0 1; do LTK_GRAPH=$G timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4b_bench_g$G.json 2>> $O/r4b_bench.err
     python -c "import json; d=json.load(open('$O/r4b_bench_g$G.json')); print('graph $G', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['hipgraph'], d['pcie_inclusive']['value'])"; done ;;
 r4c)  # round-4 job C: per-phase rowconv for the small-map transposed convs
   TAG=r4c MAXFAIL=--maxfail=20 bash $0 tests tests/test_wav2lip_gpu.py tests/test_mel_paste_gpu.py tests/test_plugin_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|rowconv" $O/pytest_r4c.log | tail -16
@@ -114,7 +114,7 @@ r4d)  # round-4 job D: conv3 stride-2 with the conflict-free LDS image (default 
     echo "######## round $rnd LTK_CONV_V3_S2=$V" >> $O/r4d_s2_layers.txt
     LTK_CONV_V3_S2=$V ROUNDS=3 timeout 300 python scripts/layer_times.py "GRAPH=1" -- 16 256 2>&1 | grep -E "^====|face_encoder_blocks.[1-6].0|^sum|^conv stack" >> $O/r4d_s2_layers.txt
   done; done; cat $O/r4d_s2_layers.txt
-  for IF in 1 2 1 2 1 2; do LTK_INFLIGHT=$IF timeout 300 python bench.py --sessions 16 --steps 12 --warmup 3 --no-also --no-cpu-baseline --no-traffic > $O/r4d_bench_s16_if$IF.json 2>> $O/r4d_bench_s16.err
+  for IF in 1 2 1 2 1 2; do LTK_INFLIGHT=$IF timeout 300 python bench.py --full --sessions 16 --steps 12 --warmup 3 --no-also --no-cpu-baseline --no-traffic > $O/r4d_bench_s16_if$IF.json 2>> $O/r4d_bench_s16.err
     python -c "import json,sys; d=json.load(open('$O/r4d_bench_s16_if$IF.json')); print('inflight $IF', d['value'], d['ms_per_step'], d['roofline']['frac'], d['scheduler'])" | tee -a $O/r4d_inflight.txt; done ;;
 r4e)  # round-4 job E: concurrency test, delivered capacity with / without the graph path, the MuseTalk sub-bench with its measured delivered run
   TAG=r4e MAXFAIL=--maxfail=20 bash $0 tests tests/test_plugin_gpu.py tests/test_mel_paste_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|in flight" $O/pytest_r4e.log | tail -8
@@ -144,7 +144,7 @@ r4vs3)  # the round-3 tree (build/r03tree: git archive 367ff43 + make) against t
     echo "######## round $rnd tree $T: conv stack / pass (scripts/layer_times.py, 3 rounds; us)" >> $L
     (cd $D && ROUNDS=3 timeout 300 python scripts/layer_times.py "TILE_RULE=1" -- 16 256 2>&1 | grep -E "^====|^sum|^conv stack") >> $L
     echo "######## round $rnd tree $T: timed line (bench.py --steps 100, 1 session x 16 frames)" >> $L
-    (cd $D && timeout 300 python bench.py --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['frac'])") >> $L
+    (cd $D && timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['frac'])") >> $L
   done; done
   for rnd in 1 2; do for T in r03 r04; do
     D=$R; [ $T = r03 ] && D=$R/build/r03tree
@@ -154,31 +154,31 @@ r4vs3)  # the round-3 tree (build/r03tree: git archive 367ff43 + make) against t
   cat $L ;;
 r4n)  # round-4 job N: the final default (GRAPH = 1: replay from 48 frames on) - tests that touch the graph path, timed line auto vs always, the default bench line
   TAG=r4n MAXFAIL=--maxfail=20 bash $0 tests tests/test_wav2lip_gpu.py tests/test_plugin_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4n.log | tail -6
-  for G in 1 2 1 2 1 2; do LTK_GRAPH=$G timeout 300 python bench.py --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4n_bench_g$G.json 2>> $O/r4n_bench.err
+  for G in 1 2 1 2 1 2; do LTK_GRAPH=$G timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4n_bench_g$G.json 2>> $O/r4n_bench.err
     python -c "import json; d=json.load(open('$O/r4n_bench_g$G.json')); print('GRAPH=$G', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['frac'], d['roofline']['hipgraph'])" | tee -a $O/r4n_graph_auto_ab.txt; done
-  timeout 600 python bench.py > $O/r4n_bench_default.json 2> $O/r4n_bench_default.err; head -c 300 $O/r4n_bench_default.json ;;
+  timeout 600 python bench.py --full > $O/r4n_bench_default.json 2> $O/r4n_bench_default.err; head -c 300 $O/r4n_bench_default.json ;;
 r4p)  # round-4 job P: row-parity LDS key on tiles narrower than 32 pixels (conv3 stride 1): in-job A/B first, then the whole -m gpu suite, smoke, a bench line
   L=$O/r4p_lds_swz_ab.txt; : > $L
   ROUNDS=5 timeout 300 python scripts/pass_ab.py "LDS_SWZ=0" "LDS_SWZ=1" -- 16 64 256 2>&1 | grep -E "^settings|frames" >> $L
   timeout 400 python scripts/mt_op_times.py 16 LDS_SWZ=0,1 2>&1 | grep -E "^====|conv/linear|->" > $O/r4p_mt_lds_swz_ab.txt; grep -E "^====|conv/linear " $O/r4p_mt_lds_swz_ab.txt | head -12 >> $L; cat $L
   TAG=r4p MAXFAIL=--maxfail=20 bash $0 tests tests > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4p.log | tail -8
   timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" 2>&1 | tail -2
-  timeout 400 python bench.py --no-cpu-baseline > $O/r4p_bench.json 2> $O/r4p_bench.err; head -c 600 $O/r4p_bench.json ;;
+  timeout 400 python bench.py --full --no-cpu-baseline > $O/r4p_bench.json 2> $O/r4p_bench.err; head -c 600 $O/r4p_bench.json ;;
 r4q)  # round-4 job Q: SQ_LDS_BANK_CONFLICT of the MuseTalk pass (then the 256-frame Wav2Lip pass) under the column key and the row key (separate --pmc runs, eager launches)
   cd /tmp && export TMPDIR=/tmp; export LTK_GRAPH=0
   for W in mt w2l256; do
     [ $W = mt ] && A="--model musetalk --steps 2 --warmup 1" || A="--sessions 16 --steps 2 --warmup 1"
-    for K in 0 1; do LTK_LDS_SWZ=$K timeout 130 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/r4q/${W}_swz$K -o r -- python $R/bench.py $A --no-cpu-baseline --no-also --no-traffic > $O/r4q_${W}_swz$K.log 2>&1; done
+    for K in 0 1; do LTK_LDS_SWZ=$K timeout 130 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/r4q/${W}_swz$K -o r -- python $R/bench.py --full $A --no-cpu-baseline --no-also --no-traffic > $O/r4q_${W}_swz$K.log 2>&1; done
     python $R/scripts/lds_conflict_report.py column-key=$O/r4q/${W}_swz0 row-key=$O/r4q/${W}_swz1 > $O/r4q_lds_conflicts_$W.txt 2>&1; head -30 $O/r4q_lds_conflicts_$W.txt
     rm -rf $O/r4q/${W}_swz0 $O/r4q/${W}_swz1
   done ;;
 r4r)  # round-4 job R: host-path trims (unbind, lazy bank indices, scheduler solo path): the plugin-level GPU tests, then the timed line (gap = ms_per_step - device pass)
   TAG=r4r MAXFAIL=--maxfail=20 timeout 120 bash $0 tests tests/test_plugin_gpu.py tests/test_egress_gpu.py tests/test_ref_loop.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|rror" $O/pytest_r4r.log | tail -8
-  for i in 1 2; do timeout 40 python bench.py --steps 200 --warmup 10 --no-also --no-cpu-baseline --no-traffic 2>> $O/r4r_bench.err | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('timed line', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], round(1e3*(d['ms_per_step']-d['roofline']['conv_stack_ms']),1), 'us host gap')" | tee -a $O/r4r_host_gap.txt; done
+  for i in 1 2; do timeout 40 python bench.py --full --steps 200 --warmup 10 --no-also --no-cpu-baseline --no-traffic 2>> $O/r4r_bench.err | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('timed line', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], round(1e3*(d['ms_per_step']-d['roofline']['conv_stack_ms']),1), 'us host gap')" | tee -a $O/r4r_host_gap.txt; done
   TAG=r4r_mt MAXFAIL=--maxfail=20 timeout 100 bash $0 tests tests/test_musetalk_plugin_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|rror" $O/pytest_r4r_mt.log | tail -4 ;;
 r4s)  # round-4 job S: host-path trims, in-job A/B of the Python trees (build/oldhost = git archive d39d0bc + the same libltk_hip.so), 16 sessions and 1 session
   L=$O/r4s_host_ab.txt; : > $L
-  one() { (cd $1 && timeout 40 python bench.py --sessions $2 --steps $3 --warmup 5 --no-also --no-cpu-baseline --no-traffic 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$4 sessions=$2', d['value'], d['ms_per_step'])") | tee -a $L; }
+  one() { (cd $1 && timeout 40 python bench.py --full --sessions $2 --steps $3 --warmup 5 --no-also --no-cpu-baseline --no-traffic 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$4 sessions=$2', d['value'], d['ms_per_step'])") | tee -a $L; }
   for rnd in 1 2; do one $R/build/oldhost 16 40 old; one $R 16 40 new; done
   one $R/build/oldhost 1 200 old; one $R 1 200 new ;;
 r4t)  # round-4 job T: the 1x1 chunk ring (LTK_RING1; needs the tree of commit cb1ad49): bitwise parity + per-shape timing, then the MuseTalk pass per op

@@ -49,7 +49,7 @@ def main():
                                                            "head kernel = one per pass; MuseTalk: gn_apply launches / 91)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--name", default="", help="workload prefix of the sub-directories (w2l, w2l256, mt, mtfp8); empty = round-2 layout")
-    ap.add_argument("--cmd", default="bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-also --no-traffic", help="the profiled command (for the headers)")
+    ap.add_argument("--cmd", default="bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-also --no-traffic", help="the profiled command (for the headers)")
     ap.add_argument("--all-kernels", action="store_true", help="PMC sums over every kernel of the run except the runtime's copy / fill blits (MuseTalk)")
     a = ap.parse_args()
     sub = (lambda d: os.path.join(a.src, f"{a.name}_{d}")) if a.name else (lambda d: os.path.join(a.src, d))

@@ -167,7 +167,7 @@ def test_bench_two_real_ranks_on_one_gpu():
         port = s.getsockname()[1]
     env = dict(os.environ, LTK_RANK_DEVICES="0,0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-also", "--no-cpu-baseline", "--no-traffic",
+           "--master-port", str(port), BENCH, "--gpus", "2", "--steps", "3", "--warmup", "2", "--full", "--no-also", "--no-cpu-baseline", "--no-traffic",
            "--sustain", "0.3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
