@@ -274,7 +274,7 @@ int ltk_debug_get(ltk_engine* e, const char* layer, float* out, size_t n_floats)
  * knobs that shape a plan (weight pack order) only affect plans created afterwards. */
 int ltk_debug_set_knob(const char* name, int value);
 
-/* Device-free consistency check of the engine's measured per-layer tile table (csrc/engine.hip kTileTable, knob TILE_TABLE):
+/* Device-free consistency check of the engine's measured per-layer tile table (csrc/w2l_program.hip kTileTable, knob TILE_TABLE):
  * every entry must name an existing layer, a frame-count bucket and a tile / split conv3 has an instantiation for.  Returns
  * the number of bad entries (0 = consistent) and writes their descriptions into `msg` (NUL-terminated, at most `cap` bytes). */
 int ltk_debug_tile_table_check(char* msg, int cap);

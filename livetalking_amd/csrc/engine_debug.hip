@@ -1,0 +1,520 @@
+// ------------------------------------------------------------------ test / measurement hooks of both models
+#include "engine_internal.h"
+
+extern "C" {
+
+// B frames from host tensors (warm_up, tests).  Runs as passes of at most one arena (micro-batch) each, so a start-up
+// warm_up(batch_size) also works when LTK_MICROBATCH is smaller than the session batch.
+int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6, int B, float* pred) {
+    if (!e || !mel || !face6 || !pred || B <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
+    if (B > e->max_frames) return fail(LTK_E_INVALID, "B exceeds max_frames");
+    CHK(enter_device(e->device));
+    const int mb = std::min(e->micro_batch, kPackMaxFrames);
+    const int cap = std::min(B, mb);
+    DevBuf d_mel, d_face, d_pred;
+    CHK(hipMalloc(&d_mel.p, (size_t)cap * 80 * 16 * sizeof(float)));
+    CHK(hipMalloc(&d_face.p, (size_t)cap * 6 * 65536 * sizeof(float)));
+    CHK(hipMalloc(&d_pred.p, (size_t)cap * 3 * 65536 * sizeof(float)));
+    for (int f0 = 0; f0 < B; f0 += mb) {
+        const int nf = std::min(mb, B - f0);
+        CHK(hipMemcpy(d_mel.p, mel + (size_t)f0 * 1280, (size_t)nf * 1280 * sizeof(float), hipMemcpyHostToDevice));
+        CHK(hipMemcpy(d_face.p, face6 + (size_t)f0 * 6 * 65536, (size_t)nf * 6 * 65536 * sizeof(float), hipMemcpyHostToDevice));
+        MelPtrs mp;
+        for (int i = 0; i < nf; ++i) mp.p[i] = (float*)d_mel.p + (size_t)i * 1280;
+        {
+            std::lock_guard<std::mutex> g(e->mu);
+            launch_upload_tables(nullptr, &mp, nullptr, nf, e->d_tab, e->compute);
+            CHK(hipGetLastError());
+            const int rc = launch_pass(e, nf, e->compute, false, (const float*)d_face.p, false, (float*)d_pred.p);
+            if (rc) return rc;
+            CHK(hipStreamSynchronize(e->compute));
+        }
+        CHK(hipMemcpy(pred + (size_t)f0 * 3 * 65536, d_pred.p, (size_t)nf * 3 * 65536 * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return LTK_OK;
+}
+
+int ltk_debug_saturation(ltk_engine* e, int reset, unsigned long long* n_at_limit, unsigned long long* n_nonfinite) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    CHK(hipDeviceSynchronize());
+    unsigned long long h[2] = {0, 0};
+    CHK(hipMemcpy(h, e->d_sat, sizeof(h), hipMemcpyDeviceToHost));
+    if (n_at_limit) *n_at_limit = h[0];
+    if (n_nonfinite) *n_nonfinite = h[1];
+    if (reset) CHK(hipMemset(e->d_sat, 0, sizeof(h)));
+    return LTK_OK;
+}
+
+int ltk_debug_capture(ltk_engine* e, int enable) {
+    if (!e) return fail(LTK_E_INVALID, "engine is null");
+    std::lock_guard<std::mutex> g(e->mu);
+    e->capture = enable != 0;
+    if (!enable) { e->taps.clear(); e->tap_shape.clear(); }
+    return LTK_OK;
+}
+
+int ltk_debug_set_knob(const char* name, int value) {
+    if (knob_set(name, value)) return fail(LTK_E_INVALID, std::string("unknown knob ") + (name ? name : "(null)"));
+    return LTK_OK;
+}
+
+int ltk_debug_get(ltk_engine* e, const char* layer, float* out, size_t n_floats) {
+    if (!e || !layer || !out) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    auto it = e->taps.find(layer);
+    if (it == e->taps.end()) return fail(LTK_E_STATE, std::string("no capture for layer ") + layer);
+    if (it->second.size() != n_floats) return fail(LTK_E_INVALID, "size mismatch: captured " + std::to_string(it->second.size()));
+    memcpy(out, it->second.data(), n_floats * sizeof(float));
+    return LTK_OK;
+}
+
+// Dummy inputs of the timing hooks: every frame reads one zero bank crop and one zero mel window and writes its own scratch frame, so
+// that the hooks run the pass exactly as ltk_wav2lip_infer does (bank crops in, fused head out, captured graph included).
+namespace {
+struct TimingIO {
+    DevBuf face, mel, frames;
+    int setup(ltk_engine* e, int nf) {
+        CHK(hipMalloc(&face.p, 65536 * 3));
+        CHK(hipMemset(face.p, 0, 65536 * 3));
+        CHK(hipMalloc(&mel.p, 1280 * sizeof(float)));
+        CHK(hipMemset(mel.p, 0, 1280 * sizeof(float)));
+        CHK(hipMalloc(&frames.p, (size_t)nf * 65536 * 3));
+        FacePtrs fp; MelPtrs mp; OutPtrs op;
+        for (int i = 0; i < nf; ++i) { fp.p[i] = (const uint8_t*)face.p; mp.p[i] = (const float*)mel.p; op.p[i] = (uint8_t*)frames.p + (size_t)i * 65536 * 3; }
+        launch_upload_tables(&fp, &mp, &op, nf, e->d_tab, e->compute);
+        CHK(hipGetLastError());
+        return 0;
+    }
+};
+}  // namespace
+
+int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_pass, double* macs_per_pass) {
+    if (!e || frames <= 0 || iters <= 0 || !ms_per_pass) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
+    if (frames > e->max_frames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
+    hipEvent_t t0, t1;
+    CHK(hipEventCreate(&t0));
+    CHK(hipEventCreate(&t1));
+    // the pass as ltk_wav2lip_infer runs it (pack_mel + conv stack with the bank gather and the output head fused, knobs CONV7 /
+    // HEAD_FUSED; replayed from the captured graph under knob GRAPH), same micro-batch schedule, frames going to a scratch buffer
+    const int mbs = std::min(e->micro_batch, kPackMaxFrames);
+    TimingIO tio;
+    int rc = tio.setup(e, std::min(mbs, frames));
+    if (rc) return rc;
+    // knob PREFETCH: a session's consecutive <= 32-frame calls are pipelined across calls (tune.h); what is timed is then that steady
+    // state - every pass finds its face-encoder outputs prefetched and prefetches the next pass's (dummy bank crops here) - which
+    // is what the session's calls enqueue from the third call on
+    for (ltk_engine::PfSlot& sl : e->pfs) sl.valid = false;        // the timing passes fill slots 1 and 2 with dummy crops
+    const bool pipe = knob(K_PREFETCH) && e->alt_frames > 0 && frames <= std::min(e->alt_frames, mbs) && knob(K_HEAD_FUSED) && e->c7 && knob(K_CONV7);
+    if (pipe) {
+        FacePtrs nx;
+        for (int i = 0; i < frames; ++i) nx.p[i] = (const uint8_t*)tio.face.p;
+        launch_upload_tables(&nx, nullptr, nullptr, frames, e->d_tab_next, e->aux2);
+    }
+    int cur = 0;              // slot this pass works in (0: the priming pass runs the whole network in the arena's own set)
+    auto pass = [&]() -> int {
+        int prc = 0;
+        if (pipe) {
+            if (cur) CHK(hipStreamWaitEvent(e->compute, e->pfs[cur].ev_done, 0));
+            prc = launch_pass(e, frames, e->compute, true, nullptr, true, nullptr, false, cur, cur != 0);
+            if (cur) {
+                if (hipEventRecord(e->pfs[cur].ev_read, e->compute) != hipSuccess) { if (!prc) prc = fail(LTK_E_HIP, "hipEventRecord failed"); }
+                else e->pfs[cur].read = true;
+            }
+            const int nxt = cur == 1 ? 2 : 1;
+            if (!prc) prc = launch_prefetch(e, frames, nxt);
+            cur = nxt;
+            return prc;
+        }
+        for (int f0 = 0; f0 < frames && !prc; f0 += mbs) prc = launch_pass(e, std::min(mbs, frames - f0), e->compute, true, nullptr, true, nullptr);
+        return prc;
+    };
+    if (pipe) { rc = pass(); if (!rc) rc = pass(); if (!rc) rc = pass(); if (rc) return rc; }     // prime, then both slots seen once (eager)
+    rc = pass();              // warm (eager)
+    if (!rc) rc = pass();     // warm (captures the graph under knob GRAPH)
+    if (rc) return rc;
+    CHK(hipEventRecord(t0, e->compute));
+    for (int i = 0; i < iters && !rc; ++i) rc = pass();
+    if (rc) return rc;
+    CHK(hipEventRecord(t1, e->compute));
+    CHK(hipEventSynchronize(t1));
+    float ms = 0.f;
+    CHK(hipEventElapsedTime(&ms, t0, t1));
+    *ms_per_pass = ms / iters;
+    if (macs_per_pass) *macs_per_pass = (e->macs_per_frame - (knob(K_HEAD_FUSED) ? 0.0 : 32.0 * 3 * 65536)) * frames;
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    return LTK_OK;
+}
+
+int ltk_wav2lip_prefetch_stats(ltk_engine* e, unsigned long long* hits, unsigned long long* misses, unsigned long long* issued) {
+    if (!e) return fail(LTK_E_INVALID, "engine is null");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (hits) *hits = e->pf_hits;
+    if (misses) *misses = e->pf_misses;
+    if (issued) *issued = e->pf_issued;
+    return LTK_OK;
+}
+
+int ltk_program_graph_count(ltk_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> g(e->mu);
+    return e->prog_graphs.live();
+}
+
+int ltk_wav2lip_graph_count(ltk_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> g(e->mu);
+    return e->graphs.live();
+}
+
+int ltk_wav2lip_layer_count(ltk_engine* e) {
+    if (!e || !e->loaded) return 0;
+    return (int)e->layers.size();
+}
+
+int ltk_wav2lip_layer_name(ltk_engine* e, int layer, char* buf, int buf_len) {
+    if (!e || !e->loaded || layer < 0 || layer >= (int)e->layers.size() || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    snprintf(buf, (size_t)buf_len, "%s", e->layers[layer].name.c_str());
+    return LTK_OK;
+}
+
+int ltk_wav2lip_set_layer_tile(ltk_engine* e, int layer, int bucket, int pxw, int nbt, int ksplit) {
+    if (!e || !e->loaded || layer < 0 || layer >= (int)e->layers.size() || bucket < 0 || bucket > 4) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    Layer::Tile& t = e->layers[layer].tile[bucket];
+    t.pxw = (signed char)pxw; t.nbt = (signed char)nbt; t.ks = (signed char)ksplit;
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->compute);
+    e->graphs.drop();                  // captured passes carry the old tile choice
+    return LTK_OK;
+}
+
+int ltk_wav2lip_time_layers(ltk_engine* e, int frames, int iters, float* ms_per_layer, int n_layers) {
+    if (!e || frames <= 0 || iters <= 0 || !ms_per_layer) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
+    if (frames > e->micro_batch || frames > kPackMaxFrames) return fail(LTK_E_INVALID, "frames exceeds one arena pass");
+    if (n_layers != (int)e->layers.size()) return fail(LTK_E_INVALID, "n_layers != ltk_wav2lip_layer_count");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
+    std::vector<hipEvent_t> evs(e->layers.size() + 1);
+    for (auto& ev : evs) CHK(hipEventCreate(&ev));
+    const bool fused = knob(K_HEAD_FUSED) != 0;
+    TimingIO tio;
+    int rc = tio.setup(e, frames);
+    if (rc) return rc;
+    const OutPtrs* d_outs = fused ? &e->d_tab->outs : nullptr;
+    const FacePtrs* d_faces = (e->c7 && knob(K_CONV7)) ? &e->d_tab->faces : nullptr;
+    std::vector<double> acc(e->layers.size(), 0.0);
+    rc = run_convs(e, frames, e->compute, d_outs, nullptr, d_faces);     // warm
+    for (int it = 0; it < iters && !rc; ++it) {
+        rc = run_convs(e, frames, e->compute, d_outs, &evs, d_faces);
+        if (rc) break;
+        CHK(hipEventSynchronize(evs.back()));
+        for (size_t i = 0; i < e->layers.size(); ++i) {
+            float ms = 0.f;
+            CHK(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
+            acc[i] += ms;
+        }
+    }
+    for (auto& ev : evs) (void)hipEventDestroy(ev);
+    if (rc) return rc;
+    for (size_t i = 0; i < e->layers.size(); ++i) ms_per_layer[i] = (float)(acc[i] / iters);
+    return LTK_OK;
+}
+
+int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
+                   const float* weight, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                   int transposed, int out_pad, const float* scale, const float* shift,
+                   const void* d_res, int relu, void* d_y, int iters, float* ms_avg) {
+    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    ConvPlan plan;
+    std::string err;
+    int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, H * W);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    ConvIO io;
+    io.partial = e->d_partial; io.partial_cap = e->partial_cap;
+    io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;
+    io.y = (f16*)d_y; io.y_ld = Cout; io.y_coff = 0;
+    io.res = (const f16*)d_res; io.res_ld = Cout; io.res_coff = 0;
+    io.relu = relu;
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    rc = conv_launch(plan, io, s, &err);
+    if (!rc && iters > 0 && ms_avg) {
+        hipEvent_t t0, t1;
+        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
+        (void)hipEventRecord(t0, s);
+        for (int i = 0; i < iters && !rc; ++i) rc = conv_launch(plan, io, s, &err);
+        (void)hipEventRecord(t1, s);
+        (void)hipEventSynchronize(t1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        *ms_avg = ms / iters;
+        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    }
+    hipError_t he = hipStreamSynchronize(s);
+    conv_plan_destroy(&plan);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
+    return LTK_OK;
+}
+
+int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
+                      int silu, int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg) {
+    if (!e || !d_x || !d_y || !gamma || !beta || N <= 0 || C <= 0 || P <= 0 || groups <= 0 || C % groups || C % 16 || (out_fp8 && C % 32))
+        return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    const bool fits_group = gn_group_fits(C, P, groups);
+    const int members = gn_coop_members(C, P, groups);
+    if (impl == 0) impl = (knob(K_MT_GN1) && fits_group) ? 2 : (knob(K_GN_COOP) && members) ? 3 : 1;
+    if ((impl == 2 && !fits_group) || (impl == 3 && !members) || impl < 1 || impl > 3) return fail(LTK_E_INVALID, "this GroupNorm kernel does not serve the shape");
+    float *d_gamma = nullptr, *d_beta = nullptr, *d_partial = nullptr;
+    unsigned *d_slots = nullptr, *err_host = nullptr, *err_dev = nullptr;
+    const int segs = gn_segments(N, C, P);
+    const size_t slot_words = (size_t)N * (C / 16) * std::max(members, 1) * 8;
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    int rc = LTK_OK;
+    auto cleanup = [&]() {
+        if (d_gamma) (void)hipFree(d_gamma);
+        if (d_beta) (void)hipFree(d_beta);
+        if (d_partial) (void)hipFree(d_partial);
+        if (d_slots) (void)hipFree(d_slots);
+        if (err_host) (void)hipHostFree(err_host);
+    };
+    if (hipMalloc((void**)&d_gamma, C * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_beta, C * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&d_partial, (size_t)N * (C / 16) * segs * 32 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&d_slots, slot_words * sizeof(unsigned)) != hipSuccess ||
+        hipHostMalloc((void**)&err_host, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&err_dev, err_host, 0) != hipSuccess) { cleanup(); return fail(LTK_E_HIP, "allocation failed"); }
+    *err_host = 0u;
+    (void)hipMemcpyAsync(d_gamma, gamma, C * sizeof(float), hipMemcpyHostToDevice, s);
+    (void)hipMemcpyAsync(d_beta, beta, C * sizeof(float), hipMemcpyHostToDevice, s);
+    const f16* x = (const f16*)d_x;
+    const int ycb = out_fp8 ? C / 32 : C / 16;
+    auto run = [&]() {
+        if (impl == 3) {
+            launch_gn_coop_reset(d_slots, slot_words, s);
+            launch_gn_coop(x, N, C / 16, 0, C, P, groups, eps, d_slots, err_dev, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, out_fp8 ? 1 : 0, out_scale, s);
+        } else if (impl == 2) {
+            launch_gn_group(x, N, C / 16, 0, C, P, groups, eps, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, out_fp8 ? 1 : 0, out_scale, s);
+        } else {
+            launch_gn_stats(x, N, C / 16, 0, C, P, segs, d_partial, s);
+            if (out_fp8) launch_gn_apply_fp8(x, N, C / 16, 0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, out_scale, (unsigned char*)d_y, ycb, 0, s);
+            else launch_gn_apply(x, N, C / 16, 0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, s);
+        }
+    };
+    run();
+    if (iters > 0 && ms_avg) {
+        hipEvent_t t0, t1;
+        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
+        (void)hipEventRecord(t0, s);
+        for (int i = 0; i < iters; ++i) run();
+        (void)hipEventRecord(t1, s);
+        (void)hipEventSynchronize(t1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        *ms_avg = ms / iters;
+        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    }
+    const hipError_t he = hipStreamSynchronize(s);
+    if (he != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, std::string("GroupNorm kernel: ") + hipGetErrorString(he));
+    else if (*reinterpret_cast<volatile unsigned*>(err_host)) rc = fail(LTK_E_HIP, "a cooperative GroupNorm block gave up waiting for its set (gn_coop_kernel)");
+    cleanup();
+    return rc;
+}
+
+int ltk_f32_to_e4m3(const float* in, size_t n, uint8_t* out) {
+    if (!in || !out) return fail(LTK_E_INVALID, "bad arguments");
+    for (size_t i = 0; i < n; ++i) out[i] = f32_to_e4m3(in[i]);
+    return LTK_OK;
+}
+
+int ltk_conv2d_fp8(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout,
+                   const float* scale, const float* shift, float act_scale, const void* d_res, int act, void* d_y, int iters,
+                   float* ms_avg) {
+    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    ConvPlan plan;
+    std::string err;
+    int rc = conv_plan_create(&plan, weight, Cin, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, &err, H * W,
+                              (Cin % 64 == 0 && (knob(K_FP8_MX) == 2 || (knob(K_FP8_MX) == 1 && Cin >= 512))) ? 2 : 1, act_scale);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    ConvIO io;
+    io.partial = e->d_partial; io.partial_cap = e->partial_cap;
+    io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;   // 16-bit units
+    io.y = (f16*)d_y; io.y_ld = Cout; io.y_coff = 0;
+    io.res = (const f16*)d_res; io.res_ld = Cout; io.res_coff = 0;
+    io.relu = 0; io.act = act;
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    rc = conv_launch(plan, io, s, &err);
+    if (!rc && iters > 0 && ms_avg) {
+        hipEvent_t t0, t1;
+        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
+        (void)hipEventRecord(t0, s);
+        for (int i = 0; i < iters && !rc; ++i) rc = conv_launch(plan, io, s, &err);
+        (void)hipEventRecord(t1, s);
+        (void)hipEventSynchronize(t1);
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        *ms_avg = ms / iters;
+        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    }
+    hipError_t he = hipStreamSynchronize(s);
+    conv_plan_destroy(&plan);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
+    return LTK_OK;
+}
+
+int ltk_musetalk_forward_host(ltk_engine* e, const float* latents, const float* feat, int B, float* unet_out, float* image,
+                              uint8_t* frames) {
+    if (!e || !latents || !feat || B <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    if (B > e->mt_max_frames) return fail(LTK_E_INVALID, "B exceeds max_frames");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    hipStream_t s = e->compute;
+    CHK(hipMemcpyAsync(e->d_mt_lat, latents, (size_t)B * 8 * 1024 * sizeof(float), hipMemcpyHostToDevice, s));
+    CHK(hipMemcpyAsync(e->d_mt_feat, feat, (size_t)B * 50 * 384 * sizeof(float), hipMemcpyHostToDevice, s));
+    int cbt;
+    f16* lat = mt_latent_in(e->mt, &cbt);
+    launch_nchw_to_cb16(e->d_mt_lat, B, 8, 1024, lat, cbt, 0, s);
+    float* d_img = nullptr;
+    uint8_t* d_frames = nullptr;
+    if (image) CHK(hipMalloc((void**)&d_img, (size_t)B * 3 * 65536 * sizeof(float)));
+    if (frames) CHK(hipMalloc((void**)&d_frames, (size_t)B * 65536 * 3));
+    OutList64 op;
+    for (int i = 0; i < 64; ++i) op.p[i] = (frames && i < B) ? d_frames + (size_t)i * 65536 * 3 : nullptr;
+    int rc = mt_run_locked(e, e->d_mt_feat, nullptr, B, &op, d_img);
+    if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = fail(LTK_E_HIP, "stream sync failed");
+    if (!rc && unet_out) {
+        int C, ld, coff, H, W;
+        f16* t = mt_named(e->mt, "conv_out", &C, &ld, &coff, &H, &W);
+        float* d_tmp = nullptr;
+        CHK(hipMalloc((void**)&d_tmp, (size_t)B * 4 * 1024 * sizeof(float)));
+        launch_nhwc_to_nchw_f32(t, B, H, W, ld, coff, 4, d_tmp, s);
+        CHK(hipStreamSynchronize(s));
+        CHK(hipMemcpy(unet_out, d_tmp, (size_t)B * 4 * 1024 * sizeof(float), hipMemcpyDeviceToHost));
+        (void)hipFree(d_tmp);
+    }
+    if (!rc && image) CHK(hipMemcpy(image, d_img, (size_t)B * 3 * 65536 * sizeof(float), hipMemcpyDeviceToHost));
+    if (!rc && frames) CHK(hipMemcpy(frames, d_frames, (size_t)B * 65536 * 3, hipMemcpyDeviceToHost));
+    if (d_img) (void)hipFree(d_img);
+    if (d_frames) (void)hipFree(d_frames);
+    return rc;
+}
+
+int ltk_musetalk_debug_get(ltk_engine* e, const char* name, int frames, float* out, size_t n_floats) {
+    if (!e || !name || !out || frames <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->mt, name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no MuseTalk tensor named ") + name);
+    const size_t cnt = (size_t)frames * C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats for these frames");
+    float* d_tmp = nullptr;
+    CHK(hipMalloc((void**)&d_tmp, cnt * sizeof(float)));
+    launch_nhwc_to_nchw_f32(t, frames, H, W, ld, coff, C, d_tmp, e->compute);
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(out, d_tmp, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    (void)hipFree(d_tmp);
+    return LTK_OK;
+}
+
+int ltk_musetalk_op_count(ltk_engine* e) { return (e && e->mt) ? mt_op_count(e->mt) : 0; }
+
+int ltk_musetalk_op_name(ltk_engine* e, int op, char* buf, int buf_len, int* type) {
+    if (!e || !e->mt || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const char* n = mt_op_name(e->mt, op, type);
+    if (!n) return fail(LTK_E_INVALID, "no such op");
+    snprintf(buf, (size_t)buf_len, "%s", n);
+    return LTK_OK;
+}
+
+int ltk_musetalk_time_ops(ltk_engine* e, int frames, int iters, float* ms_per_op, int n_ops) {
+    if (!e || frames <= 0 || iters <= 0 || !ms_per_op) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    if (frames > e->mt_max_frames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
+    if (n_ops != mt_op_count(e->mt)) return fail(LTK_E_INVALID, "n_ops != ltk_musetalk_op_count");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::vector<hipEvent_t> evs((size_t)n_ops + 1);
+    for (auto& ev : evs) CHK(hipEventCreate(&ev));
+    std::vector<double> acc((size_t)n_ops, 0.0);
+    int rc = mt_run(e->mt, frames, e->d_partial, e->partial_cap, e->compute);
+    for (int it = 0; it < iters && !rc; ++it) {
+        rc = mt_run_timed(e->mt, frames, e->d_partial, e->partial_cap, e->compute, &evs);
+        if (rc) break;
+        CHK(hipEventSynchronize(evs.back()));
+        for (int i = 0; i < n_ops; ++i) {
+            float ms = 0.f;
+            CHK(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
+            acc[i] += ms;
+        }
+    }
+    for (auto& ev : evs) (void)hipEventDestroy(ev);
+    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    if (mt_gn_error(e->mt)) return fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
+    for (int i = 0; i < n_ops; ++i) ms_per_op[i] = (float)(acc[i] / iters);
+    return LTK_OK;
+}
+
+int ltk_musetalk_time(ltk_engine* e, int frames, int iters, float* ms_per_pass, double* macs_per_pass) {
+    if (!e || frames <= 0 || iters <= 0 || !ms_per_pass) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    if (frames > e->mt_max_frames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    hipEvent_t t0, t1;
+    CHK(hipEventCreate(&t0));
+    CHK(hipEventCreate(&t1));
+    // as ltk_musetalk_infer enqueues the program: eagerly the first time a frame count is seen, then captured, then replayed
+    int rc = run_program(e, e->mt, frames);
+    if (!rc) rc = run_program(e, e->mt, frames);
+    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    CHK(hipEventRecord(t0, e->compute));
+    for (int i = 0; i < iters && !rc; ++i) rc = run_program(e, e->mt, frames);
+    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    CHK(hipEventRecord(t1, e->compute));
+    CHK(hipEventSynchronize(t1));
+    if (mt_gn_error(e->mt)) return fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
+    float ms = 0.f;
+    CHK(hipEventElapsedTime(&ms, t0, t1));
+    *ms_per_pass = ms / iters;
+    if (macs_per_pass) *macs_per_pass = mt_macs_per_frame(e->mt) * frames;
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    return LTK_OK;
+}
+
+int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats) {
+    if (!e || !name || !out) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    int C, ld, coff, H, W;
+    f16* t = (std::string(name) == "input_features") ? mt_named(e->whisper, "input_features", &C, &ld, &coff, &H, &W) : mt_named(e->whisper, name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no Whisper tensor named ") + name);
+    const size_t cnt = (size_t)C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats");
+    float* d_tmp = nullptr;
+    CHK(hipMalloc((void**)&d_tmp, cnt * sizeof(float)));
+    launch_nhwc_to_nchw_f32(t, 1, H, W, ld, coff, C, d_tmp, e->compute);
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(out, d_tmp, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    (void)hipFree(d_tmp);
+    return LTK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,275 @@
+// MuseTalk (U-Net + VAE decoder), Whisper audio features and the VAE encoder: their entry points and run_program.
+#include "engine_internal.h"
+
+extern "C" {
+
+// ================================================================================ MuseTalk
+int ltk_musetalk_set_fp8(ltk_engine* e, int enable, float act_scale) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->mt) return fail(LTK_E_STATE, "ltk_musetalk_set_fp8 must precede ltk_musetalk_load");
+    e->mt_fp8 = enable ? 1 : 0;
+    e->mt_fp8_ascale = act_scale > 0.f ? act_scale : 8.f;
+    return LTK_OK;
+}
+
+int ltk_musetalk_info(ltk_engine* e, double* macs_per_frame, double* macs_fp8_per_frame) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    if (macs_per_frame) *macs_per_frame = mt_macs_per_frame(e->mt);
+    if (macs_fp8_per_frame) *macs_fp8_per_frame = mt_macs_fp8_per_frame(e->mt);
+    return LTK_OK;
+}
+
+int ltk_musetalk_load(ltk_engine* e, const ltk_named_tensor* unet_sd, int n_unet, const ltk_named_tensor* vae_sd, int n_vae,
+                      int max_frames) {
+    if (!e || !unet_sd || !vae_sd || n_unet <= 0 || n_vae <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (max_frames < 1 || max_frames > 64) return fail(LTK_E_INVALID, "max_frames must be in [1, 64] for MuseTalk");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->mt) return fail(LTK_E_STATE, "a MuseTalk model is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* mg = mt_graph_new();
+    mt_set_sat_counter(mg, e->d_sat);
+    mt_set_fp8(mg, e->mt_fp8, e->mt_fp8_ascale);
+    const int rc = mt_build(mg, unet_sd, n_unet, vae_sd, n_vae, max_frames);
+    if (rc) {
+        const std::string msg = mt_graph_error(mg);
+        mt_graph_delete(mg);
+        return fail(rc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, "musetalk: " + msg);
+    }
+    // avatars/musetalk/models/unet.py:12-27 PositionalEncoding(d_model=384), first 50 positions
+    std::vector<float> pe(50 * 384);
+    for (int pos = 0; pos < 50; ++pos)
+        for (int i = 0; i < 384; i += 2) {
+            const float div = expf((float)i * (-logf(10000.0f) / 384.0f));
+            pe[pos * 384 + i] = sinf((float)pos * div);
+            pe[pos * 384 + i + 1] = cosf((float)pos * div);
+        }
+    const int arc = [&]() -> int {
+        CHK(hipMalloc((void**)&e->d_pe, pe.size() * sizeof(float)));
+        CHK(hipMemcpy(e->d_pe, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice));
+        CHK(hipMalloc((void**)&e->d_mt_feat, (size_t)max_frames * 50 * 384 * sizeof(float)));
+        CHK(hipMalloc((void**)&e->d_mt_lat, (size_t)max_frames * 8 * 1024 * sizeof(float)));
+        return LTK_OK;
+    }();
+    if (arc) {                                       // a failed load leaves nothing behind and can be retried
+        if (e->d_pe) { (void)hipFree(e->d_pe); e->d_pe = nullptr; }
+        if (e->d_mt_feat) { (void)hipFree(e->d_mt_feat); e->d_mt_feat = nullptr; }
+        if (e->d_mt_lat) { (void)hipFree(e->d_mt_lat); e->d_mt_lat = nullptr; }
+        mt_graph_delete(mg);
+        return arc;
+    }
+    e->mt = mg;
+    e->mt_max_frames = max_frames;
+    return LTK_OK;
+}
+
+int ltk_musetalk_avatar_register(ltk_engine* e, const float* latents, const uint8_t* full_bank, const int32_t* face_boxes,
+                                 const int32_t* crop_boxes, const uint8_t* masks, const int64_t* mask_offsets, int n, int H,
+                                 int W, int* avatar_id) {
+    if (!e || !latents || !full_bank || !face_boxes || !crop_boxes || !masks || !mask_offsets || !avatar_id || n <= 0 || H <= 0 || W <= 0)
+        return fail(LTK_E_INVALID, "bad arguments");
+    for (int i = 0; i < n; ++i) {
+        const int32_t* f = face_boxes + 4 * i;   // (x1,y1,x2,y2), musetalk_avatar.py:157
+        const int32_t* c = crop_boxes + 4 * i;   // (x_s,y_s,x_e,y_e), myutil.py:7
+        if (c[0] < 0 || c[1] < 0 || c[2] > W || c[3] > H || c[2] <= c[0] || c[3] <= c[1])
+            return fail(LTK_E_INVALID, "crop box outside the frame (the reference's slicing is undefined there)");
+        if (f[0] < c[0] || f[1] < c[1] || f[2] > c[2] || f[3] > c[3] || f[2] <= f[0] || f[3] <= f[1])
+            return fail(LTK_E_INVALID, "face box must lie inside its crop box");
+        if (mask_offsets[i + 1] - mask_offsets[i] != (int64_t)(c[3] - c[1]) * (c[2] - c[0]) * 3)
+            return fail(LTK_E_INVALID, "mask size does not match its crop box");
+    }
+    CHK(enter_device(e->device));
+    auto ap = std::make_shared<MtAvatar>();
+    MtAvatar& a = *ap;
+    a.device = e->device;
+    a.n = n; a.H = H; a.W = W;
+    a.face_box.assign(face_boxes, face_boxes + 4 * (size_t)n);
+    a.crop_box.assign(crop_boxes, crop_boxes + 4 * (size_t)n);
+    a.mask_off.assign(mask_offsets, mask_offsets + n + 1);
+    const size_t lb = (size_t)n * 8 * 1024 * sizeof(float), ub = (size_t)n * H * W * 3, mb = (size_t)mask_offsets[n];
+    CHK(hipMalloc((void**)&a.d_latents, lb));
+    CHK(hipMalloc((void**)&a.d_full, ub));
+    CHK(hipMalloc((void**)&a.d_masks, mb));
+    CHK(hipMemcpy(a.d_latents, latents, lb, hipMemcpyHostToDevice));
+    CHK(hipMemcpy(a.d_full, full_bank, ub, hipMemcpyHostToDevice));
+    CHK(hipMemcpy(a.d_masks, masks, mb, hipMemcpyHostToDevice));
+    std::lock_guard<std::mutex> g(e->pool_mu);
+    const int id = e->next_avatar++;
+    e->mt_avatars[id] = ap;
+    *avatar_id = id;
+    return LTK_OK;
+}
+
+}  // extern "C"
+
+// One run of a device program (the U-Net + VAE decoder pass, the Whisper encoder) on the compute stream, under e->mu.  Every op
+// of a program reads and writes the program's own persistent buffers with launch arguments that depend on the frame count only,
+// so the whole launch list (436 launches for a MuseTalk pass, ~60 for a Whisper step) is captured as ONE hipGraph the second time a
+// (program, frame count) is seen and replayed from then on (knob GRAPH, as for the Wav2Lip pass: the first, eager run also sets
+// every kernel's dynamic-LDS attribute, which a capture must not do).  The kernels that carry per-call pointers - latent / token
+// gather in front, uint8 frame writer behind - stay outside the graph.  What this buys is the host side: one launch per pass
+// instead of hundreds, on a host that also runs the sessions' Python.
+int ltk::run_program(ltk_engine* e, MtGraph* prog, int nf) {
+    hipStream_t s = e->compute;
+    auto enq = [&]() -> int { return mt_run(prog, nf, e->d_partial, e->partial_cap, s); };
+    return knob(K_GRAPH) ? e->prog_graphs.run(e, {(const void*)prog, nf}, s, "program", nf, enq) : enq();
+}
+
+// latents already gathered into the graph's latent tensor; d_feat = fp32 [nf][50][384] on the device
+int ltk::mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat_ptrs, int nf, const OutList64* outs, float* d_image_f32) {
+    hipStream_t s = e->compute;
+    int cbt;
+    f16* ctx = mt_ctx_in(e->mt, &cbt);
+    if (feat_ptrs) launch_tokens_gather_to_cb16(*feat_ptrs, nf, 50, 384, e->d_pe, ctx, cbt, s);
+    else launch_tokens_to_cb16(d_feat, nf, 50, 384, e->d_pe, ctx, cbt, 0, s);
+    const int rc = run_program(e, e->mt, nf);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    if (outs || d_image_f32) {
+        OutList64 none;
+        for (int i = 0; i < 64; ++i) none.p[i] = nullptr;
+        f16* img = mt_vae_out(e->mt, &cbt);
+        launch_vae_post(img, cbt, nf, 65536, outs ? *outs : none, d_image_f32, s);
+    }
+    CHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int ltk_musetalk_infer(ltk_engine* e, const ltk_mt_req* reqs, int nreq, void* stream) {
+    if (!e || !reqs || nreq <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
+    CHK(enter_device(e->device));
+    std::vector<const float*> lptr, fptr;
+    std::vector<uint8_t*> optr;
+    std::vector<std::shared_ptr<MtAvatar>> hold;      // the banks stay alive until this call has synchronised
+    for (int r = 0; r < nreq; ++r) {
+        hold.push_back(find_mt_avatar(e, reqs[r].avatar));
+        if (!hold.back()) return fail(LTK_E_STATE, "unknown MuseTalk avatar id");
+        if (reqs[r].batch <= 0 || reqs[r].index < 0 || !reqs[r].d_feat || !reqs[r].d_pred) return fail(LTK_E_INVALID, "bad request");
+        const MtAvatar& a = *hold.back();
+        for (int i = 0; i < reqs[r].batch; ++i) {
+            const int idx = mirror_index(a.n, reqs[r].index + i);   // musetalk_avatar.py:137-139
+            lptr.push_back(a.d_latents + (size_t)idx * 8 * 1024);
+            fptr.push_back((const float*)reqs[r].d_feat + (size_t)i * 50 * 384);
+            optr.push_back((uint8_t*)reqs[r].d_pred + (size_t)i * 65536 * 3);
+        }
+    }
+    const int total = (int)lptr.size();
+    int rc = infer_call(e, stream, [&]() -> int {
+        int rc = 0;
+        for (int f0 = 0; f0 < total && !rc; f0 += e->mt_max_frames) {
+            const int nf = std::min(e->mt_max_frames, total - f0);
+            PtrList64 lp, fp;
+            OutList64 op;
+            for (int i = 0; i < 64; ++i) { lp.p[i] = nullptr; fp.p[i] = nullptr; op.p[i] = nullptr; }
+            for (int i = 0; i < nf; ++i) { lp.p[i] = lptr[f0 + i]; fp.p[i] = fptr[f0 + i]; op.p[i] = optr[f0 + i]; }
+            int cbt;
+            f16* lat = mt_latent_in(e->mt, &cbt);
+            launch_gather_latents(lp, nf, 8, 1024, lat, cbt, e->compute);
+            rc = mt_run_locked(e, nullptr, &fp, nf, &op, nullptr);
+        }
+        return rc;
+    });
+    if (!rc && mt_gn_error(e->mt)) rc = fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
+    return rc;
+}
+
+// ================================================================================ Whisper audio features
+int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n) {
+    if (!e || !encoder_sd || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->whisper) return fail(LTK_E_STATE, "a Whisper encoder is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* wg = mt_graph_new();
+    if (mt_build_whisper_graph(wg, encoder_sd, n)) {
+        const std::string msg = mt_graph_error(wg);
+        mt_graph_delete(wg);
+        return fail(LTK_E_INVALID, "whisper: " + msg);
+    }
+    std::vector<float> basis;
+    std::vector<int32_t> lohi;
+    build_mel_basis(&basis, &lohi, 201, 0.0, 8000.0);     // WhisperFeatureExtractor.mel_filters (slaney, 80 x 201)
+    CHK(hipMalloc((void**)&e->d_wbasis, basis.size() * sizeof(float)));
+    CHK(hipMemcpy(e->d_wbasis, basis.data(), basis.size() * sizeof(float), hipMemcpyHostToDevice));
+    CHK(hipMalloc((void**)&e->d_wlogspec, (size_t)80 * 3000 * sizeof(float)));
+    CHK(hipMalloc((void**)&e->d_wpcm, (size_t)480000 * sizeof(float)));
+    CHK(hipMalloc((void**)&e->d_wgmax, 16));
+    e->whisper = wg;
+    return LTK_OK;
+}
+
+int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out,
+                     void* stream) {
+    if (!e || !pcm || !d_out || n_samples <= 0 || n_samples > 479000 || batch <= 0 || rows <= 0 || rows > 64)
+        return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
+    CHK(enter_device(e->device));
+    return infer_call(e, stream, [&]() -> int {
+        hipStream_t s = e->compute;
+        CHK(hipMemcpyAsync(e->d_wpcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+        int cbt, cb0;
+        f16* mel = mt_latent_in(e->whisper, &cbt);
+        launch_whisper_logmel(e->d_wpcm, n_samples, e->d_wbasis, e->d_wlogspec, e->d_wgmax, mel, s);
+        int rc = run_program(e, e->whisper, 1);
+        if (rc) rc = fail(LTK_E_INVALID, std::string("whisper: ") + mt_graph_error(e->whisper));
+        if (!rc) {
+            WhisperStates st;
+            for (int i = 0; i < 5; ++i) { st.p[i] = mt_whisper_state(e->whisper, i, &cbt, &cb0); st.cb0[i] = cb0; }
+            launch_whisper_chunks(st, 1500, batch, first_row, row_step, rows, (float*)d_out, s);
+            if (hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, "whisper kernels failed to launch");
+        }
+        return rc;
+    });
+}
+
+// ================================================================================ VAE encoder (avatar preparation)
+int ltk_vae_encoder_load(ltk_engine* e, const ltk_named_tensor* vae_sd, int n, int max_faces) {
+    if (!e || !vae_sd || n <= 0 || max_faces < 1 || max_faces > 32) return fail(LTK_E_INVALID, "bad arguments (max_faces in [1,32])");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->vae_enc) return fail(LTK_E_STATE, "a VAE encoder is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* vg = mt_graph_new();
+    if (mt_build_vae_encoder_graph(vg, vae_sd, n, 2 * max_faces)) {
+        const std::string msg = mt_graph_error(vg);
+        mt_graph_delete(vg);
+        return fail(LTK_E_INVALID, "vae encoder: " + msg);
+    }
+    e->vae_enc = vg;
+    e->vae_enc_faces = max_faces;
+    return LTK_OK;
+}
+
+int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, const float* noise, float* latents_out) {
+    if (!e || !faces_bgr || !latents_out || nfaces <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->vae_enc) return fail(LTK_E_STATE, "ltk_vae_encoder_load has not been called");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    hipStream_t s = e->compute;
+    uint8_t* d_faces = nullptr;
+    float *d_noise = nullptr, *d_out = nullptr;
+    const int cap = e->vae_enc_faces;
+    CHK(hipMalloc((void**)&d_faces, (size_t)cap * 65536 * 3));
+    CHK(hipMalloc((void**)&d_out, (size_t)cap * 8 * 1024 * sizeof(float)));
+    if (noise) CHK(hipMalloc((void**)&d_noise, (size_t)cap * 2 * 4 * 1024 * sizeof(float)));
+    int rc = 0;
+    for (int f0 = 0; f0 < nfaces && !rc; f0 += cap) {
+        const int nf = std::min(cap, nfaces - f0);
+        CHK(hipMemcpyAsync(d_faces, faces_bgr + (size_t)f0 * 65536 * 3, (size_t)nf * 65536 * 3, hipMemcpyHostToDevice, s));
+        if (noise) CHK(hipMemcpyAsync(d_noise, noise + (size_t)f0 * 2 * 4 * 1024, (size_t)nf * 2 * 4 * 1024 * sizeof(float), hipMemcpyHostToDevice, s));
+        int cbt;
+        launch_vae_pre(d_faces, nf, mt_latent_in(e->vae_enc, &cbt), s);
+        rc = mt_run(e->vae_enc, 2 * nf, e->d_partial, e->partial_cap, s);
+        if (rc) { rc = fail(LTK_E_INVALID, std::string("vae encoder: ") + mt_graph_error(e->vae_enc)); break; }
+        launch_vae_latents(mt_unet_out(e->vae_enc, &cbt), nf, noise ? d_noise : nullptr, 0.18215f, d_out, s);
+        CHK(hipMemcpyAsync(latents_out + (size_t)f0 * 8 * 1024, d_out, (size_t)nf * 8 * 1024 * sizeof(float), hipMemcpyDeviceToHost, s));
+        CHK(hipStreamSynchronize(s));
+        if (mt_gn_error(e->vae_enc)) { rc = fail(LTK_E_HIP, std::string("vae encoder: ") + mt_graph_error(e->vae_enc)); break; }
+    }
+    (void)hipFree(d_faces); (void)hipFree(d_out);
+    if (d_noise) (void)hipFree(d_noise);
+    return rc;
+}
+
+}  // extern "C"

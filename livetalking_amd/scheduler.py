@@ -43,8 +43,8 @@ class _Req:
 class BatchingScheduler:
     """Continuous batching with up to LTK_INFLIGHT (default 2) engine calls in flight.
 
-    The engine serialises calls on one stream and releases its enqueue lock before it waits (csrc/engine.hip,
-    ltk_wav2lip_infer), so a second call issued while the first still runs queues its launches right behind the first
+    The engine serialises calls on one stream and releases its enqueue lock before it waits (csrc/engine_internal.h infer_call,
+    under ltk_wav2lip_infer), so a second call issued while the first still runs queues its launches right behind the first
     call's kernels: the GPU does not idle through the host turn-around between two calls (completion wake-up, Python,
     ctypes, launch: ~75 us of a 1.3-ms step, ~1 ms of a 16-ms 256-frame step with 16 session threads).  To keep batches
     as large as they are with one call in flight, the second call is not issued when the first request arrives but

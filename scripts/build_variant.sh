@@ -9,8 +9,11 @@ SRC=${SRC:-$ROOT/livetalking_amd/csrc}
 OBJ=$ROOT/build/$NAME
 mkdir -p $OBJ $ROOT/ab_libs
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $*"
-pids=()
-for f in tune conv_mfma conv3_mfma conv7_mfma rowgemm misc_kernels egress_kernels nn_kernels musetalk engine; do
+# the source list is the Makefile's (as scripts/kernel_resources.py reads it): a new source cannot be forgotten here
+SRCS=$(sed -n 's/^SRCS *= *//p' $SRC/Makefile)
+pids=(); objs=()
+for f in ${SRCS//.hip/}; do
+  objs+=($OBJ/$f.o)
   extra=""
   case $f in misc_kernels|egress_kernels) extra="-ffp-contract=off";; nn_kernels) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
   if [ ! -f $OBJ/$f.o ] || [ $SRC/$f.hip -nt $OBJ/$f.o ] || [ -n "$(find $SRC -name '*.h' -newer $OBJ/$f.o)" ] || [ -n "$FORCE" ]; then
@@ -19,5 +22,5 @@ for f in tune conv_mfma conv3_mfma conv7_mfma rowgemm misc_kernels egress_kernel
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/ab_libs/libltk_hip_$NAME.so $OBJ/*.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $ROOT/ab_libs/libltk_hip_$NAME.so "${objs[@]}"
 echo built ab_libs/libltk_hip_$NAME.so

@@ -5,7 +5,7 @@ For every conv3 layer and every frame-count bucket: set that ONE layer's entry o
 candidate (ltk_wav2lip_set_layer_tile), time the WHOLE pass layer by layer (ltk_wav2lip_time_layers: HIP events between
 consecutive launches, so the layer sees the cache state its predecessor left) and keep the candidate with the
 smallest time for that layer.  Tiles never change an output element's summation order; split factors do, so the
-split is only tuned where the rule would split anyway.  Prints a C table for engine.hip and writes
+split is only tuned where the rule would split anyway.  Prints a C table for w2l_program.hip and writes
 gpurun_out/tile_tune.json.
 
     TUNE_FRAMES=16,32,64,128,256 python scripts/tile_tune.py
@@ -70,7 +70,7 @@ def main():
         ms, _ = eng.time_convs(nf, 10)
         print(f"==== {nf} frames: tuned pass {tuned.sum()*1e3:.0f} us (rule {base.sum()*1e3:.0f}); two-stream conv stack {ms*1e3:.0f} us")
         result[nf] = {"rule_pass_us": base.sum() * 1e3, "tuned_pass_us": tuned.sum() * 1e3, "conv_stack_us": ms * 1e3, "layers": best}
-    print("\n// ---- table for engine.hip (layer prefix, bucket, pxw, nbt, ksplit)")
+    print("\n// ---- table for w2l_program.hip (layer prefix, bucket, pxw, nbt, ksplit)")
     for nf in frames:
         for name, r in result[nf]["layers"].items():
             if tuple(r["pick"]) != (0, 0, 0):

@@ -26,7 +26,7 @@ import numpy as np
 
 # (state_dict prefix, kind, cin, cout, k, stride_product, residual) for the 54 Conv2d/Conv2dTranspose
 # blocks of avatars/wav2lip/models/wav2lip_v2.py:12-89, in state_dict order: only what the
-# generator needs (shapes + fan-in).  The engine's own table lives in csrc/engine.hip.
+# generator needs (shapes + fan-in).  The engine's own table lives in csrc/w2l_program.hip.
 def _layers():
     L = []
     def c(p, cin, cout, k, s=1, res=False): L.append((p, "conv", cin, cout, k, s, res))

@@ -496,7 +496,7 @@ def test_abi_argument_validation_without_gpu():
 
 
 def test_tile_table_entries_name_existing_layers_and_legal_tiles():
-    """csrc/engine.hip kTileTable is keyed by layer-name strings and was tuned on single boxes: every entry must name a layer
+    """csrc/w2l_program.hip kTileTable is keyed by layer-name strings and was tuned on single boxes: every entry must name a layer
     of the network description, a frame-count bucket and a tile / split conv3 has an instantiation for (device-free check
     inside the library, include/ltk.h ltk_debug_tile_table_check); the table itself is read from the source here so that the
     test also notices an entry the C side does not parse as expected."""
@@ -507,7 +507,7 @@ def test_tile_table_entries_name_existing_layers_and_legal_tiles():
     buf = C.create_string_buffer(4096)
     bad = lib.ltk_debug_tile_table_check(buf, len(buf))
     assert bad == 0, buf.value.decode()
-    src = open(os.path.join(ROOT, "livetalking_amd", "csrc", "engine.hip")).read()
+    src = open(os.path.join(ROOT, "livetalking_amd", "csrc", "w2l_program.hip")).read()
     table = src[src.index("const TileEntry kTileTable[] = {"):]
     table = table[:table.index("};")]
     entries = re.findall(r'\{"([a-z_.0-9]+)",\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+)\}', table)
@@ -563,7 +563,7 @@ def test_kernel_resources_script_follows_the_makefile():
         for o in objs.split():
             extra.setdefault(o.replace(".o", ".hip"), []).extend(flags.split())
     assert kr.EXTRA == extra
-    assert set(kr.makefile_sources()) >= set(extra) and len(kr.makefile_sources()) == 10
+    assert set(kr.makefile_sources()) >= set(extra) and len(kr.makefile_sources()) == 15
     # the name shortener on the two kinds of names the compiler's remarks carry
     assert kr.pretty("_ZN3ltk14convs2d_kernelILi2EEEvPKDF16_ii", "_ZN3ltk14convs2d_kernelILi2EEEvPKDF16_ii") == "ltk::convs2d_kernel<2>"
     assert kr.pretty("x", "void ltk::conv7_kernel<true>(ltk::C7Args, ltk::FacePtrs const*)") == "ltk::conv7_kernel<true>"

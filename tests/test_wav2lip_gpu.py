@@ -565,7 +565,7 @@ def test_graph_replay_equals_eager_launches(engine, golden_dir):
 
 @pytest.mark.gpu
 def test_tile_table_off_equals_table_on_within_one_lsb(engine, golden_dir):
-    """The measured per-layer tile table (csrc/engine.hip kTileTable, knob TILE_TABLE) only moves work between tile shapes and
+    """The measured per-layer tile table (csrc/w2l_program.hip kTileTable, knob TILE_TABLE) only moves work between tile shapes and
     split factors: with it disabled (conv3's rule alone) a 16-frame and a 64-frame call must give the same frames - tiles never
     change a sum's order, the few split-factor entries do (fixed-order split-K: <= 1 LSB on a small share of the bytes)."""
     from livetalking_amd.engine import Engine
@@ -665,7 +665,7 @@ def test_face_cache_mode_equals_mode_off(golden_dir):
 @pytest.mark.gpu
 def test_prefetch_slots_serve_interleaved_sessions(golden_dir):
     """Round 6: the prefetched face-encoder outputs live in an LRU of slots keyed by (avatar, next bank index, frame count)
-    (csrc/engine.hip PfSlot; round 5 kept ONE engine-wide slot, which interleaved sessions never hit).  Three paced sessions call
+    (csrc/engine_internal.h PfSlot; round 5 kept ONE engine-wide slot, which interleaved sessions never hit).  Three paced sessions call
     round-robin - two of them on the SAME avatar at different bank positions, one on another avatar - then one session jumps, one
     avatar is released and a new session starts on a new avatar.  Every call's frames equal the knob off byte for byte, and every
     call except the first two of each sequence (the one that starts it, the one that proves it continues) starts at the decoder."""
