@@ -592,6 +592,7 @@ int mt_build_unet(MtGraph& g, const ltk_named_tensor* t, int n, MtTensor* latent
     *latent_in = g.alloc(8, 32, 32);         // 16-channel block, 8 real
     *ctx_in = g.alloc(384, 50, 1);
     g.named["latent_in"] = *latent_in;
+    g.named["encoder_hidden_states"] = *ctx_in;      // the position-encoded audio context as the pass wrote it (debug read-back only)
 
     // Hoisted cross-attention k | v (MT_FUSE bit 1): the k and v projections of the 16 cross-attentions read the audio context
     // only, so they are ONE stacked 384 -> 25 600 projection at the head of the pass (rows [k_0 | v_0 | k_1 | v_1 ...], heads padded

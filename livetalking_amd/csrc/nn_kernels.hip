@@ -477,12 +477,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* __restrict__ 
     const bool ok = p < P;
     const int items = C >> 3;
     const f16* xb = x + ((size_t)(n * cbt + cb0) * P) * 16;
+    // Sums of (x - k) with k = the token's first channel: var = E[(x-k)^2] - E[x-k]^2 then cancels digits in proportion to
+    // ((mean - k) / std)^2, a few units, instead of (mean / std)^2 (4096 for a token whose mean is 64 standard deviations: the
+    // un-shifted sums left rstd 3e-4 off there, tests/test_op_replay_gpu.py)
+    const float k = ok ? (float)xb[(size_t)p * 16] : 0.f;
     float s = 0.f, q = 0.f;
     if (ok) {
         for (int i = part; i < items; i += 16) {
             const f16x8 v = *reinterpret_cast<const f16x8*>(xb + ((size_t)(i >> 1) * P + p) * 16 + (i & 1) * 8);
 #pragma unroll
-            for (int c = 0; c < 8; ++c) { const float f = (float)v[c]; s += f; q += f * f; }
+            for (int c = 0; c < 8; ++c) { const float f = (float)v[c] - k; s += f; q += f * f; }
         }
     }
     red[0][tok][part] = s;
@@ -491,8 +495,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const f16* __restrict__ 
     float S = 0.f, Q = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { S += red[0][tok][i]; Q += red[1][tok][i]; }
-    const float mean = S / (float)C;
-    const float rstd = rsqrtf(fmaxf(Q / (float)C - mean * mean, 0.f) + eps);
+    const float dm = S / (float)C;
+    const float mean = k + dm;
+    const float rstd = rsqrtf(fmaxf(Q / (float)C - dm * dm, 0.f) + eps);
     if (!ok) return;
     f16* yb = y + ((size_t)(n * y_cbt + y_cb0) * P) * 16;
     for (int i = part; i < items; i += 16) {

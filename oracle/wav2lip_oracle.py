@@ -187,9 +187,20 @@ def _block(x: torch.Tensor, sd: Dict[str, torch.Tensor], l: LayerSpec) -> torch.
     return F.relu(y)
 
 
+def _forced(force, name: str, t: torch.Tensor, op: dict) -> torch.Tensor:
+    """With `force`: continue with what force(name, t) returns (None: with t); a force object with a `describe` method is told the
+    op first (layer spec and input tensor: oracle/op_replay.py builds its rounding model and its bound from that)."""
+    if force is None:
+        return t
+    if hasattr(force, "describe"):
+        force.describe(name, op)
+    r = force(name, t)
+    return t if r is None else r
+
+
 @torch.no_grad()
 def forward(sd: Dict[str, torch.Tensor], mel: torch.Tensor, face: torch.Tensor,
-            taps: Dict[str, torch.Tensor] | None = None) -> torch.Tensor:
+            taps: Dict[str, torch.Tensor] | None = None, force=None) -> torch.Tensor:
     """wav2lip_v2.py:123-163 for 4-D inputs (the only case the render loop uses).
 
     mel  (B,1,80,16) fp32, face (B,6,256,256) fp32 in [0,1] -> (B,3,256,256) in (0,1).
@@ -198,7 +209,7 @@ def forward(sd: Dict[str, torch.Tensor], mel: torch.Tensor, face: torch.Tensor,
     """
     x = mel
     for l in AUDIO_ENCODER:
-        x = _block(x, sd, l)
+        x = _forced(force, l.prefix, _block(x, sd, l), dict(kind="w2l", x=x, layer=l))
         if taps is not None:
             taps[l.prefix] = x
     audio_embedding = x  # (B,512,1,1)
@@ -207,7 +218,7 @@ def forward(sd: Dict[str, torch.Tensor], mel: torch.Tensor, face: torch.Tensor,
     x = face
     for blk in FACE_ENCODER_BLOCKS:
         for l in blk:
-            x = _block(x, sd, l)
+            x = _forced(force, l.prefix, _block(x, sd, l), dict(kind="w2l", x=x, layer=l))
             if taps is not None:
                 taps[l.prefix] = x
         feats.append(x)
@@ -215,14 +226,14 @@ def forward(sd: Dict[str, torch.Tensor], mel: torch.Tensor, face: torch.Tensor,
     x = audio_embedding
     for blk in FACE_DECODER_BLOCKS:
         for l in blk:
-            x = _block(x, sd, l)
+            x = _forced(force, l.prefix, _block(x, sd, l), dict(kind="w2l", x=x, layer=l))
             if taps is not None:
                 taps[l.prefix] = x
         x = torch.cat((x, feats[-1]), dim=1)  # wav2lip_v2.py:146
         feats.pop()
 
-    x = _block(x, sd, OUTPUT_CONV)
+    x = _forced(force, OUTPUT_CONV.prefix, _block(x, sd, OUTPUT_CONV), dict(kind="w2l", x=x, layer=OUTPUT_CONV))
     if taps is not None:
         taps[OUTPUT_CONV.prefix] = x
-    x = F.conv2d(x, sd[OUTPUT_HEAD_PREFIX + ".weight"], sd[OUTPUT_HEAD_PREFIX + ".bias"])
-    return torch.sigmoid(x)
+    y = F.conv2d(x, sd[OUTPUT_HEAD_PREFIX + ".weight"], sd[OUTPUT_HEAD_PREFIX + ".bias"])
+    return _forced(force, OUTPUT_HEAD_PREFIX, torch.sigmoid(y), dict(kind="w2l_head", x=x))
