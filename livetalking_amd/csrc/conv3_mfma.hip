@@ -1361,7 +1361,7 @@ bool conv3_lin_fk_k(int Cin) { return Cin == 320 || Cin == 640 || Cin == 512 || 
 // one round; 2 / 3: forced.
 int conv3_lin_mp_nsl(int Cin, long long rows, int Cout) {
     const int kn = knob(K_LIN_MP);
-    if (!kn || !knob(K_LIN_FK) || !(Cin == 2560 || Cin == 5120) || rows < knob(K_LIN_FK_MIN_ROWS) || Cout % 16) return 0;
+    if (!kn || !knob(K_LIN_FK) || !(Cin == 2560 || Cin == 5120) || rows < kLinFkMinRows || Cout % 16) return 0;
     if (kn == 2 || kn == 3) return kn;
     const long long mt = (rows + 127) / 128;
     const int nslabs = (Cout + 31) / 32;
@@ -1472,7 +1472,7 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         if (S == 2) PW = (PW + 1) & ~1;                      // the stride-2 LDS image permutes units inside aligned pixel pairs of a row
         // stride-1 images: column key on 32-pixel tile rows, row key below (header); 8-pixel rows with a halo need a row pitch of 12 pixels for it
         swz_x = 1; swz_row = 0;
-        if (S == 1 && l2w <= 4 && knob(K_LDS_SWZ)) {
+        if (S == 1 && l2w <= 4) {
             swz_x = 0; swz_row = 1;
             if (l2w == 3 && ext > 0) PW = 12;
         }
@@ -1486,8 +1486,9 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tiles_n = tiles_n;
         return (NC8 / 2) * SLOTS <= k3_maxa(pxw, NC8, S, T) * 256 && npix < 32768;
     };
+    const bool conv3x3 = G == 1 && T == 9 && S == 1;
     bool fit;
-    if (G == 1 && T == 9 && S == 1 && kn_pxw == 0 && kn_nbt == 0 && knob(K_TILE_RULE)) {
+    if (conv3x3 && kn_pxw == 0 && kn_nbt == 0) {
         // 3x3 stride 1: the largest tile that still gives the chip ~1.5 items per CU.  Measured per layer and frame count
         // (scripts/conv_sweep2.py, profiles/r02_conv_sweep.txt): with fewer items a launch runs one wave per SIMD and
         // cannot hide its own DMA latency -- at 16 frames 128 ch @32^2 takes 22.8 us as 128 items of 256 px x 64 ch and
@@ -1511,7 +1512,8 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         fit = geom(PXW);
         if (PXW == 4) {
             const long long nt = (p.lCout + 32 * NBT - 1) / (32 * NBT);
-            if (!fit || (!forced_tile && blocks * nt < knob(K_CONV_PXW4_MIN))) { PXW = 2; fit = geom(PXW); }
+            constexpr int kPxw4MinItems = 448;      // a forced 512-pixel tile only when it still gives this many items
+            if (!fit || (!forced_tile && blocks * nt < kPxw4MinItems)) { PXW = 2; fit = geom(PXW); }
         }
     }
     if (!fit) { if (err) *err = "conv3: patch does not fit the staging budget"; return -1; }
@@ -1519,12 +1521,12 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     if (T == 1 && NC8 == 4 && G == 1 && p.lCout % 128 == 0 && ((blocks * (p.lCout / 128) >= 384 && kn_nbt == 0) || kn_nbt == 4)) NBT = 4;
     // (1x1 / linear layers on >= 1024 pixels: below one item per CU; MuseTalk's 640-channel projections on 4096 tokens are 10 %
     // faster as 320 items of 256 px x 32 ch than as 160 of 256 x 64)
-    if (NBT == 2 && blocks * ((p.lCout + 63) / 64) < ((T == 1 && blocks >= 4) ? 256 : 128) && !(G == 1 && T == 9 && S == 1 && knob(K_TILE_RULE)) && !forced_tile) NBT = 1;
+    if (NBT == 2 && blocks * ((p.lCout + 63) / 64) < ((T == 1 && blocks >= 4) ? 256 : 128) && !conv3x3 && !forced_tile) NBT = 1;
     const int BN = NBT * 32;
     a.n_ntiles = (p.lCout + BN - 1) / BN;
     a.ablate = LTK_ABLATE_BUILD ? knob(K_ABLATE) : 0;
     // LTK_SPLITK=0: never split (batch-size independent summation order); LTK_KSPLIT=n forces a factor (sweeps)
-    int ksplit = knob(K_SPLITK) ? k3_ksplit(blocks * a.n_ntiles, a.nchunks, (T == 1 || !knob(K_TILE_RULE)) ? 0 : (G == 4 ? 8 : 4)) : 1;
+    int ksplit = knob(K_SPLITK) ? k3_ksplit(blocks * a.n_ntiles, a.nchunks, T == 1 ? 0 : (G == 4 ? 8 : 4)) : 1;
     const int fks = io.force_ksplit ? io.force_ksplit : knob(K_KSPLIT);
     if (fks > 0 && knob(K_SPLITK)) ksplit = std::max(1, std::min(std::min(fks, kMaxKSplit), a.nchunks));
     if (io.head_w != nullptr && io.head_outs != nullptr) ksplit = 1;      // the fused head finishes in the epilogue: no partial slabs
@@ -1542,7 +1544,7 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     // short-K linear layers on many tokens: lin_fk_kernel (A rows in registers, full-K weight slabs through LDS)
     const int mp_nsl = (G == 1 && T == 1 && S == 1) ? conv3_lin_mp_nsl(p.Cin, a.Mtot, p.lCout) : 0;
     if (G == 1 && T == 1 && S == 1 && !p.q8 && !p.mx && !a.ups && !p.gemm_1x1_expand && knob(K_LIN_FK) && (conv3_lin_fk_k(p.Cin) || mp_nsl) &&
-        a.nchunks * NC8 * 8 == p.Cin && a.Mtot >= knob(K_LIN_FK_MIN_ROWS) && a.ablate == 0 && p.lCout % 16 == 0 &&
+        a.nchunks * NC8 * 8 == p.Cin && a.Mtot >= kLinFkMinRows && a.ablate == 0 && p.lCout % 16 == 0 &&
         (a.relu == 0 || a.relu == 1 || a.relu == 4)) {
         const int nslabs = (p.lCout + 31) / 32;
         if (mp_nsl) {          // lin_mp_kernel: passes of 1280 channels, NSL slabs' accumulators per block
@@ -1559,8 +1561,10 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
             return 0;
         }
         const long long mtiles = (a.Mtot + 127) / 128;
+        // blocks a launch aims at: the output channels are split into groups of slabs until the grid has this many
         // (K = 1280: one 8-wave block per CU)
-        const int want = p.Cin == 1280 ? knob(K_LIN_FK_BLOCKS) / 2 : knob(K_LIN_FK_BLOCKS);
+        constexpr int kLinFkBlocks = 512;
+        const int want = p.Cin == 1280 ? kLinFkBlocks / 2 : kLinFkBlocks;
         int ngroups = (int)std::max(1ll, std::min((long long)nslabs, (want + mtiles - 1) / mtiles));
         const int cpg = (nslabs + ngroups - 1) / ngroups;
         ngroups = (nslabs + cpg - 1) / cpg;
@@ -1613,8 +1617,8 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     if (nblk <= 0 || nblk > 0x7fffffffll) { if (err) *err = "bad grid"; return -1; }
     HIPCHK3((hipError_t)ensure_dyn_lds((const void*)k, 160 * 1024));
     a.nitems = (int)nblk;
-    const int persist_blocks = knob(K_CONV_PERSIST);      // 0: one block per item
-    const long long grid = (persist_blocks > 0 && nblk > persist_blocks) ? persist_blocks : nblk;
+    constexpr int kPersistBlocks = 512;      // resident grid size above which a launch walks its items persistently
+    const long long grid = nblk > kPersistBlocks ? kPersistBlocks : nblk;
     if (head) {
         typedef void (*k3_head_t)(const K3Args, const HeadArgs);
         const k3_head_t kh = PXW == 4 ? (k3_head_t)conv3_head_kernel<4> : (k3_head_t)conv3_head_kernel<2>;

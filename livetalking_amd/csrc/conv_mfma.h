@@ -77,7 +77,6 @@ struct ConvPlan {
     // kernel config
     int NC8 = 4, NBT = 2;                 // channel planes per chunk, 32-cout subtiles per block
     bool tt9 = false;                     // 3x3 taps compiled in
-    int mode = 1;                         // 0 double-buffered LDS, 1 single-buffered + register prefetch
     int nphase = 1;
     int Tp = 0;
     // conv3 (LDS-DMA staged, merged-phase convT, split-K): conv3_mfma.hip
@@ -111,16 +110,18 @@ struct ConvPlan {
 // fp16 [ntile][chunk][tap][plane][cout][8]) and upload.  `weight` is
 // [Cout][Cin][kh][kw] (conv) or [Cin][Cout][kh][kw] (transposed).
 // Cin is padded up to a multiple of 8 with zero weights (CinPad = plan.Cin).
-// `hint_hw` = pixels per image of the map the layer runs on (0 = unknown): it only steers the
-// channel-chunk width, which is baked into the weight pack order.
 int conv_plan_create(ConvPlan* p, const float* weight, int Cin, int Cout, int kh, int kw,
                      int sh, int sw, int ph, int pw, bool transposed, int out_pad,
-                     const float* scale, const float* shift, std::string* err, int hint_hw = 0,
+                     const float* scale, const float* shift, std::string* err,
                      int quant = 0, float act_scale = 1.f, int ups4 = 0);
 // `ups4` = 1: the conv always runs on a nearest-2x upsampled input (ConvIO::ups): build the four-phase form (ConvPlan::ups4).
 // `quant` = 2: the same on the MX-scaled fp8 MFMA (ConvPlan::mx; needs Cin % 64 == 0).
 // `quant` = 1: e4m3 weights with one scale per output channel (224 / max|w|), folded together with `act_scale`
 // (what the producer of the fp8 input multiplied by) into the epilogue scale.  3x3 stride-1 pad-1 convs, Cin % 32 == 0.
+
+// The `quant` of an fp8 conv of Cin input channels: the MX-scaled MFMA (32x32x64, 2x MAC rate) where it wins - Cin >= 512: its
+// 64-channel chunks leave one block per CU, which only deep K loops repay (profiles/r02_fp8_mx_layers.txt)
+inline int conv_fp8_quant(int Cin) { return (Cin % 64 == 0 && Cin >= 512) ? 2 : 1; }
 
 // fp32 -> OCP e4m3fn byte, round to nearest even, saturating to +-448 (host side of the weight packer; the device side
 // uses v_cvt_pk_fp8_f32)
@@ -191,7 +192,8 @@ int rowconv_launch(const RowGemmPlan& p, const RowConvIO& io, hipStream_t stream
 // W_eff[j][(dy * (1 + px) + dx) * C + c] = w[c][j][py + 1 - 2 dy][px + 1 - 2 dx], one launch; io.H x io.W source, io.Ho x io.Wo = 2H x 2W output
 int rowconvT_launch(const RowGemmPlan* p, const RowConvIO& io, hipStream_t stream, std::string* err);
 
-// conv3_mfma.hip: input-channel counts of 1x1 / linear layers that lin_fk_kernel serves (knob LIN_FK; >= LIN_FK_MIN_ROWS pixels or tokens)
+// conv3_mfma.hip: input-channel counts of 1x1 / linear layers that lin_fk_kernel serves (knob LIN_FK; >= kLinFkMinRows pixels or tokens)
+constexpr int kLinFkMinRows = 512;
 bool conv3_lin_fk_k(int Cin);
 int conv3_lin_mp_nsl(int Cin, long long rows, int Cout);     // lin_mp_kernel's slabs per block for this layer on `rows` tokens, 0: not its case
 

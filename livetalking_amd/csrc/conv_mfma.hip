@@ -71,17 +71,14 @@ struct KArgs {
 };
 
 // A-patch staging registers per thread (16-byte items): the largest variant a configuration has.
-__host__ __device__ constexpr int max_a_items(int NC8, int NBT) {
-    return NC8 == 4 ? 6 : (NC8 == 1 ? 5 : (NBT == 4 ? 3 : 10));
-}
+constexpr int max_a_items(int NC8) { return NC8 == 4 ? 6 : (NC8 == 1 ? 5 : 10); }
 constexpr int kMaxBItems = 9;   // 16-byte weight items a thread stages per chunk
 constexpr int kTapTableBytes = 128;
 constexpr int kLdsLimit = 160 * 1024;
 
-// MODE 0: double-buffered LDS (one barrier per chunk, one workgroup per CU when the slabs are large)
-// MODE 1: single-buffered LDS + register prefetch (two barriers per chunk, several workgroups per CU
-//         overlap each other's load / epilogue phases)
-template <int NC8, int NBT, bool TT9, int MODE, int MAXA>
+// Single-buffered LDS + register prefetch: two barriers per chunk, several workgroups per CU overlap each other's
+// load / epilogue phases.  (The double-buffered variant, one workgroup per CU, was last in commit fb7f771.)
+template <int NC8, int NBT, bool TT9, int MAXA>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BN = NBT * 32;
@@ -115,10 +112,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
     const int ooy = pm->ooy, oox = pm->oox;
 
     const int A_BYTES = NC8 * a.NPIXP * 16;
-    const int B_BYTES = a.Tp * NC8 * BN * 16;
-    constexpr int NBUF = (MODE == 0) ? 2 : 1;
     unsigned char* const smemA = smem;
-    unsigned char* const smemB = smem + NBUF * A_BYTES;
+    unsigned char* const smemB = smem + A_BYTES;
     // the tap table sits at the very end of the allocation (the epilogue reuses the front)
     short* const tapl = reinterpret_cast<short*>(smem + a.lds_bytes - kTapTableBytes);
 
@@ -190,9 +185,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
             rb[k] = v;
         }
     };
-    auto store_chunk = [&](int buf) {
-        unsigned char* Ab = smemA + buf * A_BYTES;
-        unsigned char* Bb = smemB + buf * B_BYTES;
+    auto store_chunk = [&]() {
+        unsigned char* Ab = smemA;
+        unsigned char* Bb = smemB;
 #pragma unroll
         for (int k = 0; k < MAXA; ++k) {
             const int i = tid + k * 256;
@@ -237,9 +232,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
 
     const int PS = a.NPIXP * 16;
     const int nchunks = a.nchunks;
-    auto compute_chunk = [&](int c, int cur) {
-        const unsigned char* Ab = smemA + cur * A_BYTES;
-        const unsigned char* Bb = smemB + cur * B_BYTES;
+    auto compute_chunk = [&](int c) {
+        const unsigned char* Ab = smemA;
+        const unsigned char* Bb = smemB;
         if constexpr (NC8 == 1) {
             // 8-channel input: one MFMA k16 step = two taps (lanes 0-31 tap 2s, lanes 32-63 tap 2s+1)
             const int nsteps = a.Tp >> 1;
@@ -290,27 +285,14 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
     };
 
     load_chunk(0);
-    if constexpr (MODE == 0) {
-        store_chunk(0);
+    for (int c = 0; c < nchunks; ++c) {
+        if (c) __syncthreads();          // every wave is done reading chunk c-1
+        store_chunk();
         __syncthreads();
-        for (int c = 0; c < nchunks; ++c) {
-            const int cur = c & 1;
-            const bool more = (c + 1) < nchunks;
-            if (more) load_chunk(c + 1);
-            compute_chunk(c, cur);
-            if (more) store_chunk(cur ^ 1);
-            __syncthreads();
-        }
-    } else {
-        for (int c = 0; c < nchunks; ++c) {
-            if (c) __syncthreads();          // every wave is done reading chunk c-1
-            store_chunk(0);
-            __syncthreads();
-            if (c + 1 < nchunks) load_chunk(c + 1);   // in flight under the MFMAs
-            compute_chunk(c, 0);
-        }
-        __syncthreads();
+        if (c + 1 < nchunks) load_chunk(c + 1);   // in flight under the MFMAs
+        compute_chunk(c);
     }
+    __syncthreads();
 
     // ---- epilogue: y = relu(acc*scale + shift + res) -> fp16, through a wave-private LDS
     // transpose so the residual is READ and the result WRITTEN as whole 16-byte channel
@@ -387,30 +369,24 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
 
 typedef void (*conv_kernel_t)(const KArgs);
 
-template <int NC8, int NBT, bool TT9, int MAXA>
-static conv_kernel_t kptr(int mode) {
-    return mode == 0 ? (conv_kernel_t)conv_mfma_kernel<NC8, NBT, TT9, 0, MAXA> : (conv_kernel_t)conv_mfma_kernel<NC8, NBT, TT9, 1, MAXA>;
-}
-
 // `need` = 16-byte A items per thread this launch stages; returns the smallest instantiation that holds them.
-static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int mode, int need) {
-    if (NC8 == 1) return (NBT == 1 && need <= 5) ? kptr<1, 1, false, 5>(mode) : nullptr;
-    if (NC8 == 4) {
-        if (need > 6) return nullptr;
-        if (NBT == 1) return tt9 ? kptr<4, 1, true, 6>(mode) : kptr<4, 1, false, 6>(mode);
-        if (NBT == 2) return tt9 ? kptr<4, 2, true, 6>(mode) : kptr<4, 2, false, 6>(mode);
-        if (NBT == 4) return tt9 ? kptr<4, 4, true, 6>(mode) : kptr<4, 4, false, 6>(mode);
+// A launch runs blocks of at most 64 output channels (NBT <= 2, conv_launch).
+static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int need) {
+#define KERNEL(nc8, nbt, maxa) (tt9 ? (conv_kernel_t)conv_mfma_kernel<nc8, nbt, true, maxa> : (conv_kernel_t)conv_mfma_kernel<nc8, nbt, false, maxa>)
+    if (NC8 == 1) return (NBT == 1 && need <= 5) ? (conv_kernel_t)conv_mfma_kernel<1, 1, false, 5> : nullptr;
+    if (NC8 == 4 && need <= 6) {
+        if (NBT == 1) return KERNEL(4, 1, 6);
+        if (NBT == 2) return KERNEL(4, 2, 6);
     }
-    if (NC8 == 2) {
-        if (need <= 3) {
-            if (NBT == 1) return tt9 ? kptr<2, 1, true, 3>(mode) : kptr<2, 1, false, 3>(mode);
-            if (NBT == 2) return tt9 ? kptr<2, 2, true, 3>(mode) : kptr<2, 2, false, 3>(mode);
-            if (NBT == 4) return tt9 ? kptr<2, 4, true, 3>(mode) : kptr<2, 4, false, 3>(mode);
-        } else if (need <= 10) {
-            if (NBT == 1) return tt9 ? kptr<2, 1, true, 10>(mode) : kptr<2, 1, false, 10>(mode);
-            if (NBT == 2) return tt9 ? kptr<2, 2, true, 10>(mode) : kptr<2, 2, false, 10>(mode);
-        }
+    if (NC8 == 2 && need <= 3) {
+        if (NBT == 1) return KERNEL(2, 1, 3);
+        if (NBT == 2) return KERNEL(2, 2, 3);
     }
+    if (NC8 == 2 && need <= 10) {
+        if (NBT == 1) return KERNEL(2, 1, 10);
+        if (NBT == 2) return KERNEL(2, 2, 10);
+    }
+#undef KERNEL
     return nullptr;
 }
 
@@ -470,7 +446,7 @@ unsigned char f32_to_e4m3(float v) {
 
 int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int kh, int kw,
                      int sh, int sw, int ph, int pw, bool transposed, int out_pad,
-                     const float* scale, const float* shift, std::string* err, int hint_hw, int quant, float act_scale, int ups4) {
+                     const float* scale, const float* shift, std::string* err, int quant, float act_scale, int ups4) {
     *p = ConvPlan();
     if (quant) {
         if (transposed || kh != 3 || kw != 3 || sh != 1 || sw != 1 || ph != 1 || pw != 1 || CinArg % 32 != 0) {
@@ -508,7 +484,7 @@ int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int
     std::vector<float> weff;
     const float* wsrc = weight;
     int wkh = kh, wkw = kw;
-    if (ups4 && v3_on && knob(K_UPS4) && !transposed && !quant && kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 &&
+    if (ups4 && v3_on && !transposed && !quant && kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 &&
         out_pad == 0 && Cin % 16 == 0) {
         p->v3 = true; p->v3_G = 4; p->v3_T = 16; p->ups4 = true;
         lsh = lsw = 1;
@@ -578,13 +554,13 @@ int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int
     }
 
     if (v3_on && !p->v3 && !transposed && Cin % 16 == 0 && kh == 3 && kw == 3 && sh == 2 && sw == 2 &&
-        ((ph == 1 && pw == 1 && out_pad == 0) || (ph == 0 && pw == 0 && out_pad == 1)) && knob(K_CONV_V3_S2) &&
+        ((ph == 1 && pw == 1 && out_pad == 0) || (ph == 0 && pw == 0 && out_pad == 1)) &&
         // measured in the pass (profiles/r04_s2_conflict_free.txt; conv3's stride-2 LDS image is bank-conflict free since round 4), register-
         // staged kernel -> conv3, 16 / 256 frames: 64->128 @64^2 16.9 -> 16.4 / 127 -> 94 us, 128->256 @32^2 20.4 -> 17.2 / 93 -> 69 us: conv3 from
         // 64 input channels on.  The wide, shallow ones stay register-staged: 16->32 @256^2 22.7 -> 30.5 / 249 -> 389 us (one 16-channel chunk per
         // item: 18 MFMAs per wave behind a 36-KB patch copy), 32->64 @128^2 15.0 -> 16.9 at 16 frames (-52 us at 256: a per-launch choice would
         // need both weight packs).  The asymmetric-pad form exists only in conv3.
-        (Cin >= 64 || out_pad == 1 || knob(K_CONV_V3_S2) == 2)) {
+        (Cin >= 64 || out_pad == 1)) {
         p->v3 = true; p->v3_G = 1; p->v3_T = 9; p->v3_S = 2;
     }
     if (v3_on && !p->v3 && Cin % 16 == 0 && lsh == 1 && lsw == 1) {
@@ -603,10 +579,6 @@ int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int
         if (Cin8 % 2) { if (err) *err = "Cin must be 8 or a multiple of 16"; return -1; }
         NBT = lCout >= 128 ? 4 : (lCout >= 64 ? 2 : 1);
         NC8 = (Cin8 >= 4) ? 4 : 2;
-        // tuning overrides (sweeps): LTK_CONV_NBT / LTK_CONV_NC8 apply where legal
-        const int fn = knob(K_CONV_NBT), fc = knob(K_CONV_NC8);
-        if (fn == 1 || fn == 2 || fn == 4) NBT = std::min(NBT, fn);
-        if (fc == 2 || (fc == 4 && Cin8 >= 4)) NC8 = fc;
         if (strided || Tmax > 9) { NC8 = 2; NBT = std::min(NBT, 2); }   // large patches: 10 staging items, 2 planes
         // weight slab of one chunk must fit the staging registers (9 x 16 B per thread)
         while (((NC8 == 1) ? ((Tmax + 1) / 2 * 2) : Tmax) * NC8 * NBT * 32 > kMaxBItems * 256) {
@@ -616,16 +588,13 @@ int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int
     if (p->v3) {
         // 1x1: 64-channel chunks; wide outputs take 32-channel chunks so that a 128-cout block (conv3_launch) still fits two
         // resident blocks per CU
-        if (p->v3_T == 1) NC8 = (Cin % 32 == 0 && lCout >= 128 && lCout % 128 == 0 && knob(K_GEMM_NC8) == 4) ? 4 : (Cin % 64 == 0) ? 8 : 2;
+        if (p->v3_T == 1) NC8 = (Cin % 32 == 0 && lCout >= 128 && lCout % 128 == 0) ? 4 : (Cin % 64 == 0) ? 8 : 2;
         else if (p->ups4) NC8 = 2;          // 16 weight matrices per chunk: 16-channel chunks keep two blocks per CU
         else if (p->v3_G == 4) NC8 = (Cin % 32 == 0) ? 4 : 2;
-        else {
-            // 16-channel chunks everywhere: measured (profiles/r02_conv_sweep.txt) equal or better than 32-channel chunks on
-            // every 3x3 layer at 16 frames and 25-28 % better on the 256/512-channel 8^2..16^2 maps at 256 frames (the
-            // smaller stage leaves room for two resident blocks and allows 512-pixel tiles)
-            NC8 = knob(K_TILE_RULE) ? 2 : ((Cin % 32 != 0 || hint_hw >= 1024 || hint_hw == 0) ? 2 : 4);     // 0: round-1 rule (A/B)
-            if (knob(K_CONV3_NC8) == 2 || (knob(K_CONV3_NC8) == 4 && Cin % 32 == 0)) NC8 = knob(K_CONV3_NC8);
-        }
+        // 16-channel chunks everywhere: measured (profiles/r02_conv_sweep.txt) equal or better than 32-channel chunks on
+        // every 3x3 layer at 16 frames and 25-28 % better on the 256/512-channel 8^2..16^2 maps at 256 frames (the
+        // smaller stage leaves room for two resident blocks and allows 512-pixel tiles); sweeps force 32 through knob CONV3_NC8
+        else NC8 = (knob(K_CONV3_NC8) == 4 && Cin % 32 == 0) ? 4 : 2;
         if (p->v3_S == 2) NC8 = 2;
         if (p->mx) NC8 = 4;                 // 4 planes of 16 e4m3 channels = the 64 channels one MX MFMA contracts
         NBT = 2;
@@ -633,12 +602,11 @@ int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int
     p->NC8 = NC8; p->NBT = NBT;      // NBT here = the widest block the staging registers allow
     p->tt9 = (!transposed && kh == 3 && kw == 3 && NC8 >= 2);
     p->nphase = (int)phases.size();
-    p->mode = knob(K_CONV_MODE);
     const int Tp = (NC8 == 1) ? ((Tmax + 1) / 2 * 2) : Tmax;
     p->Tp = Tp;
     if (!p->v3) {
         if (Tp * NC8 * NBT * 32 > kMaxBItems * 256) { if (err) *err = "weight slab too large for staging registers"; return -1; }
-        if (!pick_kernel(NC8, NBT, p->tt9, 1, 1)) { if (err) *err = "no kernel instantiation for this configuration"; return -1; }
+        if (!pick_kernel(NC8, std::min(NBT, 2), p->tt9, 1)) { if (err) *err = "no kernel instantiation for this configuration"; return -1; }
     }
 
     const int CoutPad = (lCout + 127) / 128 * 128;   // any block width <= 128 tiles it evenly
@@ -791,11 +759,8 @@ int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::st
     // tile: TW x TH output pixels x NB images, 256 rows
     int l2w = std::min(5, ceil_log2(a.Wo));
     int l2h = std::min(8 - l2w, ceil_log2(a.Ho));
-    const int forced_nbt = knob(K_CONV_NBT);
-    const int min_blocks = knob(K_CONV_MIN_BLOCKS);
     int NBT = std::min(p.NBT, 2);
-    if (forced_nbt == 1 || forced_nbt == 2 || forced_nbt == 4) NBT = std::min(p.NBT, forced_nbt);
-    const int maxpix = max_a_items(NC8, NBT) * 256 / NC8;
+    const int maxpix = max_a_items(NC8) * 256 / NC8;
     int PH, PW, NB;
     for (;;) {
         PH = ((1 << l2h) - 1) * a.sh + kext_y;
@@ -816,10 +781,10 @@ int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::st
     a.tiles_x = (a.Wo + (1 << l2w) - 1) >> l2w;
     a.tiles_y = (a.Ho + (1 << l2h) - 1) >> l2h;
     a.tiles_n = (io.N + NB - 1) / NB;
-    // block width: the widest (<= 64 couts unless forced) that still gives the chip >= min_blocks workgroups
+    // block width: the widest (<= 64 couts) that still gives the chip >= kMinBlocks workgroups
+    constexpr int kMinBlocks = 512;
     const long long mtiles = (long long)p.nphase * a.tiles_n * a.tiles_y * a.tiles_x;
-    if (!forced_nbt)
-        while (NBT > 1 && mtiles * ((p.lCout + 32 * NBT - 1) / (32 * NBT)) < min_blocks) NBT /= 2;
+    while (NBT > 1 && mtiles * ((p.lCout + 32 * NBT - 1) / (32 * NBT)) < kMinBlocks) NBT /= 2;
     const int BN = NBT * 32;
     a.n_ntiles = (p.lCout + BN - 1) / BN;
     a.nchunks = (a.Cin8 + NC8 - 1) / NC8;
@@ -827,20 +792,18 @@ int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::st
 
     const size_t a_bytes = (size_t)NC8 * NPIXP * 16, b_bytes = (size_t)p.Tp * NC8 * BN * 16;
     const size_t epi_bytes = (size_t)4 * 64 * (BN * 2 + 16);
-    int mode = p.mode ? 1 : 0;
-    if (mode == 0 && 2 * (a_bytes + b_bytes) + kTapTableBytes > (size_t)kLdsLimit) mode = 1;
-    size_t lds = (mode == 0 ? 2 : 1) * (a_bytes + b_bytes) + kTapTableBytes;
+    size_t lds = a_bytes + b_bytes + kTapTableBytes;
     lds = std::max(lds, epi_bytes + kTapTableBytes);
     lds = (lds + 255) / 256 * 256;
     if (lds > (size_t)kLdsLimit) { if (err) *err = "LDS budget exceeded"; return -1; }
     a.lds_bytes = (int)lds;
     // stride-2 3x3 layers whose tile rows hold >= 16 output pixels: column-parity split of the patch rows (KArgs::s2half)
-    a.s2half = (p.tt9 && a.sw == 2 && l2w >= 4 && knob(K_CONV_S2SPLIT)) ? (PW + 1) / 2 : 0;
+    a.s2half = (p.tt9 && a.sw == 2 && l2w >= 4) ? (PW + 1) / 2 : 0;
     // largest 32-bit element offset the kernel forms
     if ((double)io.N * io.H * io.W * io.x_ld >= 2147483647.0) { if (err) *err = "input tensor too large for 32-bit offsets"; return -1; }
 
     const int need = (npix * NC8 + 255) / 256;
-    conv_kernel_t k = pick_kernel(NC8, NBT, p.tt9, mode, need);
+    conv_kernel_t k = pick_kernel(NC8, NBT, p.tt9, need);
     if (!k) { if (err) *err = "no kernel instantiation for this launch"; return -1; }
     const long long nblk = (long long)p.nphase * a.tiles_n * a.tiles_y * a.tiles_x * a.n_ntiles;
     if (nblk <= 0 || nblk > 0x7fffffffll) { if (err) *err = "bad grid"; return -1; }

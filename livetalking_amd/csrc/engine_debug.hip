@@ -101,7 +101,7 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
     hipEvent_t t0, t1;
     CHK(hipEventCreate(&t0));
     CHK(hipEventCreate(&t1));
-    // the pass as ltk_wav2lip_infer runs it (pack_mel + conv stack with the bank gather and the output head fused, knobs CONV7 /
+    // the pass as ltk_wav2lip_infer runs it (pack_mel + conv stack with the bank gather and the output head fused, knob
     // HEAD_FUSED; replayed from the captured graph under knob GRAPH), same micro-batch schedule, frames going to a scratch buffer
     const int mbs = std::min(e->micro_batch, kPackMaxFrames);
     TimingIO tio;
@@ -111,7 +111,7 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
     // state - every pass finds its face-encoder outputs prefetched and prefetches the next pass's (dummy bank crops here) - which
     // is what the session's calls enqueue from the third call on
     for (ltk_engine::PfSlot& sl : e->pfs) sl.valid = false;        // the timing passes fill slots 1 and 2 with dummy crops
-    const bool pipe = knob(K_PREFETCH) && e->alt_frames > 0 && frames <= std::min(e->alt_frames, mbs) && knob(K_HEAD_FUSED) && e->c7 && knob(K_CONV7);
+    const bool pipe = knob(K_PREFETCH) && e->alt_frames > 0 && frames <= std::min(e->alt_frames, mbs) && knob(K_HEAD_FUSED) && e->c7;
     if (pipe) {
         FacePtrs nx;
         for (int i = 0; i < frames; ++i) nx.p[i] = (const uint8_t*)tio.face.p;
@@ -210,7 +210,7 @@ int ltk_wav2lip_time_layers(ltk_engine* e, int frames, int iters, float* ms_per_
     int rc = tio.setup(e, frames);
     if (rc) return rc;
     const OutPtrs* d_outs = fused ? &e->d_tab->outs : nullptr;
-    const FacePtrs* d_faces = (e->c7 && knob(K_CONV7)) ? &e->d_tab->faces : nullptr;
+    const FacePtrs* d_faces = e->c7 ? &e->d_tab->faces : nullptr;
     std::vector<double> acc(e->layers.size(), 0.0);
     rc = run_convs(e, frames, e->compute, d_outs, nullptr, d_faces);     // warm
     for (int it = 0; it < iters && !rc; ++it) {
@@ -237,7 +237,7 @@ int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
     CHK(enter_device(e->device));
     ConvPlan plan;
     std::string err;
-    int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, H * W);
+    int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err);
     if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
     ConvIO io;
     io.partial = e->d_partial; io.partial_cap = e->partial_cap;
@@ -345,8 +345,7 @@ int ltk_conv2d_fp8(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
     CHK(enter_device(e->device));
     ConvPlan plan;
     std::string err;
-    int rc = conv_plan_create(&plan, weight, Cin, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, &err, H * W,
-                              (Cin % 64 == 0 && (knob(K_FP8_MX) == 2 || (knob(K_FP8_MX) == 1 && Cin >= 512))) ? 2 : 1, act_scale);
+    int rc = conv_plan_create(&plan, weight, Cin, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, &err, conv_fp8_quant(Cin), act_scale);
     if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
     ConvIO io;
     io.partial = e->d_partial; io.partial_cap = e->partial_cap;

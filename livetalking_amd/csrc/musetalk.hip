@@ -198,8 +198,8 @@ struct MtGraph {
         if (scale) memcpy(sc.data(), scale, Cout * sizeof(float));
         ConvPlan p;
         std::string e;
-        int rc = conv_plan_create(&p, wuse, Cin, CoutP, kh, kw, sh, sw, ph, pw, false, pad_br, sc.data(), sf.data(), &e, x.P(),
-                                  x.q8 ? ((CinR % 64 == 0 && (knob(K_FP8_MX) == 2 || (knob(K_FP8_MX) == 1 && CinR >= 512))) ? 2 : 1) : 0, fp8_ascale, ups ? 1 : 0);
+        int rc = conv_plan_create(&p, wuse, Cin, CoutP, kh, kw, sh, sw, ph, pw, false, pad_br, sc.data(), sf.data(), &e,
+                                  x.q8 ? conv_fp8_quant(CinR) : 0, fp8_ascale, ups ? 1 : 0);
         if (rc) { err = name + ": " + e; return -1; }
         plans.push_back(p);
         MtOp op;
@@ -214,7 +214,7 @@ struct MtGraph {
         // Only the 1x1 / linear layers with <= 2560 outputs: a row block re-gathers its rows for every 32-output slab and every weight slab is
         // re-read by every row group, so the 3x3 layers (K = 11 520..23 040: ~1.4 GB of L2 -> CU traffic per layer at 1024 rows) and the
         // 10 240-output GEGLU projection would lose to conv3.
-        if (knob(K_MT_ROWCONV) > 0 && !x.q8 && !ups && act == 0 && sh == 1 && sw == 1 && kh == 1 && kw == 1 && ph == 0 && pw == 0 && pad_br == 0 &&
+        if (!x.q8 && !ups && act == 0 && sh == 1 && sw == 1 && kh == 1 && kw == 1 && ph == 0 && pw == 0 && pad_br == 0 &&
             Cin % 32 == 0 && Cin <= 5120 && CoutP % 256 == 0 && CoutP <= 2560 && x.P() <= 64 && x.P() == y.P()) {
             const size_t K = (size_t)kk * Cin;
             std::vector<float> we((size_t)CoutP * K);
@@ -441,8 +441,7 @@ int build_attention(MtGraph& g, SD& sd, const std::string& p, const MtTensor& x,
         for (const std::vector<float>* v : parts) o.insert(o.end(), v->begin(), v->end());
         return o;
     };
-    const bool fuse = !knob(K_MT_NO_QKV_FUSE);      // A/B switch
-    const bool self = fuse && x.buf == ctx.buf && x.coff == ctx.coff && x.C == ctx.C;
+    const bool self = x.buf == ctx.buf && x.coff == ctx.coff && x.C == ctx.C;
     MtTensor q, k, v, o = g.alloc(Cp, x.H, x.W);
     // a projection of x: plain, or with the LayerNorm in front of it folded in
     auto proj_x = [&](const std::string& name, const std::vector<float>& w, const std::vector<float>& b, int Cout, const MtTensor& y) -> int {
@@ -464,11 +463,6 @@ int build_attention(MtGraph& g, SD& sd, const std::string& p, const MtTensor& x,
         const std::vector<float> w3 = stack({&wqp, &wkp, &wvp}), b3 = stack({&bqp, &bkp, &bvp});
         if (proj_x(p + ".to_qkv", w3, b3, 3 * Cp, qkv)) return -1;
         q = MtGraph::view(qkv, 0, Cp); k = MtGraph::view(qkv, Cp, Cp); v = MtGraph::view(qkv, 2 * Cp, Cp);
-    } else if (!fuse) {
-        q = g.alloc(Cp, x.H, x.W); k = g.alloc(Cp, ctx.H, ctx.W); v = g.alloc(Cp, ctx.H, ctx.W);
-        if (g.add_conv(p + ".to_q", wqp.data(), bqp.data(), C, Cp, 1, 1, 0, x, q, nullptr, 0, 0)) return -1;
-        if (g.add_conv(p + ".to_k", wkp.data(), bkp.data(), Cctx, Cp, 1, 1, 0, ctx, k, nullptr, 0, 0)) return -1;
-        if (g.add_conv(p + ".to_v", wvp.data(), bvp.data(), Cctx, Cp, 1, 1, 0, ctx, v, nullptr, 0, 0)) return -1;
     } else {
         q = g.alloc(Cp, x.H, x.W);
         MtTensor kv = g.alloc(2 * Cp, ctx.H, ctx.W);
@@ -499,7 +493,7 @@ int build_transformer(MtGraph& g, SD& sd, const std::string& p, const MtTensor& 
     // (proj_in, attn1.to_out.0, attn2.to_out.0) writes per-token partial sums beside its output, the consumer (to_qkv, attn2.to_q,
     // ff.net.0.proj) reads the raw tensor with gamma folded into its weights and normalises in its epilogue (ln_fold).  48 launches
     // and as many tensor round trips of a pass; needs the stacked q|k|v projection and the hoisted cross-attention k|v (bit 1).
-    const bool fold = (knob(K_MT_FUSE) & 4) && (knob(K_MT_FUSE) & 2) && !knob(K_MT_NO_QKV_FUSE) && C % 32 == 0 &&
+    const bool fold = (knob(K_MT_FUSE) & 4) && (knob(K_MT_FUSE) & 2) && C % 32 == 0 &&
                       g.kv_pre.find(b + ".attn2") != g.kv_pre.end();
     LnFold l1{nullptr, nullptr, C, -1, 1e-5f}, l2 = l1, l3 = l1;
     if (fold) {
@@ -999,13 +993,14 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
             // 8x8 1280..2560 ch 116 -> 89 us at 256-px tiles, 16x16 640 ch 67 -> 49 us at 128-px tiles, 32x32 320 ch 55 -> 44 us at 256-px tiles).
             // The VAE decoder keeps the rule (it wants its 512-px tiles).
             // (The 4x4 level keeps the rule: forced 256-px tiles measured 31 -> 37 us there, profiles/r04_mt_rowconv_tile_ab.txt.)
-            if (op.unet3x3 && nf <= 16 && knob(K_MT_TILE_TABLE) && op.x.P() >= 64) io.force_pxw = op.x.P() == 256 ? 1 : 2;
+            if (op.unet3x3 && nf <= 16 && op.x.P() >= 64) io.force_pxw = op.x.P() == 256 ? 1 : 2;
             std::string e;
             int rc;
-            // (K = 1280 linear layers from LIN_FK_MIN_ROWS rows on - the 8^2 level of a 16-frame pass - take conv3_launch's lin_fk route)
-            const bool lin_fk = knob(K_LIN_FK) && op.ksz == 1 && (long long)nf * op.y.P() >= knob(K_LIN_FK_MIN_ROWS) &&
+            // (K = 1280 linear layers from kLinFkMinRows rows on - the 8^2 level of a 16-frame pass - take conv3_launch's lin_fk route)
+            const bool lin_fk = knob(K_LIN_FK) && op.ksz == 1 && (long long)nf * op.y.P() >= kLinFkMinRows &&
                                 (conv3_lin_fk_k(g.plans[op.plan].Cin) || conv3_lin_mp_nsl(g.plans[op.plan].Cin, (long long)nf * op.y.P(), g.plans[op.plan].lCout) > 0);
-            if (op.rplan >= 0 && !lin_fk && (long long)nf * op.y.P() <= std::min(knob(K_MT_ROWCONV), kRowConvMaxRows)) {
+            constexpr int kMtRowConvMaxRows = 1024;      // rowconv plans (add_conv) in launches of at most this many rows (frames x pixels)
+            if (op.rplan >= 0 && !lin_fk && (long long)nf * op.y.P() <= kMtRowConvMaxRows) {
                 RowConvIO rio;
                 rio.x = io.x; rio.x_ld = op.x.ld; rio.x_coff = op.x.coff; rio.H = op.x.H; rio.W = op.x.W;
                 rio.y = io.y; rio.y_ld = op.y.ld; rio.y_coff = op.y.coff; rio.Ho = op.y.H; rio.Wo = op.y.W;

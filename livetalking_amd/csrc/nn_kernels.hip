@@ -589,28 +589,24 @@ struct AttnArgs {
 
 // One wave = 32 queries of one (image, head).  S^T = K Q^T (keys as MFMA rows, queries as columns): a lane then
 // holds 16 keys of ONE query, so the softmax statistics are per lane (+ one exchange with the partner lane), and
-// the probabilities already sit in B-operand order for O^T += V^T P^T.  SHARE: the 4 waves of a block take the
-// same query tile and a quarter of the value channels each (head dim 512 of the VAE mid-block attention).
-template <int DT, int DVT, bool SHARE, bool PF = false>
+// the probabilities already sit in B-operand order for O^T += V^T P^T.
+template <int DT, int DVT, bool PF>
 __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
     const int h = blockIdx.y, n = blockIdx.z;
-    const int qtile = SHARE ? blockIdx.x : blockIdx.x * 4 + wave;
+    const int qtile = blockIdx.x * 4 + wave;
     const int q0 = qtile * 32;
     if (q0 >= a.Tq) return;
-    const int dvt0 = SHARE ? wave * DVT : 0;
     const int Tq = a.Tq, Tk = a.Tk, Tkp = a.Tkp;
     const f16* qb = a.q + ((size_t)(n * a.q_cbt + a.q_cb0 + h * DT) * Tq) * 16 + hh * 8;
     const f16* kb = a.k + ((size_t)(n * a.k_cbt + a.k_cb0 + h * DT) * Tk) * 16 + hh * 8;
-    const f16* vtb = a.vt + ((size_t)(n * a.heads + h) * a.dv32 + dvt0 * 32 + l31) * Tkp + hh * 8;
+    const f16* vtb = a.vt + ((size_t)(n * a.heads + h) * a.dv32 + l31) * Tkp + hh * 8;
     const int qrow = min(q0 + l31, Tq - 1);
 
-    f16x8 qf[SHARE ? 1 : DT];
-    if constexpr (!SHARE) {
+    f16x8 qf[DT];
 #pragma unroll
-        for (int j = 0; j < DT; ++j) qf[j] = *reinterpret_cast<const f16x8*>(qb + ((size_t)j * Tq + qrow) * 16);
-    }
+    for (int j = 0; j < DT; ++j) qf[j] = *reinterpret_cast<const f16x8*>(qb + ((size_t)j * Tq + qrow) * 16);
     f32x16 acc[DVT];
 #pragma unroll
     for (int t = 0; t < DVT; ++t)
@@ -619,18 +615,15 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
     float m = -1e30f, l = 0.f;
 
     // Round 6: (a) PF: the K and V^T fragments of key tile t+1 are loaded while tile t is computed (register double buffer; they were
-    // loaded right in front of their MFMAs: one exposed L2 round trip per tile and contraction; knob ATTN_PF, head dims <= 80); (b) the key-range mask is a
+    // loaded right in front of their MFMAs: one exposed L2 round trip per tile and contraction; head dims <= 80, head dim 160 stays un-prefetched); (b) the key-range mask is a
     // wave-uniform branch taken on a ragged last tile only; (c) the running maximum rarely moves after the first tiles: the
     // accumulators are rescaled only when some lane's maximum did (wave-uniform test), with alpha == 1 exactly otherwise.
     // Values are identical to the straight loop: (a) and (b) change no arithmetic, (c) skips multiplications by exactly 1.0f.
-    constexpr int KF = SHARE ? 1 : DT;
-    struct Frag { f16x8 k[KF], v[2][DVT]; };
+    struct Frag { f16x8 k[DT], v[2][DVT]; };
     auto load_tile = [&](int key0, Frag& f) {
         const int krow = min(key0 + l31, Tk - 1);
-        if constexpr (!SHARE) {
 #pragma unroll
-            for (int j = 0; j < DT; ++j) f.k[j] = *reinterpret_cast<const f16x8*>(kb + ((size_t)j * Tk + krow) * 16);
-        }
+        for (int j = 0; j < DT; ++j) f.k[j] = *reinterpret_cast<const f16x8*>(kb + ((size_t)j * Tk + krow) * 16);
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -640,18 +633,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
         f32x16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
-        if constexpr (SHARE) {
-            const int krow = min(key0 + l31, Tk - 1);
 #pragma unroll
-            for (int j = 0; j < DT; ++j) {
-                const f16x8 kj = *reinterpret_cast<const f16x8*>(kb + ((size_t)j * Tk + krow) * 16);
-                const f16x8 qj = *reinterpret_cast<const f16x8*>(qb + ((size_t)j * Tq + qrow) * 16);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kj, qj, st, 0, 0, 0);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < DT; ++j) st = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.k[j], qf[j], st, 0, 0, 0);
-        }
+        for (int j = 0; j < DT; ++j) st = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.k[j], qf[j], st, 0, 0, 0);
         if (key0 + 32 > Tk) {                   // ragged last tile (wave-uniform)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -715,7 +698,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnArgs a) {
     for (int t = 0; t < DVT; ++t) {
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
-            const int cbl = (dvt0 + t) * 2 + pr;       // channel block of the head
+            const int cbl = t * 2 + pr;       // channel block of the head
             unsigned pk[2][2];
 #pragma unroll
             for (int eo = 0; eo < 2; ++eo) {
@@ -887,9 +870,9 @@ __global__ __launch_bounds__(256) void attn_lds_kernel(const AttnArgs a) {
 //         32), the four partial S^T tiles meet in LDS (one 16-byte-strided exchange area per key-tile parity, one barrier
 //         per key tile) and every wave then holds the complete tile in the usual register layout;
 //   O^T += V^T P^T over the value channels: wave w owns value channels [128w, 128w+128) as before.
-// Per key tile a wave issues 16 MFMAs (attn_kernel<32,4,true> issued 40: every wave recomputed the whole S^T), its 8 Q
-// fragments stay in registers for the whole kernel (they were re-read from memory for every key tile), and the K / V^T
-// fragments of tile t+1 are loaded while tile t is computed.
+// Per key tile a wave issues 16 MFMAs, its 8 Q fragments stay in registers for the whole kernel, and the K / V^T fragments of
+// tile t+1 are loaded while tile t is computed.  (Its predecessor, attn_kernel's SHARE form - every wave recomputed the whole
+// S^T: 40 MFMAs per key tile, Q re-read from memory for every key tile - was last in commit fb7f771.)
 __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float xch[2][4][4][64][4];        // [parity][wave][register quad][lane][4]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1026,23 +1009,11 @@ int launch_attention(const f16* q, int q_cbt, int q_cb0, int Tq, const f16* k, i
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
     switch (d16) {
-        case 48:
-            if (knob(K_ATTN_PF)) hipLaunchKernelGGL((attn_kernel<3, 2, false, true>), grid4, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_kernel<3, 2, false>), grid4, dim3(256), 0, s, a);
-            break;
-        case 64:
-            if (knob(K_ATTN_PF)) hipLaunchKernelGGL((attn_kernel<4, 2, false, true>), grid4, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_kernel<4, 2, false>), grid4, dim3(256), 0, s, a);
-            break;
-        case 80:
-            if (knob(K_ATTN_PF)) hipLaunchKernelGGL((attn_kernel<5, 3, false, true>), grid4, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_kernel<5, 3, false>), grid4, dim3(256), 0, s, a);
-            break;
+        case 48: hipLaunchKernelGGL((attn_kernel<3, 2, true>), grid4, dim3(256), 0, s, a); break;
+        case 64: hipLaunchKernelGGL((attn_kernel<4, 2, true>), grid4, dim3(256), 0, s, a); break;
+        case 80: hipLaunchKernelGGL((attn_kernel<5, 3, true>), grid4, dim3(256), 0, s, a); break;
         case 160: hipLaunchKernelGGL((attn_kernel<10, 5, false>), grid4, dim3(256), 0, s, a); break;
-        case 512:
-            if (knob(K_ATTN_WIDE)) hipLaunchKernelGGL(attn_wide_kernel, grid1, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((attn_kernel<32, 4, true>), grid1, dim3(256), 0, s, a);
-            break;
+        case 512: hipLaunchKernelGGL(attn_wide_kernel, grid1, dim3(256), 0, s, a); break;      // the VAE mid block's single head
         default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -18,41 +18,9 @@ namespace {
 
 struct KnobDef { const char* name; int dflt; };
 const KnobDef kDefs[K_COUNT] = {
-    {"LTK_CONV_V3", 1},        {"LTK_CONV_V3_S2", 1},      {"LTK_CONV_NBT", 0},          {"LTK_CONV_NC8", 0},
-    {"LTK_GEMM_NC8", 4},       {"LTK_CONV_MODE", 1},       {"LTK_CONV_MIN_BLOCKS", 512}, {"LTK_CONV_PXW", 0},
-    {"LTK_CONV3_NBT", 0},      {"LTK_CONV_PXW4_MIN", 448}, {"LTK_SPLITK", 1},            {"LTK_KSPLIT", 0},
-    {"LTK_CONV_PERSIST", 512}, {"LTK_NO_FOLD_RESIDUAL", 0}, {"LTK_NO_FLATTEN", 0},       {"LTK_NO_AUX_STREAM", 0},
-    {"LTK_MICROBATCH", 0},     {"LTK_MT_NO_QKV_FUSE", 0},  {"LTK_HEAD_FUSED", 1},
-    {"LTK_CONV3_NC8", 0},      {"LTK_TILE_RULE", 1},       {"LTK_TILE_TABLE", 1},        {"LTK_CONV7", 1},           {"LTK_ATTN_WIDE", 1},       {"LTK_UPS4", 1},            {"LTK_FP8_MX", 1},
-    {"LTK_ROWGEMM", 1},
-    {"LTK_ROWCONV", 1024},
-    {"LTK_ABLATE", 0},
-    {"LTK_GRAPH", 1},
-    {"LTK_DF_FRAMES", 0},
-    {"LTK_DF_BLOCK", 6},
-    {"LTK_DF_MIN", 32},
-    {"LTK_ROWCONVT", 512},
-    {"LTK_MT_ROWCONV", 1024},
-    {"LTK_MT_TILE_TABLE", 1},
-    {"LTK_LDS_SWZ", 1},
-    {"LTK_FACE_CACHE", 0},
-    {"LTK_PREFETCH", 1},
-    {"LTK_AUDIO_ROWCONV", 54},
-    {"LTK_MT_FUSE", 7},
-    {"LTK_MT_GN1", 1},
-    {"LTK_ATTN_PF", 1},
-    {"LTK_SAT_CHECK", 0},
-    {"LTK_CONV_S2SPLIT", 1},
-    {"LTK_FACE_CACHE_MAX_MB", 16384},
-    {"LTK_LIN_FK", 1},
-    {"LTK_LIN_FK_BLOCKS", 512},
-    {"LTK_LIN_FK_MIN_ROWS", 512},
-    {"LTK_ATTN_LDS", 1},
-    {"LTK_LIN_MP", 1},
-    {"LTK_GN_COOP", 1},
-    {"LTK_AUDIO0", 3},
-    {"LTK_CONV_S2D", 1},
-    {"LTK_PF_LRU", 0},
+#define LTK_KNOB_DEF(name, dflt) {"LTK_" #name, dflt},
+    LTK_KNOBS(LTK_KNOB_DEF)
+#undef LTK_KNOB_DEF
 };
 
 std::atomic<int> g_val[K_COUNT];     // knob_set (tests, tuners) may run beside launch threads reading the table
@@ -62,8 +30,8 @@ std::once_flag g_once;
 void init() {
     for (int i = 0; i < K_COUNT; ++i) {
         const char* e = getenv(kDefs[i].name);
-        // presence-style switches (LTK_NO_*): any value means 1 - the empty string, "true", "yes" - unless the WHOLE value
-        // parses as a number (LTK_NO_AUX_STREAM=0 switches it off again)
+        // presence-style switches: any value means 1 - the empty string, "true", "yes" - unless the WHOLE value parses as a
+        // number (LTK_FACE_CACHE=0 switches it off again)
         int v = kDefs[i].dflt;
         if (e) {
             char* end = nullptr;

@@ -28,7 +28,7 @@ static int enqueue_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, c
                         float* d_pred_f32, bool cached = false, int par = 0, bool have_feats = false) {
     const FacePtrs* d_faces = &e->d_tab->faces;
     const OutPtrs* d_outs = &e->d_tab->outs;
-    const bool pack_fused = bank_faces && e->c7 && knob(K_CONV7);     // the first layer reads the bank crops itself
+    const bool pack_fused = bank_faces && e->c7;     // the first layer reads the bank crops itself
     if (cached) launch_feat_copy(d_faces, nf, feat_geom(e), 0, s);
     else if (have_feats) {}
     else if (bank_faces) { if (!pack_fused) launch_pack_faces(d_faces, nf, e->buf[B_X0], s); }
@@ -64,9 +64,9 @@ int ltk::launch_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, cons
     // one launch instead of ~70: a single session's step is 0..1.8 % faster end to end depending on the box's host (three interleaved pairs on the
     // last box: 1.3836 / 1.3904 / 1.3956 ms eager, 1.3619 / 1.3699 / 1.3596 ms replayed), and a host serving hundreds of sessions sustains 512 instead
     // of 448 of them (profiles/r04_delivered_graph_ab.txt).
-    const bool graphable = knob(K_GRAPH) && bank_faces && fused && e->c7 && knob(K_CONV7) && s == e->compute;
+    const bool graphable = knob(K_GRAPH) && bank_faces && fused && e->c7 && s == e->compute;
     if (!graphable) {
-        const bool product = bank_faces && fused && e->c7 && knob(K_CONV7) && s == e->compute;
+        const bool product = bank_faces && fused && e->c7 && s == e->compute;
         if ((par || have_feats) && !product) return fail(LTK_E_STATE, "pipelined pass outside the product configuration");
         return enqueue_pass(e, nf, s, bank_faces, d_face6, fused, have_outs, d_pred_f32, cached && bank_faces, par, have_feats);
     }
@@ -111,7 +111,7 @@ static int build_face_cache(ltk_engine* e, Avatar& a) {
         a.feat_bytes.store(rec * a.n, std::memory_order_release);
     }
     const int chunk = std::min(std::min(16, a.n), std::min(e->micro_batch, kPackMaxFrames));
-    const bool pack_fused = e->c7 && knob(K_CONV7);
+    const bool pack_fused = e->c7;
     for (int f0 = 0; f0 < a.n; f0 += chunk) {
         const int first = std::min(f0, a.n - chunk);
         FacePtrs fp;
@@ -194,7 +194,7 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
         // its session prefetched them into (key: avatar, first bank index, frame count), and - when it continues a session's sequence
         // (it was a hit, or it starts where a recent solo call of the same avatar and size ended) - prefetches the next call's in turn
         const bool solo = nreq == 1 && !cached && knob(K_PREFETCH) && e->alt_frames > 0 && total <= std::min(e->alt_frames, mbs) &&
-                          !e->capture && knob(K_HEAD_FUSED) && e->c7 && knob(K_CONV7);
+                          !e->capture && knob(K_HEAD_FUSED) && e->c7;
         const int first = reqs[0].index;
         int slot = 0;
         if (solo)
@@ -248,7 +248,6 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
                 // once: the first ~35 calls of a session - all of a 20-step benchmark run - paid for captures, 4.5 % on its timed line)
                 // (... whose last reader is done: with calls of several sessions in flight the most recently consumed slot may still be read by
                 // another session's pass, and a prefetch into it would wait for that pass instead of running beside it)
-                if (knob(K_PF_LRU)) { if (!victim || sl.stamp < e->pfs[victim].stamp) victim = k; continue; }      // (A/B: the rule this replaced)
                 if (sl.read && hipEventQuery(sl.ev_read) != hipSuccess) { if (!busy || sl.stamp > e->pfs[busy].stamp) busy = k; continue; }
                 if (!victim || sl.stamp > e->pfs[victim].stamp) victim = k;
             }

@@ -190,8 +190,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
     // activation) disappears.  Not applied when a scale is too small for 1/s to be a sane fp16 weight.
     std::vector<float> wfold;
     L->res_folded = false;
-    if (d.residual && !d.transposed && d.cin == d.cout && (d.k & 1) && d.sh == 1 && d.sw == 1 && d.pad == d.k / 2 &&
-        !knob(K_NO_FOLD_RESIDUAL)) {
+    if (d.residual && !d.transposed && d.cin == d.cout && (d.k & 1) && d.sh == 1 && d.sw == 1 && d.pad == d.k / 2) {
         bool ok = true;
         for (int c = 0; c < d.cout; ++c) ok = ok && fabsf(sc[c]) >= 1e-3f;
         if (ok) {
@@ -211,10 +210,10 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             for (int ci = 0; ci < d.cin; ++ci)
                 for (int t = 0; t < kk; ++t)
                     wf[(size_t)co * cin_flat + ((size_t)(ci >> 4) * kk + t) * 16 + (ci & 15)] = w[((size_t)co * d.cin + ci) * kk + t];
-        rc = conv_plan_create(&L->plan, wf.data(), cin_flat, d.cout, 1, 1, 1, 1, 0, 0, false, 0, sc.data(), sf.data(), &err, 1);
+        rc = conv_plan_create(&L->plan, wf.data(), cin_flat, d.cout, 1, 1, 1, 1, 0, 0, false, 0, sc.data(), sf.data(), &err);
     } else {
         rc = conv_plan_create(&L->plan, w, d.cin, d.cout, d.k, d.k, d.sh, d.sw, d.pad, d.pad, d.transposed, d.out_pad,
-                              sc.data(), sf.data(), &err, hint_hw);
+                              sc.data(), sf.data(), &err);
     }
     if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
     // one pixel per frame on both sides: a plain GEMM with as many rows as frames (rowgemm.hip, used for launches of <= 32 frames).
@@ -290,7 +289,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             }
         }
     }
-    if (!d.transposed && d.k == 7 && d.cin == 6 && d.cout == 16 && d.sh == 1 && d.pad == 3 && knob(K_CONV7) && !e->c7) {
+    if (!d.transposed && d.k == 7 && d.cin == 6 && d.cout == 16 && d.sh == 1 && d.pad == 3 && !e->c7) {
         rc = conv7_plan_create(&e->c7, w, sc.data(), sf.data(), &err);
         if (rc) return fail(LTK_E_HIP, p + ": " + err);
     }
@@ -390,10 +389,12 @@ int build_program(ltk_engine* e, const ltk_named_tensor* sd, int n) {
             // audio_encoder.11: the 3x3 "valid" conv on the 3x3 map = a GEMM over the flattened map with one row per frame (K = 2304),
             // like face_encoder_blocks.7.0: rowgemm for launches of <= 32 frames (16 blocks of the first-generation kernel streamed its
             // 2.4 MB of weights in 26 us - the longest launch of the audio branch, which heads the critical path under knob PREFETCH)
-            const bool flat = !d.transposed && d.pad == 0 && d.k > 1 && d.k == H && d.k == W && d.cin % 64 == 0 && !knob(K_NO_FLATTEN);
+            const bool flat = !d.transposed && d.pad == 0 && d.k > 1 && d.k == H && d.k == W && d.cin % 64 == 0;
             const int oh = (H + 2 * d.pad - d.k) / d.sh + 1, ow = (W + 2 * d.pad - d.k) / d.sw + 1;
-            // audio_encoder.6 .. .10 (output maps 9 x 6 and 3 x 3: <= 864 rows per 16-frame launch): rowconv (build_layer)
-            const bool small = !flat && d.k == 3 && d.pad == 1 && oh * ow <= 54 && d.cin % 32 == 0;
+            // audio_encoder.6 .. .10 (output maps 9 x 6 and 3 x 3: <= 864 rows per 16-frame launch): rowconv (build_layer) in launches of
+            // <= ROWCONV rows, instead of the first-generation kernel / conv3 + split-K finish of rounds 1-4
+            constexpr int kAudioRowconvMaxPixels = 54;
+            const bool small = !flat && d.k == 3 && d.pad == 1 && oh * ow <= kAudioRowconvMaxPixels && d.cin % 32 == 0;
             if ((rc = build_layer(e, d, sd, n, &L, H * W, flat ? in_ld : 0, small ? -1 : 0))) return rc;
             L.audio = true;
             L.in_buf = in_buf; L.in_ld = in_ld; L.in_coff = 0; L.H = H; L.W = W;
@@ -417,8 +418,7 @@ int build_program(ltk_engine* e, const ltk_named_tensor* sd, int n) {
             const bool last = (li + 1 == nl) || kFaceEnc[li + 1].block != bl.block;
             Layer L;
             // the 4x4 "valid" conv on the 4x4 map: a 1x1 conv over the flattened map (needs in_ld % 64 == 0)
-            const bool flat = !bl.d.transposed && bl.d.pad == 0 && bl.d.k > 1 && bl.d.k == H && bl.d.k == W &&
-                              bl.d.cin % 64 == 0 && !knob(K_NO_FLATTEN);
+            const bool flat = !bl.d.transposed && bl.d.pad == 0 && bl.d.k > 1 && bl.d.k == H && bl.d.k == W && bl.d.cin % 64 == 0;
             if ((rc = build_layer(e, bl.d, sd, n, &L, H * W, flat ? in_ld : 0, H == W ? W : 0))) return rc;
             L.in_buf = in_buf; L.in_ld = in_ld; L.in_coff = in_coff; L.H = H; L.W = W;
             if (flat) {
@@ -513,7 +513,7 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
         return e->buf[id];
     };
     std::string err;
-    const bool fork = !e->capture && e->aux && !knob(K_NO_AUX_STREAM) && !evs && part != 1;
+    const bool fork = !e->capture && e->aux && !evs && part != 1;
     size_t evi = 0;
     bool joined = !fork;
     if (fork) {
@@ -540,6 +540,7 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
             if ((part == 1) == L->face_enc) kept.push_back(L);
         order.swap(kept);
     }
+    constexpr int kRowConvTMaxRows = 512;      // measured (profiles/r04_rowconvT_ab.txt): 256 rows -7.5 us, 1024 rows +-0
     // one layer on frames [f0, f0 + n) of the arena
     auto launch_layer = [&](Layer& L, int f0, int n, bool on_aux) -> int {
         const int bucket = frame_bucket(n);
@@ -553,7 +554,7 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
         if (head_outs && &L == &e->layers.back()) { io.head_w = e->d_head; io.head_outs = reinterpret_cast<const uint8_t* const*>(head_outs) + f0; }
         if (knob(K_TILE_TABLE)) { io.force_pxw = L.tile[bucket].pxw; io.force_nbt = L.tile[bucket].nbt; io.force_ksplit = L.tile[bucket].ks; }
         int rc;
-        if (e->c7 && knob(K_CONV7) && L.in_buf == B_X0)       // face_encoder_blocks.0.0
+        if (e->c7 && L.in_buf == B_X0)       // face_encoder_blocks.0.0
             rc = conv7_launch(e->c7, faces ? reinterpret_cast<const FacePtrs*>(reinterpret_cast<const uint8_t* const*>(faces) + f0) : nullptr,
                               B(B_X0) + (size_t)f0 * 65536 * 8, n, io.y, L.out_ld, L.out_coff, s, &err);
         else if (L.s2d && knob(K_CONV_S2D) && !(L.H & 1) && !(L.W & 63))                          // face_encoder_blocks.1.0 / 2.0
@@ -564,8 +565,7 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
             rc = audio0_launch(e->a0, reinterpret_cast<const MelPtrs*>(e->d_tab->mels.p + f0), n, io.y, L.out_ld, L.out_coff, on_aux ? e->aux : s, &err);
         // one-pixel maps: a skinny GEMM, no split-K finish launch.  Not under LTK_SPLITK=0, whose promise is ONE summation order per
         // output element whatever the launch's frame count (larger launches run these layers on conv3)
-        else if (L.rowconv && L.rg.d_w && (long long)n * L.Ho * L.Wo <= std::min(knob(K_ROWCONV), kRowConvMaxRows) && knob(K_SPLITK) &&
-                 (!L.audio || L.Ho * L.Wo <= knob(K_AUDIO_ROWCONV))) {
+        else if (L.rowconv && L.rg.d_w && (long long)n * L.Ho * L.Wo <= std::min(knob(K_ROWCONV), kRowConvMaxRows) && knob(K_SPLITK)) {
             // 3x3 layers on the 4x4 / 8x8 maps: the same weight-streaming GEMM over gathered im2col rows (same LTK_SPLITK=0 rule)
             RowConvIO rio;
             rio.x = io.x; rio.x_ld = L.in_ld; rio.x_coff = L.in_coff; rio.H = L.H; rio.W = L.W;
@@ -573,8 +573,9 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
             rio.res = io.res; rio.res_ld = io.res_ld; rio.res_coff = io.res_coff;
             rio.N = n; rio.KW = 3; rio.stride = L.rc_stride; rio.stride_w = L.rc_stride_w; rio.pad = 1; rio.relu = 1;
             rc = rowconv_launch(L.rg, rio, on_aux ? e->aux : s, &err);
-        } else if (L.rgT[0].d_w && (long long)n * L.H * L.W <= std::min(knob(K_ROWCONVT), kRowConvMaxRows) && knob(K_ROWCONV) > 0 && knob(K_SPLITK)) {
+        } else if (L.rgT[0].d_w && (long long)n * L.H * L.W <= kRowConvTMaxRows && knob(K_ROWCONV) > 0 && knob(K_SPLITK)) {
             // stride-2 transposed convs on the 4x4 / 8x8 maps: four per-phase weight-streaming GEMMs in one launch (no split-K finish)
+            // instead of conv3's merged-phase items, in launches of at most kRowConvTMaxRows SOURCE pixels (frames x H x W)
             RowConvIO rio;
             rio.x = io.x; rio.x_ld = L.in_ld; rio.x_coff = L.in_coff; rio.H = L.H; rio.W = L.W;
             rio.y = io.y; rio.y_ld = L.out_ld; rio.y_coff = L.out_coff; rio.Ho = L.Ho; rio.Wo = L.Wo;

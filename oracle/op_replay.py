@@ -164,7 +164,7 @@ class Replay:
         self.fp8 = fp8
         self.ascale = ascale
         self.may_fuse = fused_into(fp8)
-        self.fold_residual = True                  # Wav2Lip: knob NO_FOLD_RESIDUAL off
+        self.fold_residual = True                  # Wav2Lip: the engine folds the residual into the centre tap
         self.only = only
         self.ops: Dict[str, dict] = {}
         self.fused: Dict[str, dict] = {}           # ops the device did not materialise: name -> description
@@ -361,8 +361,8 @@ class Replay:
 
     def _w2l_layer(self, op, ref):
         """A Wav2Lip Conv2d / ConvTranspose2d block as csrc/w2l_program.hip packs it: fp16 weights, BatchNorm (eval) as an fp32
-        scale / shift in the epilogue, the residual of a stride-1 same-size block folded into the centre tap (w += 1 / scale, knob
-        NO_FOLD_RESIDUAL; not when a scale is below 1e-3), ReLU, one rounding to fp16."""
+        scale / shift in the epilogue, the residual of a stride-1 same-size block folded into the centre tap (w += 1 / scale;
+        not when a scale is below 1e-3), ReLU, one rounding to fp16."""
         l, sd = op["layer"], self.sd
         x = op["x"].float()
         pre = l.prefix + ".conv_block."

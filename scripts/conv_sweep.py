@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Time the Wav2Lip layer geometries through ltk_conv2d_f16 under kernel-config
-overrides (LTK_CONV_MODE / LTK_CONV_NBT / LTK_CONV_NC8).  GPU only."""
-import itertools
+"""Time the Wav2Lip layer geometries through ltk_conv2d_f16: first-generation kernel (CONV_V3=0) against conv3, or
+(SWEEP_V3TILES=1) conv3 under forced tile widths / block widths (CONV_PXW / CONV3_NBT).  GPU only."""
 import os
 import sys
 
@@ -54,15 +53,13 @@ def macs(l):
 
 def main():
     eng = Engine(0)
-    # (LTK_CONV_V3, LTK_CONV_MODE, LTK_CONV_NBT, LTK_CONV_NC8)
-    variants = [(0, 1, 0, 0), (1, 1, 0, 0)]
+    # CONV_V3 value, or a forced conv3 tile
+    variants = [0, 1]
     if os.environ.get("SWEEP_V3TILES"):
-        variants = [(1, 1, 0, 0), ("pxw2", 1, 0, 0), ("nbt1", 1, 0, 0), ("pxw2nbt1", 1, 0, 0)]
-    if os.environ.get("SWEEP_FULL"):
-        variants = [(0, m, n, c) for m, n, c in itertools.product((1, 0), (0, 2, 1), (0, 2))] + [(1, 1, 0, 0)]
+        variants = [1, "pxw2", "nbt1", "pxw2nbt1"]
     only = os.environ.get("SWEEP_ONLY")
     print(f"frames={N}   cell = us / TFLOP/s")
-    hdr = "layer".ljust(16) + "".join(((str(v) if isinstance(v, str) else "v3" if v else f"old m{m}n{n}c{c}")).rjust(14) for v, m, n, c in variants)
+    hdr = "layer".ljust(16) + "".join((v if isinstance(v, str) else "v3" if v else "old").rjust(14) for v in variants)
     print(hdr)
     for l in LAYERS:
         name, H, W, Cin, Cout, k, s, p, tr, op, res = l
@@ -82,16 +79,13 @@ def main():
         sc = np.ones(Cout, np.float32)
         sf = np.zeros(Cout, np.float32)
         row = name.ljust(16)
-        for v3, mode, nbt, nc8 in variants:
+        for v3 in variants:
             Engine.set_knob("CONV_PXW", 0); Engine.set_knob("CONV3_NBT", 0)
             if isinstance(v3, str):
                 if "pxw2" in v3: Engine.set_knob("CONV_PXW", 2)
                 if "nbt1" in v3: Engine.set_knob("CONV3_NBT", 1)
                 v3 = 1
             Engine.set_knob("CONV_V3", v3)
-            Engine.set_knob("CONV_MODE", mode)
-            Engine.set_knob("CONV_NBT", nbt)
-            Engine.set_knob("CONV_NC8", nc8)
             try:
                 ms = eng.conv2d_f16(x.data_ptr(), N, H, W, Cin, w, Cout, k, s, p, tr, op, sc, sf,
                                     x.data_ptr() if res else 0, True, y.data_ptr(), iters=10)

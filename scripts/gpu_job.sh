@@ -61,7 +61,7 @@ ab-lib)
   TAG=$1; shift; LOG=$O/ab_$TAG.log; : > $LOG
   for rnd in 1 2; do for lib in "$@"; do
     echo "######## round $rnd lib $lib" >> $LOG
-    LTK_LIB=$R/$lib ROUNDS=3 timeout 300 python scripts/layer_times.py "TILE_RULE=1" -- ${FRAMES:-16 256} 2>&1 | grep -E "${ROWS:-^(====|sum|conv stack|face_decoder_blocks.[3-7]|face_encoder_blocks.[2-6].[01]|output)}" >> $LOG
+    LTK_LIB=$R/$lib ROUNDS=3 timeout 300 python scripts/layer_times.py "GRAPH=1" -- ${FRAMES:-16 256} 2>&1 | grep -E "${ROWS:-^(====|sum|conv stack|face_decoder_blocks.[3-7]|face_encoder_blocks.[2-6].[01]|output)}" >> $LOG
     if [ "${MT:-1}" != "0" ]; then
       LTK_LIB=$R/$lib timeout 300 python scripts/mt_op_times.py 16 2>&1 | grep -E "pass|conv/linear|GroupNorm|resnets.1.conv2|resnets.1.conv1" | head -8 >> $LOG
     fi
@@ -103,19 +103,6 @@ r4b)  # round-4 job B: paste diagnostic, the whole GPU suite (no stop at the fir
   ROUNDS=7 timeout 300 python scripts/pass_ab.py "ROWCONV=1024" "ROWCONV=2048" "ROWCONV=0" -- 16 32 > $O/r4b_rowconv_ab.txt 2>&1; cat $O/r4b_rowconv_ab.txt
   for G in 0 1 0 1; do LTK_GRAPH=$G timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4b_bench_g$G.json 2>> $O/r4b_bench.err
     python -c "import json; d=json.load(open('$O/r4b_bench_g$G.json')); print('graph $G', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['hipgraph'], d['pcie_inclusive']['value'])"; done ;;
-r4c)  # round-4 job C: per-phase rowconv for the small-map transposed convs
-  TAG=r4c MAXFAIL=--maxfail=20 bash $0 tests tests/test_wav2lip_gpu.py tests/test_mel_paste_gpu.py tests/test_plugin_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|rowconv" $O/pytest_r4c.log | tail -16
-  ROUNDS=9 timeout 300 python scripts/pass_ab.py "ROWCONVT=0" "ROWCONVT=1" -- 16 8 4 > $O/r4c_rowconvT_ab.txt 2>&1; cat $O/r4c_rowconvT_ab.txt
-  ROUNDS=3 timeout 300 python scripts/layer_times.py "ROWCONVT=0" "ROWCONVT=1" -- 16 2>&1 | grep -E "^====|face_decoder_blocks.[123]|^sum|^conv stack" > $O/r4c_rowconvT_layers.txt; cat $O/r4c_rowconvT_layers.txt ;;
-r4d)  # round-4 job D: conv3 stride-2 with the conflict-free LDS image (default routing and LTK_CONV_V3_S2=2 = every stride-2 3x3 layer on conv3); scheduler in-flight A/B
-  TAG=r4d MAXFAIL=--maxfail=20 bash $0 tests tests/test_conv_gpu.py tests/test_wav2lip_gpu.py tests/test_musetalk_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4d.log | tail -8
-  LTK_CONV_V3_S2=2 TAG=r4d_s2all MAXFAIL=--maxfail=20 bash $0 tests tests/test_conv_gpu.py tests/test_wav2lip_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4d_s2all.log | tail -8
-  for rnd in 1 2; do for V in 1 2; do
-    echo "######## round $rnd LTK_CONV_V3_S2=$V" >> $O/r4d_s2_layers.txt
-    LTK_CONV_V3_S2=$V ROUNDS=3 timeout 300 python scripts/layer_times.py "GRAPH=1" -- 16 256 2>&1 | grep -E "^====|face_encoder_blocks.[1-6].0|^sum|^conv stack" >> $O/r4d_s2_layers.txt
-  done; done; cat $O/r4d_s2_layers.txt
-  for IF in 1 2 1 2 1 2; do LTK_INFLIGHT=$IF timeout 300 python bench.py --full --sessions 16 --steps 12 --warmup 3 --no-also --no-cpu-baseline --no-traffic > $O/r4d_bench_s16_if$IF.json 2>> $O/r4d_bench_s16.err
-    python -c "import json,sys; d=json.load(open('$O/r4d_bench_s16_if$IF.json')); print('inflight $IF', d['value'], d['ms_per_step'], d['roofline']['frac'], d['scheduler'])" | tee -a $O/r4d_inflight.txt; done ;;
 r4e)  # round-4 job E: concurrency test, delivered capacity with / without the graph path, the MuseTalk sub-bench with its measured delivered run
   TAG=r4e MAXFAIL=--maxfail=20 bash $0 tests tests/test_plugin_gpu.py tests/test_mel_paste_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|in flight" $O/pytest_r4e.log | tail -8
   for G in 0 1 0 1; do LTK_GRAPH=$G timeout 400 python bench.py --sub delivered-capacity --batch 16 --delivered-sessions 384,448,512 > $O/r4e_delivered_g$G.json 2>> $O/r4e_delivered.err
@@ -125,15 +112,6 @@ for f in ('bgr24','i420'): print('graph $G', f, [(t['sessions'], t.get('latency_
   timeout 900 python bench.py --sub musetalk-both --batch 16 > $O/r4e_musetalk_both.json 2> $O/r4e_musetalk_both.err; python -c "
 import json; d=json.load(open('$O/r4e_musetalk_both.json'))
 for o in d: print(o.get('value'), o.get('roofline',{}).get('frac'), o.get('sessions_25fps'), json.dumps(o.get('delivered'))[:900])" ;;
-r4g)  # round-4 job G: MuseTalk small-map linear layers on rowconv
-  TAG=r4g MAXFAIL=--maxfail=20 bash $0 tests tests/test_musetalk_gpu.py tests/test_musetalk_plugin_gpu.py tests/test_fp8_gpu.py tests/test_wav2lip_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4g.log | tail -8
-  timeout 500 python scripts/mt_op_times.py 16 MT_ROWCONV=0,1024 2>&1 | grep -E "^====|conv/linear|GroupNorm|by block|->" > $O/r4g_mt_rowconv_ab.txt; head -60 $O/r4g_mt_rowconv_ab.txt
-  timeout 400 python scripts/mt_op_times.py 64 MT_ROWCONV=0,1024 2>&1 | grep -E "^====|conv/linear|->" > $O/r4g_mt_rowconv_ab64.txt; head -30 $O/r4g_mt_rowconv_ab64.txt ;;
-r4h)  # round-4 job H: MuseTalk per-level tile width of the U-Net's 3x3 convs
-  TAG=r4h MAXFAIL=--maxfail=20 bash $0 tests tests/test_musetalk_gpu.py tests/test_musetalk_plugin_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4h.log | tail -8
-  timeout 500 python scripts/mt_op_times.py 16 MT_TILE_TABLE=0,1 2>&1 | grep -E "^====|conv/linear|by block|->" > $O/r4h_mt_tile_ab.txt; grep -E "^====|->" $O/r4h_mt_tile_ab.txt | head -70 ;;
-r4i)  # round-4 job I: 128-cout blocks + forced split-K for the small-map linear layers of MuseTalk (conv3 1x1), per-op response
-  ALL_OPS=attentions,conv_shortcut timeout 500 python scripts/mt_op_times.py 16 MT_ROWCONV=1024,0,0+CONV3_NBT=0,4,4+KSPLIT=0,8,4 2>&1 | grep -E "^====| us  conv/linear" | grep -E "^====|down_blocks.2|mid_block|up_blocks.[01]" > $O/r4i_mt_nbt4_ops.txt; head -150 $O/r4i_mt_nbt4_ops.txt ;;
 r4m)  # round-4 job M: fused small-map GroupNorm (MuseTalk)
   TAG=r4m MAXFAIL=--maxfail=20 bash $0 tests tests/test_musetalk_gpu.py tests/test_musetalk_plugin_gpu.py tests/test_fp8_gpu.py > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4m.log | tail -8
   timeout 500 python scripts/mt_op_times.py 16 MT_GN_FUSED=0,1 2>&1 | grep -E "^====|GroupNorm|->" > $O/r4m_mt_gn_fused_ab.txt; grep -E "^====|GroupNorm " $O/r4m_mt_gn_fused_ab.txt | head; grep -E "\->" $O/r4m_mt_gn_fused_ab.txt | head -70 ;;
@@ -142,7 +120,7 @@ r4vs3)  # the round-3 tree (build/r03tree: git archive 367ff43 + make) against t
   for rnd in 1 2 3; do for T in r03 r04; do
     D=$R; [ $T = r03 ] && D=$R/build/r03tree
     echo "######## round $rnd tree $T: conv stack / pass (scripts/layer_times.py, 3 rounds; us)" >> $L
-    (cd $D && ROUNDS=3 timeout 300 python scripts/layer_times.py "TILE_RULE=1" -- 16 256 2>&1 | grep -E "^====|^sum|^conv stack") >> $L
+    (cd $D && ROUNDS=3 timeout 300 python scripts/layer_times.py "GRAPH=1" -- 16 256 2>&1 | grep -E "^====|^sum|^conv stack") >> $L
     echo "######## round $rnd tree $T: timed line (bench.py --steps 100, 1 session x 16 frames)" >> $L
     (cd $D && timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['frac'])") >> $L
   done; done
@@ -157,21 +135,6 @@ r4n)  # round-4 job N: the final default (GRAPH = 1: replay from 48 frames on) -
   for G in 1 2 1 2 1 2; do LTK_GRAPH=$G timeout 300 python bench.py --full --steps 100 --warmup 5 --no-also --no-cpu-baseline --no-traffic > $O/r4n_bench_g$G.json 2>> $O/r4n_bench.err
     python -c "import json; d=json.load(open('$O/r4n_bench_g$G.json')); print('GRAPH=$G', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], d['roofline']['frac'], d['roofline']['hipgraph'])" | tee -a $O/r4n_graph_auto_ab.txt; done
   timeout 600 python bench.py --full > $O/r4n_bench_default.json 2> $O/r4n_bench_default.err; head -c 300 $O/r4n_bench_default.json ;;
-r4p)  # round-4 job P: row-parity LDS key on tiles narrower than 32 pixels (conv3 stride 1): in-job A/B first, then the whole -m gpu suite, smoke, a bench line
-  L=$O/r4p_lds_swz_ab.txt; : > $L
-  ROUNDS=5 timeout 300 python scripts/pass_ab.py "LDS_SWZ=0" "LDS_SWZ=1" -- 16 64 256 2>&1 | grep -E "^settings|frames" >> $L
-  timeout 400 python scripts/mt_op_times.py 16 LDS_SWZ=0,1 2>&1 | grep -E "^====|conv/linear|->" > $O/r4p_mt_lds_swz_ab.txt; grep -E "^====|conv/linear " $O/r4p_mt_lds_swz_ab.txt | head -12 >> $L; cat $L
-  TAG=r4p MAXFAIL=--maxfail=20 bash $0 tests tests > /dev/null 2>&1; grep -E "passed|failed|FAILED" $O/pytest_r4p.log | tail -8
-  timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" 2>&1 | tail -2
-  timeout 400 python bench.py --full --no-cpu-baseline > $O/r4p_bench.json 2> $O/r4p_bench.err; head -c 600 $O/r4p_bench.json ;;
-r4q)  # round-4 job Q: SQ_LDS_BANK_CONFLICT of the MuseTalk pass (then the 256-frame Wav2Lip pass) under the column key and the row key (separate --pmc runs, eager launches)
-  cd /tmp && export TMPDIR=/tmp; export LTK_GRAPH=0
-  for W in mt w2l256; do
-    [ $W = mt ] && A="--model musetalk --steps 2 --warmup 1" || A="--sessions 16 --steps 2 --warmup 1"
-    for K in 0 1; do LTK_LDS_SWZ=$K timeout 130 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $O/r4q/${W}_swz$K -o r -- python $R/bench.py --full $A --no-cpu-baseline --no-also --no-traffic > $O/r4q_${W}_swz$K.log 2>&1; done
-    python $R/scripts/lds_conflict_report.py column-key=$O/r4q/${W}_swz0 row-key=$O/r4q/${W}_swz1 > $O/r4q_lds_conflicts_$W.txt 2>&1; head -30 $O/r4q_lds_conflicts_$W.txt
-    rm -rf $O/r4q/${W}_swz0 $O/r4q/${W}_swz1
-  done ;;
 r4r)  # round-4 job R: host-path trims (unbind, lazy bank indices, scheduler solo path): the plugin-level GPU tests, then the timed line (gap = ms_per_step - device pass)
   TAG=r4r MAXFAIL=--maxfail=20 timeout 120 bash $0 tests tests/test_plugin_gpu.py tests/test_egress_gpu.py tests/test_ref_loop.py > /dev/null 2>&1; grep -E "passed|failed|FAILED|rror" $O/pytest_r4r.log | tail -8
   for i in 1 2; do timeout 40 python bench.py --full --steps 200 --warmup 10 --no-also --no-cpu-baseline --no-traffic 2>> $O/r4r_bench.err | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('timed line', d['value'], d['ms_per_step'], d['roofline']['conv_stack_ms'], round(1e3*(d['ms_per_step']-d['roofline']['conv_stack_ms']),1), 'us host gap')" | tee -a $O/r4r_host_gap.txt; done

@@ -2,7 +2,7 @@
 """lin_fk_kernel against conv3's 1x1 path on the linear-layer shapes of MuseTalk's 32^2 / 16^2 transformer levels (16 frames):
 single-layer launches through ltk_conv2d_f16, knob LIN_FK = 0 / 1 interleaved, average of `iters` back-to-back launches.  GPU only.
 
-    python scripts/lin_fk_ab.py [iters] [LIN_FK_BLOCKS values...]
+    python scripts/lin_fk_ab.py [iters]
 """
 import os
 import sys
@@ -32,28 +32,25 @@ SHAPES = [  # (N, H, Cin, Cout, residual, name)
 
 def main():
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
-    blocks = [v for v in sys.argv[2:]] or ["512"]          # LIN_FK_BLOCKS values
     eng = Engine(0)
     if os.environ.get("LIN_MP"):
         Engine.set_knob("LIN_MP", int(os.environ["LIN_MP"]))
     g = torch.Generator(device="cpu").manual_seed(1)
-    settings = [("conv3", 0, "0")] + [(f"lin_fk/{b}", 1, b) for b in blocks]
-    print("us per launch: " + " | ".join(n for n, _, _ in settings))
+    settings = [("conv3", 0), ("lin_fk", 1)]
+    print("us per launch: " + " | ".join(n for n, _ in settings))
     for N, H, Cin, Cout, res, name in SHAPES:
         x = to_cb16(torch.randn(N, Cin, H, H, generator=g).cuda())
         w = (torch.randn(Cout, Cin, 1, 1, generator=g) * (2.0 / Cin) ** 0.5).numpy()
         y = empty_cb16(N, Cout, H, H)
-        t = {n: [] for n, _, _ in settings}
+        t = {n: [] for n, _ in settings}
         for rnd in range(3):
-            for n, fk, b in settings:
+            for n, fk in settings:
                 Engine.set_knob("LIN_FK", fk)
-                if fk:
-                    Engine.set_knob("LIN_FK_BLOCKS", int(b.split(":")[0]))
                 ms = eng.conv2d_f16(x.data_ptr(), N, H, H, Cin, w, Cout, 1, 1, 0, False, 0, None, None, x.data_ptr() if res and Cin == Cout else 0, False,
                                     y.data_ptr(), iters)
                 t[n].append(ms * 1e3)
         gf = 2.0 * N * H * H * Cin * Cout / 1e9
-        print(f"{name:32s} M={N * H * H:6d} K={Cin} N={Cout:5d} {gf:6.1f} GFLOP  " + " | ".join(f"{np.median(t[n]):7.1f}" for n, _, _ in settings))
+        print(f"{name:32s} M={N * H * H:6d} K={Cin} N={Cout:5d} {gf:6.1f} GFLOP  " + " | ".join(f"{np.median(t[n]):7.1f}" for n, _ in settings))
     eng.close()
 
 
