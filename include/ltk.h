@@ -73,7 +73,8 @@ int ltk_wav2lip_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int max_f
  * (coords.pkl, avatars/wav2lip/genavatar.py:130).  Host pointers. */
 int ltk_avatar_register(ltk_engine* e, const uint8_t* face_bank, const uint8_t* full_bank,
                         const int32_t* coords, int n, int H, int W, int* avatar_id);
-/* Drops a bank registered by ltk_avatar_register or ltk_musetalk_avatar_register (ids of both kinds come from one counter).
+/* Drops a bank registered by ltk_avatar_register, ltk_musetalk_avatar_register or ltk_ultralight_avatar_register (ids of all kinds come
+ * from one counter).
  * Safe while other threads render from it: every call holds a reference to its bank until it returns, the device buffers are
  * freed when the last of them does. */
 int ltk_avatar_release(ltk_engine* e, int avatar_id);
@@ -157,6 +158,40 @@ int ltk_musetalk_infer(ltk_engine* e, const ltk_mt_req* reqs, int nreq, void* st
  * resize the 256x256 prediction to the face box, paste into the crop region and cv2.blendLinear it with the
  * cached frame under the avatar's mask.  out: uint8 [H][W][3] (device or host, as ltk_paste_back). */
 int ltk_paste_blend(ltk_engine* e, int avatar_id, int idx, const void* d_pred, void* out, int out_is_device, void* stream);
+
+/* =========================== Ultralight path (avatars/ultralight_avatar.py) =========================== */
+
+/* avatars/ultralight_avatar.py:63-81 load_avatar.  The model is per avatar (`ultralight.pth`, :69-70), so the state_dict travels with
+ * the bank: sd = the 484 tensors of avatars/ultralight/unet.py Model(6, 'hubert') under their names, fp32 host (the
+ * num_batches_tracked counters may be left out).  Eval-mode BatchNorm is folded into per-channel scale / shift, the 1x1 / dense
+ * kernels are repacked to fp16 MFMA tiles, the depthwise kernels stay fp32.  face_bank uint8 [n][168][168][3] BGR (face_imgs/),
+ * full_bank uint8 [n][H][W][3] BGR (full_imgs/), coords int32 [n][4] = (x1,y1,x2,y2) (coords.pkl, :176).  Host pointers.
+ * max_frames (1..256) sizes the engine's Ultralight activation arena (frames per launch; it grows to the largest value asked for,
+ * longer requests run as several launches).  The id comes from the counter ltk_avatar_register uses; ltk_avatar_release frees the
+ * avatar.  A missing tensor, a wrong shape or a box outside the frame returns LTK_E_INVALID with a message. */
+int ltk_ultralight_avatar_register(ltk_engine* e, const ltk_named_tensor* sd, int n_tensors, const uint8_t* face_bank,
+                                   const uint8_t* full_bank, const int32_t* coords, int n, int H, int W, int max_frames, int* avatar_id);
+
+typedef struct ltk_ul_req {
+    int avatar;            /* id returned by ltk_ultralight_avatar_register */
+    int index;             /* running frame index (mirror_index over the face bank) */
+    int batch;
+    const void* d_feat;    /* device, float32 [batch][16][32][32]: the (16, 1024) HuBERT chunks of HubertASR, reshaped (:164) */
+    void* d_pred;          /* device, uint8 [batch][160][160][3] BGR */
+} ltk_ul_req;
+
+/* avatars/ultralight_avatar.py:143-171 LightReal.inference_batch for `nreq` sessions at once: bank gather, the [4:164, 4:164] crop,
+ * the zeroed rectangle (5, 5, 150, 145) of the masked copy and the 6-channel pack (fused into the first kernel's loads),
+ * Model.forward (unet.py:198-215), and trunc(sigmoid * 255) as paste_back_frame's astype(uint8) applies it (:170,181).  Requests may
+ * name different avatars (each runs its own weights).  Return contract as ltk_wav2lip_infer: returns when the frames are ready,
+ * an error return leaves none of the call's launches in flight.  A frame count's pass runs eagerly the first time, is captured
+ * the second time and replayed afterwards (knob GRAPH, counted by ltk_program_graph_count). */
+int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* stream);
+
+/* avatars/ultralight_avatar.py:173-184 LightReal.paste_back_frame: the 168x168 bank face with the prediction written at
+ * [4:164, 4:164], bilinear-resized (cv2.resize INTER_LINEAR semantics) to the frame's box and pasted into a copy of full_bank[idx].
+ * d_pred: device uint8 [160][160][3].  out: uint8 [H][W][3], device or host as ltk_paste_back. */
+int ltk_ultralight_paste_back(ltk_engine* e, int avatar_id, int idx, const void* d_pred, void* out, int out_is_device, void* stream);
 
 /* ---- frame egress: the steps between paste_back_frame and the encoder ------------
  * Reference: avatars/base_avatar.py:384-453 process_frames (silent path :407-428, transition blend :419-426 and
@@ -255,6 +290,27 @@ int ltk_musetalk_time_ops(ltk_engine* e, int frames, int iters, float* ms_per_op
  * host float32 [B][6][256][256] in [0,1] (as wav2lip_avatar.py:133-134 builds
  * them); pred host float32 [B][3][256][256] = sigmoid output (before *255). */
 int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6, int B, float* pred);
+
+/* Model.forward of an Ultralight avatar on explicit inputs (avatars/ultralight_avatar.py:85-90 warm_up, tests): img6 host float32
+ * [B][6][160][160] in [0,1] (reference crop then masked crop, BGR, as :156-161 builds them), feat host float32 [B][16][32][32];
+ * pred host float32 [B][3][160][160] = the sigmoid output (before * 255).  With ltk_debug_capture on, every launch's output is kept
+ * under its state_dict prefix for ltk_debug_get ("inc.inconv.0.conv.0", "down1.maxpool_conv.0.double_conv.1.conv.6", "audio_model.conv3",
+ * "up1.up", "outc.conv", ...): a conv's tap is the tensor after its BatchNorm, ReLU and residual add. */
+int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6, const float* feat, int B, float* pred);
+/* average milliseconds of one pass of `frames` frames as ltk_ultralight_infer enqueues it (replayed graph under knob GRAPH), on
+ * dummy inputs, and the MACs (dense + depthwise + head) it executes */
+int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, float* ms_per_pass, double* macs_per_pass);
+
+/* Standalone depthwise 3x3 conv (nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False), avatars/ultralight/unet.py:19-25) used by kernel
+ * unit tests: x device fp16 [N][C/16][H][W][16], weight host fp32 [C][1][3][3], scale / shift host fp32 [C] (NULL = 1 / 0), stride 1
+ * or 2, zero padding 1; y device fp16 [N][C/16][Ho][Wo][16] = act(conv * scale + shift), Ho = (H - 1) / stride + 1. */
+int ltk_dwconv3x3_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, const float* weight, int stride, const float* scale,
+                      const float* shift, int relu, void* d_y);
+/* Standalone Up.forward head (unet.py:79-85): y[:, :C_up] = nn.Upsample(scale_factor=2, bilinear, align_corners=True)(x),
+ * y[:, C_up:] = skip.  x device fp16 [N][C_up/16][h][w][16], skip [N][C_skip/16][Hs][Ws][16], y [N][(C_up+C_skip)/16][2h][2w][16];
+ * LTK_E_INVALID unless Hs == 2h and Ws == 2w (the reference pads; the network never needs it at 160 x 160). */
+int ltk_upsample2x_cat_f16(ltk_engine* e, const void* d_x, int N, int h, int w, int C_up, const void* d_skip, int Hs, int Ws, int C_skip,
+                           void* d_y);
 
 /* After a forward with capture enabled, copy one layer's activation
  * (state_dict prefix, e.g. "face_encoder_blocks.1.0") as NCHW float32. */

@@ -1,0 +1,116 @@
+"""Drop-in for avatars/audio_features/hubert.py (HubertASR), the audio front end of the Ultralight avatar.
+
+Same class name, constructor `(opt, parent, audio_processor, audio_feat_length)`, queue protocol and step cadence as the
+reference (hubert.py:13-49): every `run_step` pulls 2*batch_size 20-ms chunks, forwards them to `output_queue`, and - once
+l+r chunks of context exist - puts ONE list of batch_size feature chunks on `feat_queue` and keeps the last l+r chunks.
+With `audio_feat_length=[4, 4]` (ultralight_avatar.py:140), start = l/2 and multiplier 2, frame i takes HuBERT rows
+[2*(i + l/2) - 8, 2*(i + l/2) + 8), index-clamped (base_asr.py:91-133): 16 rows of 1024 per frame.
+
+HuBERT-large itself (24 transformer layers) is NOT on the engine: `audio_processor` is any object with
+`get_hubert_from_16k_speech(pcm) -> (T, 1024)` - the reference's Audio2Feature, `load_model()` below, or a test stand-in.
+The engine's part starts at these chunks (Engine.ultralight_infer takes them as float32 [batch][16][32][32]).
+
+One deliberate difference: the reference's silent default is `batch_size * [zeros((10, 1024))]` (hubert.py:38), which
+LightReal.inference_batch cannot reshape to (16, 32, 32); the silent chunks here are zeros((16, 1024)).
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from ...hostshim import BaseASR
+
+HUBERT_DIR = "./models/hubert-large-ls960-ft"      # avatars/ultralight/audio2feature.py:9-10
+
+
+class Audio2Feature:
+    """avatars/ultralight/audio2feature.py:6-53: transformers' HuBERT-large on torch (ROCm build: device "cuda")."""
+
+    def __init__(self, model_dir: str = HUBERT_DIR):
+        import torch
+        from transformers import HubertModel, Wav2Vec2Processor
+        self._torch = torch
+        self.device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.processor = Wav2Vec2Processor.from_pretrained(model_dir)
+        self.model = HubertModel.from_pretrained(model_dir).to(self.device)
+        self.model.requires_grad_(False)
+
+    def get_hubert_from_16k_speech(self, speech):
+        torch = self._torch
+        if speech.ndim == 2:
+            speech = speech[:, 0]
+        with torch.no_grad():
+            x = self.processor(speech, return_tensors="pt", sampling_rate=16000).input_values.to(self.device)
+            kernel, stride = 400, 320
+            clip = stride * 1000
+            expected = (x.shape[1] - (kernel - stride)) // stride
+            parts = []
+            n_iter = x.shape[1] // clip
+            for i in range(n_iter):
+                parts.append(self.model(x[:, clip * i: clip * i + clip - stride + kernel]).last_hidden_state[0])
+            tail = x[:, clip * n_iter:]
+            if tail.shape[1] >= kernel:
+                parts.append(self.model(tail).last_hidden_state[0])
+            ret = torch.cat(parts, dim=0).cpu()
+            if abs(ret.shape[0] - expected) > 1:
+                raise RuntimeError(f"HuBERT returned {ret.shape[0]} rows for {expected} expected")
+            if ret.shape[0] < expected:
+                ret = torch.nn.functional.pad(ret, (0, 0, 0, expected - ret.shape[0]))
+            return ret[:expected]
+
+
+def load_model(model_dir: str = HUBERT_DIR) -> Audio2Feature:
+    """The audio processor ultralight_avatar.load_model hands to every session (ultralight_avatar.py:58-61)."""
+    if not os.path.isdir(model_dir):
+        raise FileNotFoundError(
+            f"{model_dir} is missing: the Ultralight avatar needs the HuBERT-large checkpoint the reference uses "
+            "(facebook/hubert-large-ls960-ft) there, or pass your own audio_processor with get_hubert_from_16k_speech()")
+    return Audio2Feature(model_dir)
+
+
+def feature2chunks(feature_array, batch_size, audio_feat_win, start, feature_idx_multiplier):
+    """base_asr.py:91-156 (_get_sliced_feature + _feature2chunks): frame i takes rows
+    [int((i + start) * m) - win[0] * m, int((i + start) * m) + win[1] * m), every index clamped into the array."""
+    feature_array = np.asarray(feature_array)
+    length = feature_array.shape[0]
+    chunks = []
+    for i in range(batch_size):
+        center = int((i + start) * feature_idx_multiplier)
+        left = int(center - audio_feat_win[0] * feature_idx_multiplier)
+        right = int(center + audio_feat_win[1] * feature_idx_multiplier)
+        idx = np.clip(np.arange(left, right), 0, length - 1)
+        chunks.append(np.ascontiguousarray(feature_array[idx], dtype=np.float32))
+    return chunks
+
+
+class HubertASR(BaseASR):
+    def __init__(self, opt, parent, audio_processor, audio_feat_length=[8, 8]):
+        super().__init__(opt, parent)
+        if not hasattr(audio_processor, "get_hubert_from_16k_speech"):
+            raise TypeError("audio_processor must provide get_hubert_from_16k_speech(pcm)")
+        self.audio_processor = audio_processor
+        self.audio_feat_length = audio_feat_length
+        self.last_is_silence = True
+
+    def run_step(self):
+        is_all_silence = True
+        for _ in range(self.batch_size * 2):
+            audio_frame = self.get_audio_frame()
+            if audio_frame.type == 0:
+                is_all_silence = False
+            self.frames.append(audio_frame.data)
+            self.output_queue.put(audio_frame)
+        if len(self.frames) <= self.stride_left_size + self.stride_right_size:
+            return
+        rows = 2 * (self.audio_feat_length[0] + self.audio_feat_length[1])
+        chunks = [np.zeros((rows, 1024), dtype=np.float32) for _ in range(self.batch_size)]
+        if not is_all_silence or not self.last_is_silence:
+            inputs = np.concatenate(self.frames)
+            feat = self.audio_processor.get_hubert_from_16k_speech(inputs)
+            if hasattr(feat, "detach"):
+                feat = feat.detach().cpu().numpy()
+            chunks = feature2chunks(feat, self.batch_size, self.audio_feat_length, self.stride_left_size / 2, 2)
+        self.feat_queue.put(chunks)
+        self.frames = self.frames[-(self.stride_left_size + self.stride_right_size):]
+        self.last_is_silence = is_all_silence

@@ -1,0 +1,151 @@
+"""HIP-backed drop-in for avatars/ultralight_avatar.py.
+
+Module contract the reference's app.py relies on (the plugin is picked by name):
+  load_model(opt) -> (audio_processor, model)            (ultralight_avatar.py:58-61)
+  load_avatar(avatar_id) -> avatar tuple                 (ultralight_avatar.py:63-81)
+  warm_up(batch_size, avatar, modelres)                  (ultralight_avatar.py:84-90)
+  @register("avatar", "ultralight") class LightReal(BaseAvatar) with
+  inference_batch(index, audiofeat_batch) and paste_back_frame(pred_frame, idx)   (ultralight_avatar.py:125-184)
+
+What changes underneath: the U-Net is per avatar (`ultralight.pth`), so `load_avatar` returns an `UltralightNet` handle in the
+model's place; it registers state_dict + bank with the engine (libltk_hip.so) on first use.  `inference_batch` returns device
+handles (uint8 160x160x3, already truncated the way paste_back_frame's astype(uint8) does) instead of float numpy frames;
+`paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array.  HuBERT-large stays on
+torch (audio_features/hubert.py).
+"""
+from __future__ import annotations
+
+import glob
+import os
+import pickle
+import threading
+
+import numpy as np
+
+from ..engine import Engine
+from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror_index: part of the reference module's namespace)
+from .audio_features.hubert import HubertASR
+from .audio_features import hubert as _hubert
+
+_engines = {}
+_engines_lock = threading.Lock()
+
+
+def _engine(device: int = 0) -> Engine:
+    """One engine per GPU and process, shared by every Ultralight avatar and session."""
+    with _engines_lock:
+        eng = _engines.get(device)
+        if eng is None or eng._h is None:
+            eng = _engines[device] = Engine(device)
+        return eng
+
+
+class UltralightNet:
+    """Stands where the reference's `Model(6, 'hubert')` stands in the avatar tuple: the state_dict plus, once a session
+    or warm_up needs it, the engine-side avatar (weights folded and packed, bank in HBM)."""
+
+    def __init__(self, state_dict, face_list, frame_list, coord_list, engine=None, max_frames=None):
+        self.state_dict = state_dict
+        self._bank = (face_list, frame_list, coord_list)
+        self.engine = engine
+        self.max_frames = int(max_frames or os.environ.get("LTK_UL_MAX_FRAMES", "32"))
+        self._aid = None
+        self._lock = threading.Lock()
+
+    def avatar_id(self) -> int:
+        with self._lock:
+            if self._aid is None:
+                if self.engine is None:
+                    self.engine = _engine(0)
+                faces, frames, coords = self._bank
+                self._aid = self.engine.register_ultralight_avatar(self.state_dict, faces, frames, coords, max_frames=self.max_frames)
+            return self._aid
+
+    def release(self):
+        with self._lock:
+            if self._aid is not None:
+                self.engine.release_avatar(self._aid)
+                self._aid = None
+
+    def eval(self):
+        return self
+
+
+def load_model(opt):
+    """ultralight_avatar.py:58-61: (audio_processor, None) - the U-Net comes with the avatar."""
+    audio_processor = _hubert.load_model()
+    model = None
+    return audio_processor, model
+
+
+def read_imgs(img_list):
+    import cv2  # same third-party reader the reference uses (utils/image.py:14-24)
+    return [cv2.imread(p) for p in img_list]
+
+
+def load_avatar(avatar_id):
+    import torch
+    avatar_path = f"./data/avatars/{avatar_id}"
+    sd = torch.load(f"{avatar_path}/ultralight.pth", map_location="cpu")
+    with open(f"{avatar_path}/coords.pkl", "rb") as f:
+        coord_list_cycle = pickle.load(f)
+
+    def numbered(d):
+        files = glob.glob(os.path.join(d, "*.[jpJP][pnPN]*[gG]"))
+        return sorted(files, key=lambda x: int(os.path.splitext(os.path.basename(x))[0]))
+
+    frame_list_cycle = read_imgs(numbered(f"{avatar_path}/full_imgs"))
+    face_list_cycle = read_imgs(numbered(f"{avatar_path}/face_imgs"))
+    model = UltralightNet(sd, face_list_cycle, frame_list_cycle, coord_list_cycle)
+    return model.eval(), frame_list_cycle, face_list_cycle, coord_list_cycle
+
+
+def warm_up(batch_size, avatar, modelres):
+    """One forward on ones, as the reference does, to fault in kernels and arena."""
+    model, _, _, _ = avatar
+    aid = model.avatar_id()
+    n = min(batch_size, model.max_frames)
+    img = np.ones((n, 6, modelres, modelres), dtype=np.float32)
+    feat = np.ones((n, 16, 32, 32), dtype=np.float32)
+    model.engine.ultralight_forward_host(aid, img, feat)
+
+
+@register("avatar", "ultralight")
+class LightReal(BaseAvatar):
+    def __init__(self, opt, model, avatar):
+        super().__init__(opt)
+        audio_processor, _ = model
+        self.model, self.frame_list_cycle, self.face_list_cycle, self.coord_list_cycle = avatar
+        self._aid = self.model.avatar_id()
+        self.engine = self.model.engine
+        h, w = self.frame_list_cycle[0].shape[:2]
+        self._frame_hw = (int(h), int(w))
+        self.asr = HubertASR(opt, self, audio_processor, audio_feat_length=[4, 4])
+        self.asr.warm_up()
+
+    def _feat_to_device(self, audiofeat_batch):
+        import torch
+        if isinstance(audiofeat_batch, torch.Tensor):
+            return audiofeat_batch.to(self.engine.torch_device, torch.float32).reshape(-1, 16, 32, 32).contiguous()
+        arr = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float32).reshape(16, 32, 32) for a in audiofeat_batch]))
+        return torch.from_numpy(arr).to(self.engine.torch_device)
+
+    def inference_batch(self, index, audiofeat_batch):
+        """Returns batch_size device handles (uint8 [160][160][3] BGR), item i for bank index mirror_index(len, index+i)."""
+        import torch
+        feat = self._feat_to_device(audiofeat_batch)
+        B = self.batch_size
+        if feat.shape[0] != B:
+            raise ValueError(f"expected {B} feature chunks, got {feat.shape[0]}")
+        pred = torch.empty((B, 160, 160, 3), dtype=torch.uint8, device=feat.device)
+        self.engine.ultralight_infer([(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())])
+        return list(pred.unbind(0))
+
+    def paste_back_frame(self, pred_frame, idx: int):
+        import torch
+        if not isinstance(pred_frame, torch.Tensor):   # a float frame from a foreign inference_batch
+            pred_frame = torch.from_numpy(np.ascontiguousarray(pred_frame).astype(np.uint8)).to(self.engine.torch_device)
+        h, w = self._frame_hw
+        out = np.empty((h, w, 3), dtype=np.uint8)
+        self.engine.ultralight_paste_back(self._aid, int(idx), pred_frame.contiguous().data_ptr(), out)
+        return out

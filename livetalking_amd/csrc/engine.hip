@@ -1,6 +1,8 @@
 // libltk_hip.so: engine lifetime, avatar banks, mel step and paste-back of the C ABI (include/ltk.h).  The Wav2Lip program is
 // in w2l_program.hip, its inference path in w2l_infer.hip, MuseTalk / Whisper / VAE encoder in mt_engine.hip, frame egress in
-// egress.hip, the test and measurement hooks in engine_debug.hip; engine_internal.h is what they share.
+// egress.hip, the test and measurement hooks in engine_debug.hip; engine_internal.h is what they share.  The Ultralight avatar
+// (ultralight.hip: its launch program, register / infer / paste-back; dw_kernels.hip: its VALU kernels) is included at the end of
+// this file and compiled with it.
 #include "engine_internal.h"
 
 thread_local std::string ltk::g_err;
@@ -96,6 +98,7 @@ void ltk_engine_destroy(ltk_engine* e) {
     e->avatars.clear();
     e->mt_avatars.clear();
     e->prog_graphs.drop();
+    ul_unload(e);
     if (e->mt) mt_graph_delete(e->mt);
     if (e->whisper) mt_graph_delete(e->whisper);
     if (e->vae_enc) mt_graph_delete(e->vae_enc);
@@ -165,12 +168,15 @@ int ltk_avatar_release(ltk_engine* e, int avatar_id) {
                 sl.valid = false;
                 sl.hold.reset();
             }
+        ul_drop_graphs(e, avatar_id);        // the captured passes of an Ultralight avatar hold its weights' addresses
     }
     std::lock_guard<std::mutex> g(e->pool_mu);
     auto it = e->avatars.find(avatar_id);
     if (it != e->avatars.end()) { e->avatars.erase(it); return LTK_OK; }      // buffers go with the last call that still uses them
     auto mt = e->mt_avatars.find(avatar_id);                                       // ids of both kinds come from one counter
     if (mt != e->mt_avatars.end()) { e->mt_avatars.erase(mt); return LTK_OK; }
+    auto ul = e->ul_avatars.find(avatar_id);
+    if (ul != e->ul_avatars.end()) { e->ul_avatars.erase(ul); return LTK_OK; }
     return fail(LTK_E_STATE, "unknown avatar id");
 }
 
@@ -286,3 +292,5 @@ int ltk_paste_blend(ltk_engine* e, int avatar_id, int idx, const void* d_pred, v
 }
 
 }  // extern "C"
+
+#include "ultralight.hip"

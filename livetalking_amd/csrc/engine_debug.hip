@@ -332,6 +332,122 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
     return rc;
 }
 
+// ------------------------------------------------------------------ Ultralight hooks
+int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6, const float* feat, int B, float* pred) {
+    if (!e || !img6 || !feat || !pred || B <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
+    if (!ap) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    CHK(enter_device(e->device));
+    constexpr size_t P = (size_t)kUlRes * kUlRes;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int cap = std::min(std::min(e->ul_frames, kPackMaxFrames), B);
+    if (cap <= 0) return fail(LTK_E_STATE, "no Ultralight arena");
+    if (e->capture && B > cap) return fail(LTK_E_INVALID, "layer capture needs B <= max_frames");
+    DevBuf d_img, d_feat, d_pred;
+    CHK(hipMalloc(&d_img.p, cap * 6 * P * sizeof(float)));
+    CHK(hipMalloc(&d_feat.p, (size_t)cap * 16 * 1024 * sizeof(float)));
+    CHK(hipMalloc(&d_pred.p, cap * 3 * P * sizeof(float)));
+    for (int f0 = 0; f0 < B; f0 += cap) {
+        const int nf = std::min(cap, B - f0);
+        CHK(hipMemcpy(d_img.p, img6 + f0 * 6 * P, nf * 6 * P * sizeof(float), hipMemcpyHostToDevice));
+        CHK(hipMemcpy(d_feat.p, feat + (size_t)f0 * 16 * 1024, (size_t)nf * 16 * 1024 * sizeof(float), hipMemcpyHostToDevice));
+        MelPtrs mp;
+        for (int i = 0; i < nf; ++i) mp.p[i] = (const float*)d_feat.p + (size_t)i * 16 * 1024;
+        launch_upload_tables(nullptr, &mp, nullptr, nf, e->ul_tab, e->compute);
+        CHK(hipGetLastError());
+        const int rc = ul_pass(e, *ap, nf, false, (const float*)d_img.p, false, (float*)d_pred.p);
+        const hipError_t se = hipStreamSynchronize(e->compute);
+        if (rc) return rc;
+        if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight forward: ") + hipGetErrorString(se));
+        CHK(hipMemcpy(pred + f0 * 3 * P, d_pred.p, nf * 3 * P * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return LTK_OK;
+}
+
+int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, float* ms_per_pass, double* macs_per_pass) {
+    if (!e || frames <= 0 || iters <= 0 || !ms_per_pass) return fail(LTK_E_INVALID, "bad arguments");
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
+    if (!ap) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
+    if (frames > e->ul_frames || frames > kPackMaxFrames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
+    // every frame reads the avatar's first bank crop and one zero chunk and writes its own scratch frame: the pass as
+    // ltk_ultralight_infer enqueues it
+    DevBuf d_feat, d_frames;
+    CHK(hipMalloc(&d_feat.p, 16 * 1024 * sizeof(float)));
+    CHK(hipMemset(d_feat.p, 0, 16 * 1024 * sizeof(float)));
+    CHK(hipMalloc(&d_frames.p, (size_t)frames * kUlRes * kUlRes * 3));
+    FacePtrs fp; MelPtrs mp; OutPtrs op;
+    for (int i = 0; i < frames; ++i) { fp.p[i] = ap->d_face; mp.p[i] = (const float*)d_feat.p; op.p[i] = (uint8_t*)d_frames.p + (size_t)i * kUlRes * kUlRes * 3; }
+    launch_upload_tables(&fp, &mp, &op, frames, e->ul_tab, e->compute);
+    CHK(hipGetLastError());
+    int rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr);      // eager
+    if (!rc) rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr); // captures under knob GRAPH
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (!rc && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess)) rc = fail(LTK_E_HIP, "hipEventCreate failed");
+    if (!rc) {
+        (void)hipEventRecord(t0, e->compute);
+        for (int i = 0; i < iters && !rc; ++i) rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr);
+        (void)hipEventRecord(t1, e->compute);
+    }
+    const hipError_t se = hipStreamSynchronize(e->compute);       // before the scratch buffers go
+    float ms = 0.f;
+    if (!rc && se == hipSuccess) (void)hipEventElapsedTime(&ms, t0, t1);
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    if (rc) return rc;
+    if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight pass: ") + hipGetErrorString(se));
+    *ms_per_pass = ms / iters;
+    if (macs_per_pass) *macs_per_pass = ul_macs_per_frame(*ap) * frames;
+    return LTK_OK;
+}
+
+int ltk_dwconv3x3_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, const float* weight, int stride, const float* scale,
+                      const float* shift, int relu, void* d_y) {
+    if (!e || !d_x || !weight || !d_y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (C % 16 || (stride != 1 && stride != 2)) return fail(LTK_E_INVALID, "depthwise conv: C % 16 == 0, stride 1 or 2");
+    if ((long long)N * (C / 16) > 65535 || (double)N * C * H * W >= 2147483647.0) return fail(LTK_E_INVALID, "depthwise conv: tensor too large");
+    CHK(enter_device(e->device));
+    std::vector<float> h((size_t)C * 11);
+    for (int c = 0; c < C; ++c) {
+        for (int t = 0; t < 9; ++t) h[((size_t)(c >> 4) * 9 + t) * 16 + (c & 15)] = weight[(size_t)c * 9 + t];
+        h[(size_t)C * 9 + c] = scale ? scale[c] : 1.f;
+        h[(size_t)C * 10 + c] = shift ? shift[c] : 0.f;
+    }
+    DevBuf d_w;
+    CHK(hipMalloc(&d_w.p, h.size() * sizeof(float)));
+    CHK(hipMemcpy(d_w.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::lock_guard<std::mutex> g(e->mu);
+    const float* w = (const float*)d_w.p;
+    launch_dwconv3x3((const f16*)d_x, N, C / 16, 0, C, H, W, stride, w, w + (size_t)C * 9, w + (size_t)C * 10, relu, (f16*)d_y, C / 16, 0, e->compute);
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(e->compute);
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("depthwise conv kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
+int ltk_upsample2x_cat_f16(ltk_engine* e, const void* d_x, int N, int h, int w, int C_up, const void* d_skip, int Hs, int Ws, int C_skip,
+                           void* d_y) {
+    if (!e || !d_x || !d_skip || !d_y || N <= 0 || h <= 0 || w <= 0 || C_up <= 0 || C_skip <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (C_up % 16 || C_skip % 16) return fail(LTK_E_INVALID, "upsample + concat: channel counts must be multiples of 16");
+    if (Hs != 2 * h || Ws != 2 * w) return fail(LTK_E_INVALID, "upsample + concat: the skip tensor must be 2h x 2w");
+    const int CT = C_up + C_skip;
+    if ((long long)N * (C_up / 16) > 65535 || (double)N * CT * Hs * Ws >= 2147483647.0) return fail(LTK_E_INVALID, "upsample + concat: tensor too large");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    hipStream_t s = e->compute;
+    launch_upsample2x((const f16*)d_x, N, C_up / 16, 0, C_up, h, w, (f16*)d_y, CT / 16, 0, s);
+    hipError_t le = hipGetLastError();
+    // the skip half: image n's C_skip x Hs x Ws halfs behind its upsampled channels
+    const size_t row = (size_t)C_skip * Hs * Ws * sizeof(f16), pitch = (size_t)CT * Hs * Ws * sizeof(f16);
+    if (le == hipSuccess)
+        le = hipMemcpy2DAsync((char*)d_y + (size_t)C_up * Hs * Ws * sizeof(f16), pitch, d_skip, row, row, (size_t)N, hipMemcpyDeviceToDevice, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("upsample + concat: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
 int ltk_f32_to_e4m3(const float* in, size_t n, uint8_t* out) {
     if (!in || !out) return fail(LTK_E_INVALID, "bad arguments");
     for (size_t i = 0; i < n; ++i) out[i] = f32_to_e4m3(in[i]);

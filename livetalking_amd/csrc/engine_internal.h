@@ -18,6 +18,7 @@
 
 #include "../../include/ltk.h"
 #include "conv_mfma.h"
+#include "dw_kernels.h"
 #include "misc_kernels.h"
 #include "musetalk.h"
 #include "nn_kernels.h"
@@ -124,6 +125,30 @@ struct MtAvatar {
         if (d_masks) (void)hipFree(d_masks);
     }
 };
+
+// Ultralight avatar (avatars/ultralight_avatar.py:63-81): the model is per avatar, so the launch program (ultralight.hip) lives with
+// the bank.  boxes = coords.pkl as (x1, y1, x2, y2).
+struct UlProgram;
+void ul_program_delete(UlProgram* p);                 // ultralight.hip
+struct UlAvatar {
+    UlProgram* prog = nullptr;
+    uint8_t* d_face = nullptr;       // [n][168][168][3]
+    uint8_t* d_full = nullptr;       // [n][H][W][3]
+    std::vector<int32_t> boxes;
+    int n = 0, H = 0, W = 0;
+    int device = 0;
+    int id = 0;
+    UlAvatar() = default;
+    UlAvatar(const UlAvatar&) = delete;
+    UlAvatar& operator=(const UlAvatar&) = delete;
+    ~UlAvatar() {
+        (void)hipSetDevice(device);
+        if (d_face) (void)hipFree(d_face);
+        if (d_full) (void)hipFree(d_full);
+        ul_program_delete(prog);
+    }
+};
+constexpr int kUlBufs = 12;           // activation buffers of the Ultralight program (ultralight.hip UlBuf)
 
 // RAII HIP event: error returns between create and destroy do not leak it
 struct Ev {
@@ -273,6 +298,11 @@ struct ltk_engine {
     float* d_mt_feat = nullptr;           // staging: fp32 [max_frames][50][384]
     float* d_mt_lat = nullptr;            // staging for the host-input hook: fp32 [max_frames][8][32][32]
     std::map<int, std::shared_ptr<MtAvatar>> mt_avatars;
+    // ultralight: per-avatar programs over ONE activation arena of ul_frames frames (grown by a register call that asks for more)
+    std::map<int, std::shared_ptr<UlAvatar>> ul_avatars;
+    f16* ul_buf[kUlBufs] = {nullptr};
+    int ul_frames = 0;
+    DevTables* ul_tab = nullptr;          // per-frame bank crop / HuBERT chunk / output pointers of the pass being enqueued
     // pools
     std::vector<Scratch> scratch_free;
     std::vector<hipStream_t> stream_free;
@@ -428,6 +458,12 @@ inline std::shared_ptr<MtAvatar> find_mt_avatar(ltk_engine* e, int id) {
     return it == e->mt_avatars.end() ? nullptr : it->second;
 }
 
+inline std::shared_ptr<UlAvatar> find_ul_avatar(ltk_engine* e, int id) {
+    std::lock_guard<std::mutex> g(e->pool_mu);
+    auto it = e->ul_avatars.find(id);
+    return it == e->ul_avatars.end() ? nullptr : it->second;
+}
+
 // ---------------------------------------------------------------- what crosses the engine's sources
 void build_mel_basis(std::vector<float>* basis, std::vector<int32_t>* lohi, int n_bins = 401, double f_lo = 55.0, double f_hi = 7600.0);   // engine.hip
 int build_program(ltk_engine* e, const ltk_named_tensor* sd, int n);                                        // w2l_program.hip
@@ -438,6 +474,13 @@ int launch_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, const flo
                 bool cached = false, int par = 0, bool have_feats = false);
 int launch_prefetch(ltk_engine* e, int nf, int slot);
 int run_program(ltk_engine* e, MtGraph* prog, int nf);                                                      // mt_engine.hip
+// ultralight.hip.  ul_pass: one pass over frames [0, nf) of the arena, the per-frame tables already in e->ul_tab, under e->mu.
+// bank: the faces table holds uint8 bank crops (else d_img6: float32 NCHW test input); u8_out: the outs table holds the frame
+// destinations; d_pred_f32 (test hook): float32 NCHW sigmoid output.  The product configuration replays from e->prog_graphs.
+int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32);
+double ul_macs_per_frame(const UlAvatar& a);
+void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
+void ul_unload(ltk_engine* e);                         // engine teardown
 int mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat_ptrs, int nf, const OutList64* outs, float* d_image_f32);
 
 }  // namespace ltk

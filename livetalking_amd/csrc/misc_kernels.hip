@@ -2,6 +2,7 @@
 // streaming work: coalesced 8/16-byte accesses, no LDS reuse to exploit except
 // in the mel DFT (frame + twiddle table in LDS).
 #include "misc_kernels.h"
+#include "dw_kernels.h"
 
 #include <algorithm>
 
@@ -461,6 +462,66 @@ void launch_paste(const uint8_t* full, int H, int W, const uint8_t* pred256, int
     const size_t total = (size_t)H * W * 3;
     const size_t words = (total + 3) / 4;
     hipLaunchKernelGGL(paste_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, full, H, W, pred256, y1, y2, x1, x2, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// Ultralight paste-back: avatars/ultralight_avatar.py:173-184.  The source of the resize is the 168x168 bank face with the
+// 160x160 prediction at [4:164, 4:164]; the composite is never materialised, a source pixel is read from whichever holds it.
+// Same cv2.resize restatement as paste_body (identity, exact 2x shrink = 2x2 box, else the 11-bit fixed-point bilinear path).
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int ul_src(const uint8_t* __restrict__ face, const uint8_t* __restrict__ pred, int sy, int sx, int c) {
+    if (sy >= kUlCropOff && sy < kUlCropOff + kUlRes && sx >= kUlCropOff && sx < kUlCropOff + kUlRes)
+        return pred[((sy - kUlCropOff) * kUlRes + (sx - kUlCropOff)) * 3 + c];
+    return face[(sy * kUlFace + sx) * 3 + c];
+}
+
+__global__ __launch_bounds__(256) void ul_paste_kernel(const uint8_t* __restrict__ full, int H, int W, const uint8_t* __restrict__ face,
+                                                        const uint8_t* __restrict__ pred, int x1, int y1, int x2, int y2,
+                                                        uint8_t* __restrict__ out) {
+    const size_t total = (size_t)H * W * 3;
+    const size_t b0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (b0 >= total) return;
+    const int dh = y2 - y1, dw = x2 - x1;
+    const int rowbytes = W * 3;
+    unsigned word = 0;
+    const int nb = (int)min((size_t)4, total - b0);
+    for (int k = 0; k < nb; ++k) {
+        const size_t bi = b0 + k;
+        const int y = (int)(bi / rowbytes);
+        const int rb = (int)(bi - (size_t)y * rowbytes);
+        const int x = rb / 3, c = rb - x * 3;
+        unsigned v;
+        if (y >= y1 && y < y2 && x >= x1 && x < x2) {
+            const int dy = y - y1, dx = x - x1;
+            if (dw == kUlFace && dh == kUlFace) {
+                v = (unsigned)ul_src(face, pred, dy, dx, c);
+            } else if (2 * dw == kUlFace && 2 * dh == kUlFace) {
+                v = (unsigned)(ul_src(face, pred, 2 * dy, 2 * dx, c) + ul_src(face, pred, 2 * dy, 2 * dx + 1, c) +
+                               ul_src(face, pred, 2 * dy + 1, 2 * dx, c) + ul_src(face, pred, 2 * dy + 1, 2 * dx + 1, c) + 2) >> 2;
+            } else {
+                const AxisTap tx = axis_tap(dx, dw, kUlFace, true);
+                const AxisTap ty = axis_tap(dy, dh, kUlFace, false);
+                const int S0 = ul_src(face, pred, ty.s0, tx.s0, c) * tx.a0 + ul_src(face, pred, ty.s0, tx.s1, c) * tx.a1;
+                const int S1 = ul_src(face, pred, ty.s1, tx.s0, c) * tx.a0 + ul_src(face, pred, ty.s1, tx.s1, c) * tx.a1;
+                const int o = (((ty.a0 * (S0 >> 4)) >> 16) + ((ty.a1 * (S1 >> 4)) >> 16) + 2) >> 2;
+                v = (unsigned)min(max(o, 0), 255);
+            }
+        } else {
+            v = full[bi];
+        }
+        word |= v << (8 * k);
+    }
+    if (nb == 4 && (reinterpret_cast<uintptr_t>(out + b0) & 3) == 0) {
+        *reinterpret_cast<unsigned*>(out + b0) = word;
+    } else {
+        for (int k = 0; k < nb; ++k) out[b0 + k] = (uint8_t)(word >> (8 * k));
+    }
+}
+
+void launch_ul_paste(const uint8_t* full, int H, int W, const uint8_t* face168, const uint8_t* pred160, int x1, int y1, int x2, int y2,
+                     uint8_t* out, hipStream_t s) {
+    const size_t words = ((size_t)H * W * 3 + 3) / 4;
+    hipLaunchKernelGGL(ul_paste_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, full, H, W, face168, pred160, x1, y1, x2, y2, out);
 }
 
 }  // namespace ltk

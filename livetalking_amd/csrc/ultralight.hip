@@ -1,0 +1,480 @@
+// The Ultralight avatar (avatars/ultralight/unet.py Model(6, 'hubert'), avatars/ultralight_avatar.py): a MobileNet-style U-Net at
+// 160x160 as a static launch program over a device activation arena.  Every inverted residual (unet.py:7-36) is three launches -
+// 1x1 expand on conv3's 1x1 path, depthwise 3x3 and (where the block has one) the residual add in the 1x1 project's epilogue -
+// eval-mode BatchNorm folded into scale / shift at register time; torch.cat is a channel-block range of a shared buffer, the
+// bilinear upsample writes straight into it.  The model is per avatar (ultralight_avatar.py:69-70), so the program is built by
+// ltk_ultralight_avatar_register and owned by the avatar; the activation arena and the pointer tables belong to the engine.
+// Compiled as part of engine.hip (included at its end), together with the kernels in dw_kernels.hip.
+#include "engine_internal.h"
+#include "dw_kernels.hip"
+
+namespace ltk {
+
+enum UlBuf { U_FEAT = 0, U_X0, U_E1, U_E2, U_P, U_Q, U_CAT1, U_CAT2, U_CAT3, U_CAT4, U_FCAT, U_COUNT };
+static_assert(U_COUNT <= kUlBufs, "engine_internal.h kUlBufs");
+
+enum UlOpType { UL_CONV = 0, UL_DW, UL_UP, UL_IN, UL_FEAT, UL_HEAD };
+
+struct UlOp {
+    int type = UL_CONV;
+    std::string name;               // state_dict prefix of the conv (tap name); "<block>.up" for an upsample
+    ConvPlan plan;                  // UL_CONV
+    float* d_dw = nullptr;          // UL_DW: [C/16][9][16] weights, then scale [C], shift [C]
+    int C = 0, Creal = 0;           // channels the op writes (layout) / of the reference's tensor
+    int stride = 1, relu = 0;
+    int in_buf = 0, in_ld = 0, in_coff = 0, H = 0, W = 0;
+    int out_buf = 0, out_ld = 0, out_coff = 0, Ho = 0, Wo = 0;
+    int res_buf = -1, res_ld = 0, res_coff = 0;
+    double macs = 0;                // per frame
+};
+
+struct UlProgram {
+    std::vector<UlOp> ops;
+    UlInW inw;
+    UlHeadW headw;
+    size_t buf_halfs[U_COUNT] = {0};      // per frame
+    double macs_per_frame = 0;
+};
+
+void ul_program_delete(UlProgram* p) {
+    if (!p) return;
+    for (UlOp& op : p->ops) {
+        conv_plan_destroy(&op.plan);
+        if (op.d_dw) (void)hipFree(op.d_dw);
+    }
+    delete p;
+}
+
+double ul_macs_per_frame(const UlAvatar& a) { return a.prog ? a.prog->macs_per_frame : 0.0; }
+
+namespace {
+
+const float kUlBnEps = 1e-5f;     // nn.BatchNorm2d default (unet.py:17,26,29)
+
+struct Tn { int buf, ld, coff, C, H, W; };     // a tensor = channels [coff, coff + C) of a buffer of ld channels
+
+struct Builder {
+    const ltk_named_tensor* sd;
+    int n;
+    UlProgram* p;
+
+    const float* find(const std::string& name, size_t expect) const {
+        for (int i = 0; i < n; ++i)
+            if (sd[i].name && name == sd[i].name) {
+                if (!sd[i].data) return nullptr;
+                size_t cnt = 1;
+                for (int d = 0; d < sd[i].ndim; ++d) cnt *= (size_t)sd[i].shape[d];
+                return cnt == expect ? sd[i].data : nullptr;
+            }
+        return nullptr;
+    }
+    // BatchNorm2d eval folded: y = (x + bias - mean) / sqrt(var + eps) * gamma + beta
+    int fold_bn(const std::string& bn, int C, const float* bias, std::vector<float>* sc, std::vector<float>* sf) const {
+        const float* g = find(bn + ".weight", C);
+        const float* b = find(bn + ".bias", C);
+        const float* m = find(bn + ".running_mean", C);
+        const float* v = find(bn + ".running_var", C);
+        if (!g || !b || !m || !v) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) the BatchNorm tensors " + bn + ".*");
+        sc->resize(C); sf->resize(C);
+        for (int c = 0; c < C; ++c) {
+            const float s = g[c] / sqrtf(v[c] + kUlBnEps);
+            (*sc)[c] = s;
+            (*sf)[c] = ((bias ? bias[c] : 0.f) - m[c]) * s + b[c];
+        }
+        return 0;
+    }
+    void note(const UlOp& op) {
+        size_t& h = p->buf_halfs[op.out_buf];
+        h = std::max(h, (size_t)op.out_ld * op.Ho * op.Wo);
+        p->macs_per_frame += op.macs;
+    }
+    // dense conv (1x1 or 3x3) + folded BN (+ conv bias) + optional ReLU / residual
+    int conv(const std::string& wname, const std::string& bn, bool has_bias, const Tn& in, int cout, int k, int stride, int pad, int relu,
+             const Tn* res, int out_buf, int out_ld, int out_coff, Tn* out) {
+        const float* w = find(wname + ".weight", (size_t)cout * in.C * k * k);
+        const float* bias = has_bias ? find(wname + ".bias", cout) : nullptr;
+        if (!w || (has_bias && !bias)) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + wname + ".weight / .bias");
+        std::vector<float> sc, sf;
+        int rc = fold_bn(bn, cout, bias, &sc, &sf);
+        if (rc) return rc;
+        p->ops.emplace_back();
+        UlOp& op = p->ops.back();
+        op.type = UL_CONV; op.name = wname;
+        std::string err;
+        rc = conv_plan_create(&op.plan, w, in.C, cout, k, k, stride, stride, pad, pad, false, 0, sc.data(), sf.data(), &err);
+        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, wname + ": " + err);
+        op.C = op.Creal = cout; op.stride = stride; op.relu = relu;
+        op.in_buf = in.buf; op.in_ld = in.ld; op.in_coff = in.coff; op.H = in.H; op.W = in.W;
+        op.plan.out_dims(in.H, in.W, &op.Ho, &op.Wo);
+        op.out_buf = out_buf; op.out_ld = out_ld; op.out_coff = out_coff;
+        if (res) { op.res_buf = res->buf; op.res_ld = res->ld; op.res_coff = res->coff; }
+        op.macs = (double)in.C * cout * k * k * op.Ho * op.Wo;
+        note(op);
+        *out = Tn{out_buf, out_ld, out_coff, cout, op.Ho, op.Wo};
+        return 0;
+    }
+    // depthwise 3x3 + BN + ReLU over `Cpad` layout channels of which the first C are the reference's (the rest: zero weights)
+    int dw(const std::string& wname, const std::string& bn, const Tn& in, int C, int stride, int out_buf, Tn* out) {
+        const int Cpad = (C + 15) / 16 * 16;
+        const float* w = find(wname + ".weight", (size_t)C * 9);
+        if (!w) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + wname + ".weight");
+        std::vector<float> sc, sf;
+        int rc = fold_bn(bn, C, nullptr, &sc, &sf);
+        if (rc) return rc;
+        std::vector<float> h((size_t)Cpad * 11, 0.f);
+        for (int c = 0; c < C; ++c) {
+            for (int t = 0; t < 9; ++t) h[((size_t)(c >> 4) * 9 + t) * 16 + (c & 15)] = w[(size_t)c * 9 + t];
+            h[(size_t)Cpad * 9 + c] = sc[c];
+            h[(size_t)Cpad * 10 + c] = sf[c];
+        }
+        p->ops.emplace_back();
+        UlOp& op = p->ops.back();
+        op.type = UL_DW; op.name = wname;
+        CHK(hipMalloc((void**)&op.d_dw, h.size() * sizeof(float)));
+        CHK(hipMemcpy(op.d_dw, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        op.C = Cpad; op.Creal = C; op.stride = stride; op.relu = 1;
+        op.in_buf = in.buf; op.in_ld = in.ld; op.in_coff = in.coff; op.H = in.H; op.W = in.W;
+        op.Ho = (in.H - 1) / stride + 1; op.Wo = (in.W - 1) / stride + 1;
+        op.out_buf = out_buf; op.out_ld = Cpad; op.out_coff = 0;
+        op.macs = 9.0 * C * op.Ho * op.Wo;
+        note(op);
+        *out = Tn{out_buf, Cpad, 0, C, op.Ho, op.Wo};
+        return 0;
+    }
+    // InvertedResidual(inp, oup, stride, use_res_connect, expand_ratio = 2), unet.py:7-36: `pre`.conv.{0,1} expand + BN + ReLU,
+    // .conv.{3,4} depthwise + BN + ReLU, .conv.{6,7} project + BN (linear), + x where the block has the connection
+    int ir(const std::string& pre, const Tn& in, int cout, int stride, bool res, int out_buf, int out_ld, int out_coff, Tn* out) {
+        const int mid = in.C * 2;
+        Tn e1, e2;
+        int rc;
+        if (in.C == 6) {        // inc: the expand conv reads the bank crop itself (UL_IN); 12 channels live in one 16-channel block
+            const float* w = find(pre + ".conv.0.weight", 72);
+            if (!w) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + pre + ".conv.0.weight");
+            std::vector<float> sc, sf;
+            if ((rc = fold_bn(pre + ".conv.1", 12, nullptr, &sc, &sf))) return rc;
+            memcpy(p->inw.w, w, 72 * sizeof(float));
+            memcpy(p->inw.scale, sc.data(), 12 * sizeof(float));
+            memcpy(p->inw.shift, sf.data(), 12 * sizeof(float));
+            p->ops.emplace_back();
+            UlOp& op = p->ops.back();
+            op.type = UL_IN; op.name = pre + ".conv.0"; op.in_buf = -1;
+            op.C = 16; op.Creal = 12; op.relu = 1; op.H = op.Ho = in.H; op.W = op.Wo = in.W;
+            op.out_buf = U_X0; op.out_ld = 16; op.out_coff = 0;
+            op.macs = 72.0 * in.H * in.W;
+            note(op);
+            e1 = Tn{U_X0, 16, 0, 12, in.H, in.W};
+        } else {
+            if ((rc = conv(pre + ".conv.0", pre + ".conv.1", false, in, mid, 1, 1, 0, 1, nullptr, U_E1, mid, 0, &e1))) return rc;
+        }
+        if ((rc = dw(pre + ".conv.3", pre + ".conv.4", e1, mid, stride, U_E2, &e2))) return rc;
+        return conv(pre + ".conv.6", pre + ".conv.7", false, e2, cout, 1, 1, 0, 0, res ? &in : nullptr, out_buf, out_ld, out_coff, out);
+    }
+    // DoubleConvDW (unet.py:38-49): IR(in -> out, stride), IR(out -> out, 1, residual); the result lands at (out_buf, out_ld, out_coff)
+    int dconv(const std::string& pre, const Tn& in, int cout, int stride, int out_buf, int out_ld, int out_coff, Tn* out) {
+        const int tmp = (in.buf == U_P || out_buf == U_P) ? U_Q : U_P;
+        if (tmp == in.buf || tmp == out_buf) return fail(LTK_E_INVALID, "ultralight program: no free temporary");
+        Tn t;
+        const int rc = ir(pre + ".double_conv.0", in, cout, stride, false, tmp, cout, 0, &t);
+        if (rc) return rc;
+        return ir(pre + ".double_conv.1", t, cout, 1, true, out_buf, out_ld, out_coff, out);
+    }
+    int up(const std::string& name, const Tn& in, int out_buf, int out_ld) {
+        p->ops.emplace_back();
+        UlOp& op = p->ops.back();
+        op.type = UL_UP; op.name = name;
+        op.C = op.Creal = in.C;
+        op.in_buf = in.buf; op.in_ld = in.ld; op.in_coff = in.coff; op.H = in.H; op.W = in.W;
+        op.Ho = 2 * in.H; op.Wo = 2 * in.W;
+        op.out_buf = out_buf; op.out_ld = out_ld; op.out_coff = 0;
+        note(op);
+        return 0;
+    }
+};
+
+// unet.py:168-215 Model.forward
+int build_ul_program(UlProgram* p, const ltk_named_tensor* sd, int n) {
+    Builder b{sd, n, p};
+    int rc;
+    const int R = kUlRes;
+    // ---- face path (unet.py:200-204): every level's output is the skip half of the matching Up's concat buffer
+    Tn x1, x2, x3, x4, x5;
+    if ((rc = b.ir("inc.inconv.0", Tn{-1, 0, 0, 6, R, R}, 32, 1, false, U_CAT4, 64, 32, &x1))) return rc;
+    if ((rc = b.dconv("down1.maxpool_conv.0", x1, 64, 2, U_CAT3, 128, 64, &x2))) return rc;
+    if ((rc = b.dconv("down2.maxpool_conv.0", x2, 128, 2, U_CAT2, 256, 128, &x3))) return rc;
+    if ((rc = b.dconv("down3.maxpool_conv.0", x3, 256, 2, U_CAT1, 512, 256, &x4))) return rc;
+    if ((rc = b.dconv("down4.maxpool_conv.0", x4, 512, 2, U_FCAT, 1024, 0, &x5))) return rc;
+    // ---- audio tower (unet.py:132-166 AudioConvHubert): (16, 32, 32) -> 512 x 10 x 10, the second half of the fuse concat
+    {
+        p->ops.emplace_back();
+        UlOp& op = p->ops.back();
+        op.type = UL_FEAT; op.name = "audio_feat"; op.in_buf = -1;
+        op.C = op.Creal = 16; op.H = op.Ho = 32; op.W = op.Wo = 32;
+        op.out_buf = U_FEAT; op.out_ld = 16; op.out_coff = 0;
+        b.note(op);
+    }
+    Tn a{U_FEAT, 16, 0, 16, 32, 32}, t;
+    if ((rc = b.ir("audio_model.conv1", a, 64, 1, false, U_P, 64, 0, &t))) return rc;
+    if ((rc = b.ir("audio_model.conv2", t, 128, 1, false, U_Q, 128, 0, &a))) return rc;
+    if ((rc = b.conv("audio_model.conv3", "audio_model.bn3", true, a, 256, 3, 2, 1, 1, nullptr, U_P, 256, 0, &t))) return rc;
+    if ((rc = b.ir("audio_model.conv4", t, 256, 1, true, U_Q, 256, 0, &a))) return rc;
+    if ((rc = b.conv("audio_model.conv5", "audio_model.bn5", true, a, 512, 3, 2, 3, 1, nullptr, U_P, 512, 0, &t))) return rc;
+    if (t.H != 10 || t.W != 10) return fail(LTK_E_INVALID, "ultralight program: audio tower geometry");
+    if ((rc = b.ir("audio_model.conv6", t, 512, 1, true, U_Q, 512, 0, &a))) return rc;
+    if ((rc = b.ir("audio_model.conv7", a, 512, 1, true, U_FCAT, 1024, 512, &t))) return rc;
+    // ---- fuse (unet.py:207-208)
+    Tn f{U_FCAT, 1024, 0, 1024, 10, 10}, g;
+    if ((rc = b.dconv("fuse_conv.0", f, 512, 1, U_Q, 512, 0, &g))) return rc;
+    if ((rc = b.dconv("fuse_conv.1", g, 256, 1, U_Q, 256, 0, &f))) return rc;
+    // ---- decoder (unet.py:72-87, 209-212): cat([up(x), skip]); F.pad is a no-op at 160 x 160
+    const struct { const char* name; int cat, cup, cout; } ups[4] = {{"up1", U_CAT1, 256, 128}, {"up2", U_CAT2, 128, 64}, {"up3", U_CAT3, 64, 32}, {"up4", U_CAT4, 32, 32}};
+    for (int k = 0; k < 4; ++k) {
+        if (f.C != ups[k].cup) return fail(LTK_E_INVALID, "ultralight program: decoder geometry");
+        if ((rc = b.up(std::string(ups[k].name) + ".up", f, ups[k].cat, 2 * ups[k].cup))) return rc;
+        const Tn c{ups[k].cat, 2 * ups[k].cup, 0, 2 * ups[k].cup, 2 * f.H, 2 * f.W};
+        if ((rc = b.dconv(std::string(ups[k].name) + ".conv", c, ups[k].cout, 1, U_Q, ups[k].cout, 0, &f))) return rc;
+    }
+    if (f.H != R || f.C != 32) return fail(LTK_E_INVALID, "ultralight program: output geometry");
+    // ---- outc + sigmoid (unet.py:213-214)
+    const float* hw = b.find("outc.conv.weight", 96);
+    const float* hb = b.find("outc.conv.bias", 3);
+    if (!hw || !hb) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) outc.conv.{weight,bias}");
+    memcpy(p->headw.w, hw, 96 * sizeof(float));
+    memcpy(p->headw.b, hb, 3 * sizeof(float));
+    p->ops.emplace_back();
+    UlOp& op = p->ops.back();
+    op.type = UL_HEAD; op.name = "outc.conv";
+    op.C = op.Creal = 3; op.in_buf = f.buf; op.in_ld = 32; op.H = op.Ho = R; op.W = op.Wo = R;
+    op.out_buf = f.buf;       // (writes the caller's frames, no arena buffer)
+    op.macs = 96.0 * R * R;
+    p->macs_per_frame += op.macs;
+    return 0;
+}
+
+// the launches of one pass over frames [0, nf); tables in e->ul_tab
+int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32) {
+    std::string err;
+    for (UlOp& op : p.ops) {
+        const f16* x = op.in_buf >= 0 ? e->ul_buf[op.in_buf] : nullptr;
+        f16* y = e->ul_buf[op.out_buf];
+        switch (op.type) {
+        case UL_IN:
+            launch_ul_in(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, p.inw, y, s);
+            break;
+        case UL_FEAT:
+            launch_ul_pack_feat(&e->ul_tab->mels, nf, y, s);
+            break;
+        case UL_DW:
+            launch_dwconv3x3(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, op.stride, op.d_dw, op.d_dw + (size_t)op.C * 9,
+                             op.d_dw + (size_t)op.C * 10, op.relu, y, op.out_ld / 16, op.out_coff / 16, s);
+            break;
+        case UL_UP:
+            launch_upsample2x(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, y, op.out_ld / 16, op.out_coff / 16, s);
+            break;
+        case UL_HEAD:
+            launch_ul_head(x, nf, p.headw, u8_out ? &e->ul_tab->outs : nullptr, d_pred_f32, s);
+            break;
+        default: {
+            ConvIO io;
+            io.x = x; io.N = nf; io.H = op.H; io.W = op.W; io.x_ld = op.in_ld; io.x_coff = op.in_coff;
+            io.y = y; io.y_ld = op.out_ld; io.y_coff = op.out_coff;
+            io.res = op.res_buf >= 0 ? e->ul_buf[op.res_buf] : nullptr; io.res_ld = op.res_ld; io.res_coff = op.res_coff;
+            io.relu = op.relu;
+            io.partial = e->d_partial; io.partial_cap = e->partial_cap;
+            const int rc = conv_launch(op.plan, io, s, &err);
+            if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, op.name + ": " + err);
+        }
+        }
+        CHK(hipGetLastError());
+        if (e->capture) {           // ltk_debug_capture: every op's output as NCHW float32 under its name
+            std::vector<float>& t = e->taps[op.name];
+            t.resize((size_t)nf * op.Creal * op.Ho * op.Wo);
+            if (op.type == UL_HEAD) {
+                if (!d_pred_f32) { e->taps.erase(op.name); continue; }
+                CHK(hipStreamSynchronize(s));
+                CHK(hipMemcpy(t.data(), d_pred_f32, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+            } else {
+                DevBuf tmp;
+                CHK(hipMalloc(&tmp.p, t.size() * sizeof(float)));
+                launch_nhwc_to_nchw_f32(y, nf, op.Ho, op.Wo, op.out_ld, op.out_coff, op.Creal, (float*)tmp.p, s);
+                CHK(hipStreamSynchronize(s));
+                CHK(hipMemcpy(t.data(), tmp.p, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+            }
+            e->tap_shape[op.name] = {nf, op.Creal, op.Ho, op.Wo};
+        }
+    }
+    return 0;
+}
+
+// key of a captured Ultralight pass in e->prog_graphs: avatar ids are never reused (a program's address could be)
+const void* ul_graph_token(int avatar_id) { return reinterpret_cast<const void*>((uintptr_t)avatar_id); }
+
+// the engine's arena serves every Ultralight avatar (one architecture): grown, never shrunk.  Under e->mu.
+int ul_arena_reserve(ltk_engine* e, const UlProgram& p, int frames) {
+    if (!e->ul_tab) {
+        if (hipMalloc((void**)&e->ul_tab, sizeof(DevTables)) != hipSuccess) return fail(LTK_E_NOMEM, "pointer table allocation failed");
+        CHK(hipMemset(e->ul_tab, 0, sizeof(DevTables)));
+    }
+    if (frames <= e->ul_frames) return 0;
+    CHK(hipStreamSynchronize(e->compute));
+    // captured passes carry the old buffers' addresses
+    std::vector<int> ids;
+    {
+        std::lock_guard<std::mutex> g(e->pool_mu);
+        for (auto& kv : e->ul_avatars) ids.push_back(kv.first);
+    }
+    for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
+        bool ul = false;
+        for (int id : ids) ul = ul || it->first.first == ul_graph_token(id);
+        if (ul) { if (it->second.exec) (void)hipGraphExecDestroy(it->second.exec); it = e->prog_graphs.graphs.erase(it); }
+        else ++it;
+    }
+    for (int i = 0; i < U_COUNT; ++i) {
+        if (e->ul_buf[i]) { (void)hipFree(e->ul_buf[i]); e->ul_buf[i] = nullptr; }
+    }
+    e->ul_frames = 0;
+    for (int i = 0; i < U_COUNT; ++i) {
+        if (!p.buf_halfs[i]) continue;
+        const size_t bytes = p.buf_halfs[i] * (size_t)frames * sizeof(f16) + 4096;
+        if (hipMalloc((void**)&e->ul_buf[i], bytes) != hipSuccess) { (void)hipGetLastError(); return fail(LTK_E_NOMEM, "ultralight activation arena allocation failed"); }
+        CHK(hipMemset(e->ul_buf[i], 0, bytes));
+    }
+    e->ul_frames = frames;
+    return 0;
+}
+
+}  // namespace
+
+int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32) {
+    if (nf <= 0 || nf > e->ul_frames || nf > kPackMaxFrames) return fail(LTK_E_INVALID, "ultralight pass: frame count outside the arena");
+    hipStream_t s = e->compute;
+    auto enq = [&]() -> int { return ul_enqueue(e, *a.prog, nf, s, bank, d_img6, u8_out, d_pred_f32); };
+    // the product configuration (bank crops in, uint8 frames out) has no per-call arguments: captured and replayed (knob GRAPH)
+    if (knob(K_GRAPH) && bank && u8_out && !d_pred_f32 && !e->capture)
+        return e->prog_graphs.run(e, std::make_pair(ul_graph_token(a.id), nf), s, "ultralight pass", nf, enq);
+    return enq();
+}
+
+void ul_drop_graphs(ltk_engine* e, int avatar_id) {
+    bool synced = false;
+    for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
+        if (it->first.first != ul_graph_token(avatar_id)) { ++it; continue; }
+        if (it->second.exec) {
+            if (!synced) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->compute); synced = true; }
+            (void)hipGraphExecDestroy(it->second.exec);
+        }
+        it = e->prog_graphs.graphs.erase(it);
+    }
+}
+
+void ul_unload(ltk_engine* e) {
+    e->ul_avatars.clear();
+    for (int i = 0; i < kUlBufs; ++i)
+        if (e->ul_buf[i]) { (void)hipFree(e->ul_buf[i]); e->ul_buf[i] = nullptr; }
+    if (e->ul_tab) { (void)hipFree(e->ul_tab); e->ul_tab = nullptr; }
+    e->ul_frames = 0;
+}
+
+}  // namespace ltk
+
+extern "C" {
+
+int ltk_ultralight_avatar_register(ltk_engine* e, const ltk_named_tensor* sd, int n_tensors, const uint8_t* face_bank, const uint8_t* full_bank,
+                                   const int32_t* coords, int n, int H, int W, int max_frames, int* avatar_id) {
+    if (!e || !sd || n_tensors <= 0 || !face_bank || !full_bank || !coords || !avatar_id || n <= 0 || H <= 0 || W <= 0)
+        return fail(LTK_E_INVALID, "bad arguments");
+    if (max_frames < 1 || max_frames > kPackMaxFrames) return fail(LTK_E_INVALID, "max_frames must be in [1, 256]");
+    for (int i = 0; i < n_tensors; ++i)
+        if (!sd[i].name || !sd[i].data || sd[i].ndim < 0 || (sd[i].ndim > 0 && !sd[i].shape)) return fail(LTK_E_INVALID, "state_dict entry without a name, data or shape");
+    for (int i = 0; i < n; ++i) {
+        const int32_t* c = coords + 4 * i;      // (x1, y1, x2, y2), ultralight_avatar.py:176
+        if (c[0] < 0 || c[1] < 0 || c[2] > W || c[3] > H || c[2] <= c[0] || c[3] <= c[1]) return fail(LTK_E_INVALID, "coords box outside the frame");
+    }
+    CHK(enter_device(e->device));
+    auto ap = std::make_shared<UlAvatar>();
+    UlAvatar& a = *ap;
+    a.device = e->device;
+    a.n = n; a.H = H; a.W = W;
+    a.boxes.assign(coords, coords + 4 * (size_t)n);
+    a.prog = new UlProgram();
+    int rc = build_ul_program(a.prog, sd, n_tensors);
+    if (rc) return rc;                      // (the avatar's destructor frees the half-built program)
+    const size_t fb = (size_t)n * kUlFace * kUlFace * 3, ub = (size_t)n * H * W * 3;
+    CHK(hipMalloc((void**)&a.d_face, fb));
+    CHK(hipMalloc((void**)&a.d_full, ub));
+    CHK(hipMemcpy(a.d_face, face_bank, fb, hipMemcpyHostToDevice));
+    CHK(hipMemcpy(a.d_full, full_bank, ub, hipMemcpyHostToDevice));
+    {
+        std::lock_guard<std::mutex> g(e->mu);
+        if ((rc = ul_arena_reserve(e, *a.prog, max_frames))) return rc;
+    }
+    std::lock_guard<std::mutex> g(e->pool_mu);
+    a.id = e->next_avatar++;
+    e->ul_avatars[a.id] = ap;
+    *avatar_id = a.id;
+    return LTK_OK;
+}
+
+int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* stream) {
+    if (!e || !reqs || nreq <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    std::vector<std::shared_ptr<UlAvatar>> hold;          // the banks and programs stay alive until this call has synchronised
+    for (int r = 0; r < nreq; ++r) {
+        if (reqs[r].batch <= 0 || reqs[r].index < 0 || !reqs[r].d_feat || !reqs[r].d_pred) return fail(LTK_E_INVALID, "bad request");
+        hold.push_back(find_ul_avatar(e, reqs[r].avatar));
+        if (!hold.back()) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    }
+    CHK(enter_device(e->device));
+    return infer_call(e, stream, [&]() -> int {
+        const int cap = std::min(e->ul_frames, kPackMaxFrames);
+        if (cap <= 0) return fail(LTK_E_STATE, "no Ultralight arena");
+        // every request runs its own avatar's program (the weights are per avatar), in arena-sized launches, back to back on the
+        // compute stream; the tables of a launch are uploaded in front of it in stream order
+        for (int r = 0; r < nreq; ++r) {
+            UlAvatar& a = *hold[r];
+            for (int f0 = 0; f0 < reqs[r].batch; f0 += cap) {
+                const int nf = std::min(cap, reqs[r].batch - f0);
+                FacePtrs fp; MelPtrs mp; OutPtrs op;
+                for (int i = 0; i < nf; ++i) {
+                    const int idx = mirror_index(a.n, reqs[r].index + f0 + i);      // ultralight_avatar.py:150
+                    fp.p[i] = a.d_face + (size_t)idx * kUlFace * kUlFace * 3;
+                    mp.p[i] = (const float*)reqs[r].d_feat + (size_t)(f0 + i) * 16 * 1024;
+                    op.p[i] = (uint8_t*)reqs[r].d_pred + (size_t)(f0 + i) * kUlRes * kUlRes * 3;
+                }
+                launch_upload_tables(&fp, &mp, &op, nf, e->ul_tab, e->compute);
+                if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "pointer table upload failed");
+                const int rc = ul_pass(e, a, nf, true, nullptr, true, nullptr);
+                if (rc) return rc;
+            }
+        }
+        return 0;
+    });
+}
+
+int ltk_ultralight_paste_back(ltk_engine* e, int avatar_id, int idx, const void* d_pred, void* out, int out_is_device, void* stream) {
+    if (!e || !d_pred || !out) return fail(LTK_E_INVALID, "bad arguments");
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
+    if (!ap) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    const UlAvatar& a = *ap;
+    if (idx < 0 || idx >= a.n) return fail(LTK_E_INVALID, "frame index outside the bank");
+    CHK(enter_device(e->device));
+    const int32_t* c = a.boxes.data() + 4 * (size_t)idx;
+    const size_t bytes = (size_t)a.H * a.W * 3;
+    StreamLease sl(e, stream);
+    const uint8_t* full = a.d_full + (size_t)idx * bytes;
+    const uint8_t* face = a.d_face + (size_t)idx * kUlFace * kUlFace * 3;
+    if (out_is_device) {
+        launch_ul_paste(full, a.H, a.W, face, (const uint8_t*)d_pred, c[0], c[1], c[2], c[3], (uint8_t*)out, sl.s);
+        CHK(hipGetLastError());
+        CHK(hipStreamSynchronize(sl.s));
+        return LTK_OK;
+    }
+    ScratchLease sc(e, bytes);
+    if (!sc.s.d) return fail(LTK_E_NOMEM, "scratch allocation failed");
+    launch_ul_paste(full, a.H, a.W, face, (const uint8_t*)d_pred, c[0], c[1], c[2], c[3], (uint8_t*)sc.s.d, sl.s);
+    const hipError_t pe = hipGetLastError();
+    const hipError_t ce = pe == hipSuccess ? hipMemcpyAsync(out, sc.s.d, bytes, hipMemcpyDeviceToHost, sl.s) : pe;
+    const hipError_t se = hipStreamSynchronize(sl.s);        // before the scratch goes back to the pool
+    if (ce != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight_paste_back: ") + hipGetErrorString(ce != hipSuccess ? ce : se));
+    return LTK_OK;
+}
+
+}  // extern "C"

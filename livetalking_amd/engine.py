@@ -14,7 +14,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import LtkError, MtReq, NamedTensor, W2lReq  # noqa: F401
+from ._lib import LtkError, MtReq, NamedTensor, UlReq, W2lReq  # noqa: F401
 
 
 def _as_f32(a) -> np.ndarray:
@@ -202,6 +202,70 @@ class Engine:
     def paste_blend(self, avatar_id: int, idx: int, d_pred_ptr: int, out: np.ndarray, stream: int = 0):
         _lib.check(self._lib.ltk_paste_blend(self._h, int(avatar_id), int(idx), C.c_void_p(d_pred_ptr), out.ctypes.data, 0,
                                              C.c_void_p(stream)))
+
+    # ------------------------------------------------------------------ ultralight
+    def register_ultralight_avatar(self, state_dict: Dict[str, object], face_list: Sequence[np.ndarray], frame_list: Sequence[np.ndarray],
+                                   coord_list, max_frames: int = 16) -> int:
+        """(model, frame_list_cycle, face_list_cycle, coord_list_cycle) as ultralight_avatar.load_avatar returns them
+        (ultralight_avatar.py:63-81): `state_dict` = torch.load(ultralight.pth) (tensors or arrays), 168x168 BGR faces, full frames,
+        (x1, y1, x2, y2) boxes.  The model is per avatar, so it is registered with the bank."""
+        faces = np.ascontiguousarray(np.stack(face_list), dtype=np.uint8)
+        fulls = getattr(frame_list, "packed", None)
+        fulls = np.ascontiguousarray(np.stack(frame_list) if fulls is None else fulls, dtype=np.uint8)
+        coords = np.ascontiguousarray(np.asarray(coord_list, dtype=np.int32).reshape(-1, 4))
+        n = faces.shape[0]
+        if faces.shape[1:] != (168, 168, 3) or fulls.ndim != 4 or fulls.shape[0] != n or coords.shape[0] != n or fulls.shape[3] != 3:
+            raise ValueError("ultralight avatar bank shapes: faces (n,168,168,3), frames (n,H,W,3), coords (n,4)")
+        arr, nt, keep = self._named_tensors(state_dict)
+        aid = C.c_int()
+        _lib.check(self._lib.ltk_ultralight_avatar_register(self._h, arr, nt, faces.ctypes.data, fulls.ctypes.data, coords.ctypes.data,
+                                                            n, fulls.shape[1], fulls.shape[2], int(max_frames), C.byref(aid)))
+        del keep
+        return aid.value
+
+    def ultralight_infer(self, reqs: Sequence[tuple], stream: int = 0):
+        """reqs: (avatar_id, index, batch, d_feat_ptr fp32 [batch][16][32][32], d_pred_ptr uint8 [batch][160][160][3])."""
+        arr = (UlReq * len(reqs))()
+        for i, (aid, index, batch, feat_ptr, pred_ptr) in enumerate(reqs):
+            arr[i].avatar = int(aid); arr[i].index = int(index); arr[i].batch = int(batch)
+            arr[i].d_feat = C.c_void_p(feat_ptr); arr[i].d_pred = C.c_void_p(pred_ptr)
+        _lib.check(self._lib.ltk_ultralight_infer(self._h, arr, len(reqs), C.c_void_p(stream)))
+
+    def ultralight_paste_back(self, avatar_id: int, idx: int, d_pred_ptr: int, out: np.ndarray, stream: int = 0):
+        """out: C-contiguous uint8 (H,W,3) host array, filled in place (ultralight_avatar.py:173-184)."""
+        _lib.check(self._lib.ltk_ultralight_paste_back(self._h, int(avatar_id), int(idx), C.c_void_p(d_pred_ptr), out.ctypes.data, 0,
+                                                       C.c_void_p(stream)))
+
+    def ultralight_forward_host(self, avatar_id: int, img6: np.ndarray, feat: np.ndarray) -> np.ndarray:
+        """Model.forward on explicit inputs: img6 (B,6,160,160) in [0,1], feat (B,16,32,32) or (B,16,1024) -> sigmoid (B,3,160,160)."""
+        img6 = np.ascontiguousarray(img6, dtype=np.float32)
+        B = img6.shape[0]
+        feat = np.ascontiguousarray(feat, dtype=np.float32).reshape(B, 16, 32, 32)
+        assert img6.shape[1:] == (6, 160, 160)
+        pred = np.empty((B, 3, 160, 160), dtype=np.float32)
+        _lib.check(self._lib.ltk_ultralight_forward_host(self._h, int(avatar_id), img6.ctypes.data, feat.ctypes.data, B, pred.ctypes.data))
+        return pred
+
+    def ultralight_time(self, avatar_id: int, frames: int, iters: int):
+        ms = C.c_float()
+        macs = C.c_double()
+        _lib.check(self._lib.ltk_ultralight_time(self._h, int(avatar_id), int(frames), int(iters), C.byref(ms), C.byref(macs)))
+        return ms.value, macs.value
+
+    def dwconv3x3_f16(self, d_x_ptr: int, N, H, W, C_, weight: np.ndarray, stride: int = 1, scale=None, shift=None, relu: bool = True,
+                      d_y_ptr: int = 0):
+        """Depthwise 3x3 pad-1 conv on a CB16 tensor (include/ltk.h: ltk_dwconv3x3_f16); weight (C,1,3,3)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32) if scale is not None else None
+        sf = np.ascontiguousarray(shift, dtype=np.float32) if shift is not None else None
+        _lib.check(self._lib.ltk_dwconv3x3_f16(self._h, C.c_void_p(d_x_ptr), N, H, W, C_, w.ctypes.data, int(stride),
+                                               sc.ctypes.data if sc is not None else None, sf.ctypes.data if sf is not None else None,
+                                               1 if relu else 0, C.c_void_p(d_y_ptr)))
+
+    def upsample2x_cat_f16(self, d_x_ptr: int, N, h, w, C_up, d_skip_ptr: int, Hs, Ws, C_skip, d_y_ptr: int):
+        """cat([bilinear x2 (align_corners) of x, skip]) on CB16 tensors (include/ltk.h: ltk_upsample2x_cat_f16)."""
+        _lib.check(self._lib.ltk_upsample2x_cat_f16(self._h, C.c_void_p(d_x_ptr), N, h, w, C_up, C.c_void_p(d_skip_ptr), Hs, Ws, C_skip,
+                                                    C.c_void_p(d_y_ptr)))
 
     # ---- frame egress (include/ltk.h: ltk_egress_*)
     def egress_open(self, H: int, W: int) -> int:

@@ -4,7 +4,8 @@
     cd /path/to/LiveTalking && python /path/to/this/repo/scripts/run_amd.py [app.py arguments ...]
 
 It makes the module names app.py imports (`avatars.wav2lip_avatar`, `avatars.musetalk_avatar`,
-`avatars.audio_features.mel`, `avatars.audio_features.whisper`; app.py:128-137) resolve to the MI355X plugin modules, then
+`avatars.ultralight_avatar`, `avatars.audio_features.mel`, `avatars.audio_features.whisper`, `avatars.audio_features.hubert`;
+app.py:128-137) resolve to the MI355X plugin modules, then
 runs app.py as __main__.  The reference tree stays byte-identical; `avatars.base_avatar`, `registry`, `server/`, `streamout/`
 are the reference's own.
 """
@@ -27,10 +28,14 @@ def main():
     import livetalking_amd.avatars.audio_features.mel as mel
     import livetalking_amd.avatars.audio_features.whisper as whisper
     import livetalking_amd.avatars.musetalk_avatar as mt
+    import livetalking_amd.avatars.audio_features.hubert as hubert
+    import livetalking_amd.avatars.ultralight_avatar as ul
     import livetalking_amd.avatars.wav2lip_avatar as w2l
     sys.modules["avatars.wav2lip_avatar"] = w2l
     sys.modules["avatars.musetalk_avatar"] = mt
+    sys.modules["avatars.ultralight_avatar"] = ul
     sys.modules["avatars.audio_features.mel"] = mel
+    sys.modules["avatars.audio_features.hubert"] = hubert
     sys.modules["avatars.audio_features.whisper"] = whisper
     sys.argv = ["app.py"] + sys.argv[1:]
     runpy.run_path(os.path.join(ref, "app.py"), run_name="__main__")

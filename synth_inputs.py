@@ -455,3 +455,116 @@ def whisper_encoder_state_dict(seed: int = 2468) -> Dict[str, np.ndarray]:
     sd["layer_norm.weight"] = (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32)
     sd["layer_norm.bias"] = (0.05 * rng.standard_normal(D)).astype(np.float32)
     return sd
+
+
+# ------------------------------------------------------------------------------------------------ Ultralight
+def _ul_blocks():
+    """(prefix, kind, cin, cout, residual) in the registration order of avatars/ultralight/unet.py Model(6, 'hubert')
+    (unet.py:168-196): kind "ir" = InvertedResidual with expand_ratio 2 (unet.py:7-36), "conv" = biased dense 3x3 conv +
+    BatchNorm of the audio tower (prefix = (conv name, bn name))."""
+    out = []
+
+    def dconv(p, cin, cout):                     # DoubleConvDW, unet.py:38-49
+        out.append((p + ".double_conv.0", "ir", cin, cout, False))
+        out.append((p + ".double_conv.1", "ir", cout, cout, True))
+
+    a = "audio_model."                           # AudioConvHubert, unet.py:132-150
+    out.append((a + "conv1", "ir", 16, 64, False))
+    out.append((a + "conv2", "ir", 64, 128, False))
+    out.append(((a + "conv3", a + "bn3"), "conv", 128, 256, False))
+    out.append((a + "conv4", "ir", 256, 256, True))
+    out.append(((a + "conv5", a + "bn5"), "conv", 256, 512, False))
+    out.append((a + "conv6", "ir", 512, 512, True))
+    out.append((a + "conv7", "ir", 512, 512, True))
+    dconv("fuse_conv.0", 1024, 512)
+    dconv("fuse_conv.1", 512, 256)
+    out.append(("inc.inconv.0", "ir", 6, 32, False))
+    for i, (ci, co) in enumerate(((32, 64), (64, 128), (128, 256), (256, 512)), 1):
+        dconv(f"down{i}.maxpool_conv.0", ci, co)
+    for i, (ci, co) in enumerate(((512, 128), (256, 64), (128, 32), (64, 32)), 1):
+        dconv(f"up{i}.conv", ci, co)
+    return out
+
+
+def ultralight_state_dict(seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Reference-named fp32 state_dict of avatars/ultralight/unet.py Model(6, 'hubert') as numpy arrays (484 tensors).
+
+    Fixed BatchNorm statistics, as wav2lip_state_dict draws them (a data-calibrated draw gives dead channels a gain of
+    1/sqrt(eps) and makes the random network amplify rounding ~1000x): conv std sqrt(2/fan_in) where a ReLU follows,
+    sqrt(1/fan_in) for the linear project conv (depthwise fan_in = 9); gamma U(0.7, 1.3), U(0.3, 0.7) on the last
+    BatchNorm of a residual block; beta 0.1 N, running_mean 0.2 N, running_var U(0.6, 1.6); audio conv biases 0.05 N;
+    outc weight 0.4 N, bias 0.2 N."""
+    rng = np.random.default_rng(seed)
+    sd: Dict[str, np.ndarray] = {}
+
+    def bn(p, c, damp=False):
+        lo, hi = (0.3, 0.7) if damp else (0.7, 1.3)
+        sd[p + ".weight"] = rng.uniform(lo, hi, c).astype(np.float32)
+        sd[p + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[p + ".running_mean"] = (rng.standard_normal(c) * 0.2).astype(np.float32)
+        sd[p + ".running_var"] = rng.uniform(0.6, 1.6, c).astype(np.float32)
+        sd[p + ".num_batches_tracked"] = np.asarray(1000, dtype=np.int64)
+
+    def w(shape, fan_in, relu):
+        return (rng.standard_normal(shape) * np.sqrt((2.0 if relu else 1.0) / fan_in)).astype(np.float32)
+
+    for prefix, kind, cin, cout, residual in _ul_blocks():
+        if kind == "ir":
+            mid = 2 * cin
+            sd[prefix + ".conv.0.weight"] = w((mid, cin, 1, 1), cin, True)
+            bn(prefix + ".conv.1", mid)
+            sd[prefix + ".conv.3.weight"] = w((mid, 1, 3, 3), 9, True)
+            bn(prefix + ".conv.4", mid)
+            sd[prefix + ".conv.6.weight"] = w((cout, mid, 1, 1), mid, False)
+            bn(prefix + ".conv.7", cout, damp=residual)
+        else:
+            conv, norm = prefix
+            sd[conv + ".weight"] = w((cout, cin, 3, 3), cin * 9, True)
+            sd[conv + ".bias"] = (rng.standard_normal(cout) * 0.05).astype(np.float32)
+            bn(norm, cout)
+    sd["outc.conv.weight"] = (rng.standard_normal((3, 32, 1, 1)) * 0.4).astype(np.float32)
+    sd["outc.conv.bias"] = (rng.standard_normal(3) * 0.2).astype(np.float32)
+    return sd
+
+
+def ultralight_avatar(n_frames: int = 4, full_hw: Tuple[int, int] = (360, 640), seed: int = 3
+                      ) -> Tuple[List[np.ndarray], List[np.ndarray], List[Tuple[int, int, int, int]]]:
+    """(frame_list_cycle, face_list_cycle, coord_list_cycle) as avatars/ultralight_avatar.py:63-81 load_avatar returns them:
+    BGR uint8 full frames, BGR uint8 168x168 face crops, (x1, y1, x2, y2) boxes that differ per frame."""
+    rng = np.random.default_rng(seed)
+    H, W_ = full_hw
+    frames, faces, coords = [], [], []
+    cy, cx = H // 2, W_ // 2
+    box = min(H, W_) // 2
+    for _ in range(n_frames):
+        frames.append(_smooth_image(rng, H, W_))
+        faces.append(_smooth_image(rng, 168, 168, cells=8))
+        j = rng.integers(-4, 5, 4)
+        x1 = int(cx - box // 2 + j[0]); x2 = int(cx + box // 2 + j[1])
+        y1 = int(cy - box // 2 + j[2]); y2 = int(cy + box // 2 + j[3])
+        coords.append((x1, y1, x2, y2))
+    return frames, faces, coords
+
+
+def ultralight_feats(batch: int, seed: int = 21) -> np.ndarray:
+    """Stand-in HuBERT chunks: float32 (batch, 16, 1024), unit variance (layer-normed hidden states)."""
+    return np.random.default_rng(seed).standard_normal((batch, 16, 1024)).astype(np.float32)
+
+
+def ultralight_faces(batch: int, seed: int = 1234) -> List[np.ndarray]:
+    """The 168x168 BGR uint8 bank faces ultralight_inputs builds its images from."""
+    rng = np.random.default_rng(seed + 77)
+    return [_smooth_image(rng, 168, 168, cells=8) for _ in range(batch)]
+
+
+def ultralight_inputs(batch: int, seed: int = 1234):
+    """(img6 float32 (batch, 6, 160, 160), feat float32 (batch, 16, 32, 32)) as LightReal.inference_batch builds them
+    (avatars/ultralight_avatar.py:150-166) from ultralight_faces(batch, seed): reference crop, masked crop, / 255, BGR.
+    The first k items of a longer draw equal the draw of k items."""
+    imgs = []
+    for face in ultralight_faces(batch, seed):
+        real = face[4:164, 4:164].copy()
+        masked = real.copy()
+        masked[5:150, 5:155] = 0                    # cv2.rectangle(img, (5, 5, 150, 145), 0, -1): x 5..154, y 5..149
+        imgs.append(np.concatenate([real.transpose(2, 0, 1), masked.transpose(2, 0, 1)]).astype(np.float32) / np.float32(255.0))
+    return np.stack(imgs), ultralight_feats(batch, seed + 78).reshape(batch, 16, 32, 32)

@@ -1,0 +1,158 @@
+"""Float64 restatement of the Ultralight generator for the tests (TEST INFRASTRUCTURE ONLY).
+
+Restates, as functional F.conv2d calls over a layer table,
+  avatars/ultralight/unet.py:7-36    InvertedResidual (1x1 expand + BN + ReLU, 3x3 depthwise + BN + ReLU, 1x1 project + BN, + x)
+  avatars/ultralight/unet.py:38-49   DoubleConvDW
+  avatars/ultralight/unet.py:72-87   Up (bilinear x2, align_corners=True; F.pad is a no-op at 160 x 160; cat([up, skip]))
+  avatars/ultralight/unet.py:132-166 AudioConvHubert
+  avatars/ultralight/unet.py:198-215 Model.forward
+  avatars/ultralight_avatar.py:150-171 the 6-channel input and the * 255 output
+tests/golden/ultralight_golden.npz (scripts/gen_golden_ultralight.py) pins it to the reference's own Model(6, 'hubert').
+
+Tap names are the state_dict prefixes of the convs; a conv's tap is the tensor after its BatchNorm, its ReLU where it has one,
+and the residual add where the block has one (what one launch of the engine writes).  "<block>.up" is an upsample's output,
+"outc.conv" the sigmoid output.
+
+`fp16_model=True` is the rounding model of an fp16 implementation the frame tests measure against: weights rounded to fp16,
+and the output of every BatchNorm, every biased conv and every upsample rounded to fp16; everything else stays float64.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+BN_EPS = 1e-5
+RES = 160
+
+# DoubleConvDW blocks: (prefix, cin, cout, stride)
+DOWN = [("down1.maxpool_conv.0", 32, 64, 2), ("down2.maxpool_conv.0", 64, 128, 2), ("down3.maxpool_conv.0", 128, 256, 2),
+        ("down4.maxpool_conv.0", 256, 512, 2)]
+FUSE = [("fuse_conv.0", 1024, 512, 1), ("fuse_conv.1", 512, 256, 1)]
+UP = [("up1", 512, 128), ("up2", 256, 64), ("up3", 128, 32), ("up4", 64, 32)]
+# audio tower: ("ir", prefix, cin, cout, residual) | ("conv", conv, bn, cin, cout, stride, pad)
+AUDIO = [("ir", "audio_model.conv1", 16, 64, False), ("ir", "audio_model.conv2", 64, 128, False),
+         ("conv", "audio_model.conv3", "audio_model.bn3", 128, 256, 2, 1), ("ir", "audio_model.conv4", 256, 256, True),
+         ("conv", "audio_model.conv5", "audio_model.bn5", 256, 512, 2, 3), ("ir", "audio_model.conv6", 512, 512, True),
+         ("ir", "audio_model.conv7", 512, 512, True)]
+
+
+def conv_prefixes():
+    """Every state_dict prefix that holds a conv weight, in execution order."""
+    out = []
+
+    def ir(p):
+        out.extend([p + ".conv.0", p + ".conv.3", p + ".conv.6"])
+
+    def dconv(p):
+        ir(p + ".double_conv.0"); ir(p + ".double_conv.1")
+
+    ir("inc.inconv.0")
+    for p, *_ in DOWN:
+        dconv(p)
+    for item in AUDIO:
+        ir(item[1]) if item[0] == "ir" else out.append(item[1])
+    for p, *_ in FUSE:
+        dconv(p)
+    for p, *_ in UP:
+        dconv(p + ".conv")
+    out.append("outc.conv")
+    return out
+
+
+class _Net:
+    def __init__(self, sd, dtype, fp16_model, taps):
+        self.sd = {k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}
+        self.dtype, self.h, self.taps = dtype, fp16_model, taps
+
+    def r16(self, t):
+        return t.half().to(self.dtype) if self.h else t
+
+    def w(self, name):
+        t = self.sd[name].to(torch.float32)
+        return (t.half() if self.h else t).to(self.dtype)
+
+    def bn(self, x, p):
+        g, b = self.sd[p + ".weight"].to(self.dtype), self.sd[p + ".bias"].to(self.dtype)
+        m, v = self.sd[p + ".running_mean"].to(self.dtype), self.sd[p + ".running_var"].to(self.dtype)
+        y = (x - m[None, :, None, None]) / torch.sqrt(v[None, :, None, None] + BN_EPS) * g[None, :, None, None] + b[None, :, None, None]
+        return self.r16(y)
+
+    def tap(self, name, t):
+        if self.taps is not None:
+            self.taps[name] = t.detach().to(torch.float64).numpy().copy()
+        return t
+
+    def ir(self, p, x, stride, residual):
+        y = self.tap(p + ".conv.0", F.relu(self.bn(F.conv2d(x, self.w(p + ".conv.0.weight")), p + ".conv.1")))
+        wd = self.w(p + ".conv.3.weight")
+        y = self.tap(p + ".conv.3", F.relu(self.bn(F.conv2d(y, wd, stride=stride, padding=1, groups=wd.shape[0]), p + ".conv.4")))
+        y = self.bn(F.conv2d(y, self.w(p + ".conv.6.weight")), p + ".conv.7")
+        return self.tap(p + ".conv.6", x + y if residual else y)
+
+    def dconv(self, p, x, stride):
+        return self.ir(p + ".double_conv.1", self.ir(p + ".double_conv.0", x, stride, False), 1, True)
+
+    def forward(self, img6, feat):
+        x = self.ir("inc.inconv.0", img6, 1, False)
+        skips = [x]
+        for p, _, _, s in DOWN:
+            x = self.dconv(p, x, s)
+            skips.append(x)
+        a = feat
+        for item in AUDIO:
+            if item[0] == "ir":
+                a = self.ir(item[1], a, 1, item[4])
+            else:
+                _, conv, norm, _, _, stride, pad = item
+                a = self.r16(F.conv2d(a, self.w(conv + ".weight"), self.sd[conv + ".bias"].to(self.dtype), stride=stride, padding=pad))
+                a = self.tap(conv, F.relu(self.bn(a, norm)))
+        x = torch.cat([skips.pop(), a], dim=1)
+        for p, _, _, s in FUSE:
+            x = self.dconv(p, x, s)
+        for p, _, _ in UP:
+            u = self.tap(p + ".up", self.r16(F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)))
+            x = self.dconv(p + ".conv", torch.cat([u, skips.pop()], dim=1), 1)
+        logits = F.conv2d(x, self.sd["outc.conv.weight"].to(self.dtype) if not self.h else self.w("outc.conv.weight"),
+                          self.sd["outc.conv.bias"].to(self.dtype))
+        return self.tap("outc.conv", torch.sigmoid(logits))
+
+
+def forward(sd: Dict[str, np.ndarray], img6: np.ndarray, feat: np.ndarray, dtype=torch.float64, fp16_model: bool = False,
+            taps: Optional[dict] = None) -> np.ndarray:
+    """Model(6, 'hubert').forward: img6 (B, 6, 160, 160) in [0, 1], feat (B, 16, 32, 32) -> sigmoid output (B, 3, 160, 160)
+    as a float64 array, computed in `dtype`."""
+    with torch.no_grad():
+        net = _Net(sd, dtype, fp16_model, taps)
+        x = torch.as_tensor(np.asarray(img6)).to(dtype)
+        a = torch.as_tensor(np.asarray(feat)).to(dtype).reshape(-1, 16, 32, 32)
+        if fp16_model:
+            x, a = net.r16(x), net.r16(a)
+        return net.forward(x, a).to(torch.float64).numpy()
+
+
+def frames_u8(pred: np.ndarray) -> np.ndarray:
+    """avatars/ultralight_avatar.py:170,181: pred (B, 3, H, W) float32 -> (pred.transpose(0, 2, 3, 1) * 255).astype(uint8)."""
+    p = np.asarray(pred, dtype=np.float32).transpose(0, 2, 3, 1) * np.float32(255.0)
+    return p.astype(np.uint8)
+
+
+def img6_from_faces(faces) -> np.ndarray:
+    """avatars/ultralight_avatar.py:150-161 for a list of 168x168 BGR uint8 faces -> float32 (n, 6, 160, 160)."""
+    out = []
+    for f in faces:
+        real = np.asarray(f)[4:164, 4:164].copy()
+        masked = real.copy()
+        masked[5:150, 5:155] = 0          # cv2.rectangle(img, (5, 5, 150, 145), (0, 0, 0), -1): Rect x, y, w, h, corners inclusive
+        out.append(np.concatenate([real.transpose(2, 0, 1).astype(np.float32) / 255.0, masked.transpose(2, 0, 1).astype(np.float32) / 255.0]))
+    return np.stack(out).astype(np.float32)
+
+
+def frame_stats(got_u8: np.ndarray, ref_u8: np.ndarray):
+    """(max LSB, PSNR dB, share of differing bytes) of two uint8 frame stacks."""
+    d = np.abs(got_u8.astype(np.int32) - ref_u8.astype(np.int32))
+    mse = float((d.astype(np.float64) ** 2).mean())
+    psnr = 99.0 if mse == 0 else float(10 * np.log10(255.0 ** 2 / mse))
+    return int(d.max()), psnr, float((d != 0).mean())
