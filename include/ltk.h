@@ -254,6 +254,30 @@ int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n);
 int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows,
                      void* d_out, void* stream);
 
+/* =========================== HuBERT-large audio features (Ultralight, avatars/ultralight/audio2feature.py) =========================== */
+
+/* audio2feature.py:9-11: transformers HubertModel in the configuration of facebook/hubert-large-ls960-ft (feat_extract_norm "layer",
+ * conv_bias, do_stable_layer_norm, feat_proj_layer_norm; 7 conv layers of 512 channels, hidden 1024, 16 heads, FFN 4096, positional conv
+ * k 128 in 16 groups).  sd = HubertModel.state_dict() names, fp32 host tensors, with ONE difference: the positional conv arrives with
+ * its weight norm folded, as "encoder.pos_conv_embed.conv.weight" [1024][64][128] (Engine.load_hubert folds it).  The depth is the
+ * number of "encoder.layers.N" present; "masked_spec_embed" is ignored.  A missing tensor or a wrong shape returns LTK_E_INVALID with
+ * a message, a second load LTK_E_STATE.  The weights are packed once (0.63 GB of fp16 at 24 layers); every clip length gets a
+ * program of its own over them on first use, at most 3 are kept. */
+int ltk_hubert_load(ltk_engine* e, const ltk_named_tensor* sd, int n);
+
+/* audio2feature.py:15-54 get_hubert_from_16k_speech: pcm host float32 [n_samples] at 16 kHz, normalised over the whole input
+ * ((x - mean) / sqrt(var + 1e-7), Wav2Vec2FeatureExtractor), forwarded in clips of 320 000 samples (each with the 80 samples behind
+ * it) and a tail of at least 400 samples, concatenated, then padded with zero rows or trimmed to expected = (n_samples - 80) / 320
+ * rows.  out_host: float32 [cap_rows][1024], cap_rows >= expected; *rows = expected.  LTK_E_INVALID if the model returned a row count
+ * more than one off the expected one. */
+int ltk_hubert_features(ltk_engine* e, const float* pcm, long long n_samples, float* out_host, int cap_rows, int* rows);
+
+/* avatars/audio_features/hubert.py:24-49 HubertASR.run_step feature part: one forward of the step's l + 2B + r chunks (400 <= n_samples
+ * < 320 000) and feature2chunks (base_asr.py:91-156): frame i takes rows [first_row + i*row_step, first_row + i*row_step + rows),
+ * index-clamped.  d_out: device float32 [batch][rows][1024] (= the (16,1024) chunks ltk_ultralight_infer takes at rows 16,
+ * first_row 2*(l/2) - 8, row_step 2).  Returns when d_out is complete. */
+int ltk_hubert_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out);
+
 /* Avatar preparation: avatars/musetalk/models/vae.py:84-94,110-122 get_latents_for_unet, as
  * avatars/musetalk/genavatar.py:116-128 calls it.  vae_sd: the AutoencoderKL state_dict keys "encoder.*" and
  * "quant_conv.*" (fp32 host).  faces_bgr: host uint8 [nfaces][256][256][3] (the LANCZOS-resized crops);
@@ -268,6 +292,26 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
 /* named tensor of the last Whisper step as [C][T] float32: "input_features", "hidden_states.0".."hidden_states.4",
  * or an op name ("conv1", "layers.0.self_attn.out_proj", ...) */
 int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats);
+
+/* named tensor of the HuBERT program that ran last as [C][T] float32: an op name (ltk_hubert_op_name; an attention's output is
+ * "<op>.attn"), or "input_values": the normalised waveform fp32 [n_samples] of that clip */
+int ltk_hubert_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats);
+/* ops of a HuBERT program in execution order; type as ltk_musetalk_op_name, and 7 conv layer 0 + LayerNorm + GELU, 8 LayerNorm +
+ * GELU, 9 positional conv */
+int ltk_hubert_op_count(ltk_engine* e);
+int ltk_hubert_op_name(ltk_engine* e, int op, char* buf, int buf_len, int* type);
+/* encoder layers of the loaded model, programs currently kept, activation bytes of the program that ran last (any may be NULL) */
+int ltk_hubert_info(ltk_engine* e, int* layers, int* programs, size_t* activation_bytes);
+/* The HuBERT kernels on their own (unit tests; host in, host out; token-major inputs [T][C] are rounded to fp16 on the way in, outputs
+ * come back channel-major [C][T]).  stats: mean_var[0] = mean, [1] = population variance of pcm.  layer0: x fp32 [n] (read as is), w
+ * [512][10] -> [512][(n-10)/5+1].  ln_gelu: LayerNorm(512, eps 1e-5) + GELU.  posconv: x [T][1024], w [1024][64][128] ->
+ * x + GELU(conv)[:T].  chunks: feat [T][1024] -> out [batch][rows][1024]. */
+int ltk_hubert_stats(ltk_engine* e, const float* pcm, long long n, float* mean_var);
+int ltk_hubert_layer0_host(ltk_engine* e, const float* x, int n, const float* w, const float* bias, const float* gamma, const float* beta,
+                           float* out);
+int ltk_hubert_ln_gelu_host(ltk_engine* e, const float* x, int T, const float* gamma, const float* beta, float* out);
+int ltk_hubert_posconv_host(ltk_engine* e, const float* x, int T, const float* w, const float* bias, float* out);
+int ltk_hubert_chunks_host(ltk_engine* e, const float* feat, int T, int batch, int first_row, int row_step, int rows, float* out);
 
 /* U-Net + VAE decoder on explicit inputs: latents host fp32 [B][8][32][32], feat host fp32 [B][50][384] (before
  * the positional encoding).  Outputs (any may be NULL): unet_out fp32 [B][4][32][32], image fp32 [B][3][256][256]

@@ -6,9 +6,12 @@ l+r chunks of context exist - puts ONE list of batch_size feature chunks on `fea
 With `audio_feat_length=[4, 4]` (ultralight_avatar.py:140), start = l/2 and multiplier 2, frame i takes HuBERT rows
 [2*(i + l/2) - 8, 2*(i + l/2) + 8), index-clamped (base_asr.py:91-133): 16 rows of 1024 per frame.
 
-HuBERT-large itself (24 transformer layers) is NOT on the engine: `audio_processor` is any object with
-`get_hubert_from_16k_speech(pcm) -> (T, 1024)` - the reference's Audio2Feature, `load_model()` below, or a test stand-in.
-The engine's part starts at these chunks (Engine.ultralight_infer takes them as float32 [batch][16][32][32]).
+`audio_processor` is any object with `get_hubert_from_16k_speech(pcm) -> (T, 1024)`: `load_model()` below (transformers'
+HubertModel on torch, the default), a test stand-in, or `EngineAudio2Feature`: HuBERT-large as a device program of the engine
+(csrc/hubert.hip), opt-in through ultralight_avatar.load_model.  A processor that also has `step(pcm, batch, first_row,
+row_step, rows)` (EngineAudio2Feature does) hands back the chunks as ONE device tensor [batch][rows][1024]; run_step then puts
+batch_size views of it on feat_queue and the features never visit the host (Engine.ultralight_infer takes them as float32
+[batch][16][32][32]).
 
 One deliberate difference: the reference's silent default is `batch_size * [zeros((10, 1024))]` (hubert.py:38), which
 LightReal.inference_batch cannot reshape to (16, 32, 32); the silent chunks here are zeros((16, 1024)).
@@ -60,12 +63,47 @@ class Audio2Feature:
             return ret[:expected]
 
 
-def load_model(model_dir: str = HUBERT_DIR) -> Audio2Feature:
-    """The audio processor ultralight_avatar.load_model hands to every session (ultralight_avatar.py:58-61)."""
+class EngineAudio2Feature:
+    """Audio2Feature on the engine: `source` is the checkpoint directory (HubertModel.from_pretrained; only the weights are read,
+    the Wav2Vec2Processor's one job - zero mean, unit variance over the utterance - is part of the device program) or a
+    HubertModel state dict."""
+
+    def __init__(self, engine, source=HUBERT_DIR):
+        if isinstance(source, (str, os.PathLike)):
+            from transformers import HubertModel
+            source = HubertModel.from_pretrained(source).state_dict()
+        self.engine = engine
+        engine.load_hubert(source)
+
+    def get_hubert_from_16k_speech(self, speech):
+        speech = np.asarray(speech)
+        if speech.ndim == 2:
+            speech = speech[:, 0]
+        return self.engine.hubert_features(speech)
+
+    def step(self, pcm, batch, first_row, row_step=2, rows=16):
+        """One forward of the step's pcm -> device float32 (batch, rows, 1024): frame i = rows [first_row + i * row_step, + rows),
+        index-clamped."""
+        import torch
+        out = torch.empty((batch, rows, 1024), dtype=torch.float32, device=self.engine.torch_device)
+        self.engine.hubert_step(pcm, batch, first_row, out.data_ptr(), row_step=row_step, rows=rows)
+        return out
+
+    def zeros(self, batch, rows):
+        import torch
+        return torch.zeros((batch, rows, 1024), dtype=torch.float32, device=self.engine.torch_device)
+
+
+def check_model_dir(model_dir: str = HUBERT_DIR) -> None:
     if not os.path.isdir(model_dir):
         raise FileNotFoundError(
             f"{model_dir} is missing: the Ultralight avatar needs the HuBERT-large checkpoint the reference uses "
             "(facebook/hubert-large-ls960-ft) there, or pass your own audio_processor with get_hubert_from_16k_speech()")
+
+
+def load_model(model_dir: str = HUBERT_DIR) -> Audio2Feature:
+    """The audio processor ultralight_avatar.load_model hands to every session (ultralight_avatar.py:58-61)."""
+    check_model_dir(model_dir)
     return Audio2Feature(model_dir)
 
 
@@ -104,6 +142,19 @@ class HubertASR(BaseASR):
         if len(self.frames) <= self.stride_left_size + self.stride_right_size:
             return
         rows = 2 * (self.audio_feat_length[0] + self.audio_feat_length[1])
+        if hasattr(self.audio_processor, "step"):
+            # the processor forwards and slices on the device: first_row = int(start * 2) - 2 * win[0] with start = l / 2
+            if not is_all_silence or not self.last_is_silence:
+                first_row = int(self.stride_left_size / 2 * 2) - 2 * self.audio_feat_length[0]
+                dev = self.audio_processor.step(np.concatenate(self.frames), self.batch_size, first_row, 2, rows)
+            elif hasattr(self.audio_processor, "zeros"):
+                dev = self.audio_processor.zeros(self.batch_size, rows)           # the silent default, on the device as well
+            else:
+                dev = np.zeros((self.batch_size, rows, 1024), dtype=np.float32)
+            self.feat_queue.put([dev[i] for i in range(self.batch_size)])
+            self.frames = self.frames[-(self.stride_left_size + self.stride_right_size):]
+            self.last_is_silence = is_all_silence
+            return
         chunks = [np.zeros((rows, 1024), dtype=np.float32) for _ in range(self.batch_size)]
         if not is_all_silence or not self.last_is_silence:
             inputs = np.concatenate(self.frames)

@@ -10,8 +10,9 @@ Module contract the reference's app.py relies on (the plugin is picked by name):
 What changes underneath: the U-Net is per avatar (`ultralight.pth`), so `load_avatar` returns an `UltralightNet` handle in the
 model's place; it registers state_dict + bank with the engine (libltk_hip.so) on first use.  `inference_batch` returns device
 handles (uint8 160x160x3, already truncated the way paste_back_frame's astype(uint8) does) instead of float numpy frames;
-`paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array.  HuBERT-large stays on
-torch (audio_features/hubert.py).
+`paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array.  HuBERT-large runs on
+torch by default (audio_features/hubert.py Audio2Feature); with LTK_HUBERT_ENGINE=1 or opt.hubert_engine it runs on the engine
+(EngineAudio2Feature) and its chunks reach inference_batch as device tensors.
 """
 from __future__ import annotations
 
@@ -29,6 +30,8 @@ from .audio_features import hubert as _hubert
 
 _engines = {}
 _engines_lock = threading.Lock()
+_hubert_lock = threading.Lock()    # held across "look up, else build": two sessions' load_model calls must not both load the engine
+_hubert_processors = {}            # engine -> its EngineAudio2Feature: an engine holds one HuBERT model, load_model may be called again
 
 
 def _engine(device: int = 0) -> Engine:
@@ -73,7 +76,17 @@ class UltralightNet:
 
 def load_model(opt):
     """ultralight_avatar.py:58-61: (audio_processor, None) - the U-Net comes with the avatar."""
-    audio_processor = _hubert.load_model()
+    _hubert.check_model_dir(_hubert.HUBERT_DIR)
+    if os.environ.get("LTK_HUBERT_ENGINE", "0") == "1" or getattr(opt, "hubert_engine", False):
+        eng = _engine(0)
+        with _hubert_lock:
+            audio_processor = _hubert_processors.get(eng)
+            if audio_processor is None:
+                for dead in [e for e in _hubert_processors if e._h is None]:
+                    del _hubert_processors[dead]
+                audio_processor = _hubert_processors[eng] = _hubert.EngineAudio2Feature(eng, _hubert.HUBERT_DIR)
+    else:
+        audio_processor = _hubert.load_model()
     model = None
     return audio_processor, model
 
@@ -127,6 +140,8 @@ class LightReal(BaseAvatar):
         import torch
         if isinstance(audiofeat_batch, torch.Tensor):
             return audiofeat_batch.to(self.engine.torch_device, torch.float32).reshape(-1, 16, 32, 32).contiguous()
+        if len(audiofeat_batch) and isinstance(audiofeat_batch[0], torch.Tensor):     # HubertASR over a processor with step(): device views
+            return torch.stack([a.to(self.engine.torch_device, torch.float32).reshape(16, 32, 32) for a in audiofeat_batch]).contiguous()
         arr = np.ascontiguousarray(np.stack([np.asarray(a, dtype=np.float32).reshape(16, 32, 32) for a in audiofeat_batch]))
         return torch.from_numpy(arr).to(self.engine.torch_device)
 

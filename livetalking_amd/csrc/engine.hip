@@ -101,6 +101,7 @@ void ltk_engine_destroy(ltk_engine* e) {
     ul_unload(e);
     if (e->mt) mt_graph_delete(e->mt);
     if (e->whisper) mt_graph_delete(e->whisper);
+    hubert_unload(e);
     if (e->vae_enc) mt_graph_delete(e->vae_enc);
     if (e->d_wbasis) (void)hipFree(e->d_wbasis);
     if (e->d_wlogspec) (void)hipFree(e->d_wlogspec);

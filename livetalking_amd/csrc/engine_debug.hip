@@ -632,4 +632,168 @@ int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_
     return LTK_OK;
 }
 
+// ---------------------------------------------------------------- HuBERT: the program's tensors and ops, and its kernels on their own
+int ltk_hubert_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats) {
+    if (!e || !name || !out) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    if (!e->hubert_last) return fail(LTK_E_STATE, "no HuBERT program has run yet");
+    CHK(hipStreamSynchronize(e->compute));
+    if (std::string(name) == "input_values") {                 // the normalised waveform of the clip, fp32 [n_samples]
+        size_t n = 0;
+        for (auto& p : e->hubert_progs) if (p.g == e->hubert_last) n = (size_t)p.n_samples;
+        if (n != n_floats) return fail(LTK_E_INVALID, "size mismatch: the clip has " + std::to_string(n) + " samples");
+        CHK(hipMemcpy(out, mt_hubert_pcm_in(e->hubert_last), n * sizeof(float), hipMemcpyDeviceToHost));
+        return LTK_OK;
+    }
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->hubert_last, name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no HuBERT tensor named ") + name);
+    const size_t cnt = (size_t)C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats");
+    DevBuf tmp;
+    CHK(hipMalloc(&tmp.p, cnt * sizeof(float)));
+    launch_nhwc_to_nchw_f32(t, 1, H, W, ld, coff, C, (float*)tmp.p, e->compute);
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(out, tmp.p, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    return LTK_OK;
+}
+
+int ltk_hubert_op_count(ltk_engine* e) {
+    if (!e) return 0;
+    std::lock_guard<std::mutex> g(e->mu);
+    return e->hubert_w ? mt_op_count(e->hubert_w) : 0;
+}
+
+int ltk_hubert_op_name(ltk_engine* e, int op, char* buf, int buf_len, int* type) {
+    if (!e || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    const char* n = mt_op_name(e->hubert_w, op, type);
+    if (!n) return fail(LTK_E_INVALID, "no such op");
+    snprintf(buf, (size_t)buf_len, "%s", n);
+    return LTK_OK;
+}
+
+int ltk_hubert_info(ltk_engine* e, int* layers, int* programs, size_t* activation_bytes) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    if (layers) *layers = mt_hubert_layers(e->hubert_w);
+    if (programs) *programs = (int)e->hubert_progs.size();
+    if (activation_bytes) *activation_bytes = e->hubert_last ? mt_activation_bytes(e->hubert_last) : 0;
+    return LTK_OK;
+}
+
+int ltk_hubert_stats(ltk_engine* e, const float* pcm, long long n, float* mean_var) {
+    if (!e || !pcm || !mean_var || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    DevBuf x, st;
+    CHK(hipMalloc(&x.p, (size_t)n * sizeof(float)));
+    CHK(hipMalloc(&st.p, 2 * sizeof(float)));
+    CHK(hipMemcpy(x.p, pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    launch_hubert_stats((const float*)x.p, n, (float*)st.p, e->compute);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(mean_var, st.p, 2 * sizeof(float), hipMemcpyDeviceToHost));
+    return LTK_OK;
+}
+
+namespace {
+
+// host fp32 [T][C] -> a CB16 device tensor; a CB16 device tensor -> host fp32 [C][T]
+int hb_up(ltk_engine* e, const float* host, int T, int C, DevBuf* stage, DevBuf* cb) {
+    CHK(hipMalloc(&stage->p, (size_t)T * C * sizeof(float)));
+    CHK(hipMalloc(&cb->p, (size_t)T * C * sizeof(f16)));
+    CHK(hipMemcpy(stage->p, host, (size_t)T * C * sizeof(float), hipMemcpyHostToDevice));
+    launch_tokens_to_cb16((const float*)stage->p, 1, T, C, nullptr, (f16*)cb->p, C / 16, 0, e->compute);
+    return LTK_OK;
+}
+int hb_down(ltk_engine* e, const f16* cb, int T, int C, float* host) {
+    DevBuf tmp;
+    CHK(hipMalloc(&tmp.p, (size_t)T * C * sizeof(float)));
+    launch_nhwc_to_nchw_f32(cb, 1, T, 1, C, 0, C, (float*)tmp.p, e->compute);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(host, tmp.p, (size_t)T * C * sizeof(float), hipMemcpyDeviceToHost));
+    return LTK_OK;
+}
+int hb_vec(const float* host, size_t n, DevBuf* d) {
+    CHK(hipMalloc(&d->p, n * sizeof(float)));
+    CHK(hipMemcpy(d->p, host, n * sizeof(float), hipMemcpyHostToDevice));
+    return LTK_OK;
+}
+
+}  // namespace
+
+int ltk_hubert_layer0_host(ltk_engine* e, const float* x, int n, const float* w, const float* bias, const float* gamma, const float* beta,
+                           float* out) {
+    if (!e || !x || !w || !bias || !gamma || !beta || !out || n < 10) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    const int L0 = (n - 10) / 5 + 1;
+    DevBuf dx, dw, db, dg, de, dy;
+    int rc = hb_vec(x, (size_t)n, &dx);
+    if (!rc) rc = hb_vec(w, 5120, &dw);
+    if (!rc) rc = hb_vec(bias, 512, &db);
+    if (!rc) rc = hb_vec(gamma, 512, &dg);
+    if (!rc) rc = hb_vec(beta, 512, &de);
+    if (rc) return rc;
+    CHK(hipMalloc(&dy.p, (size_t)L0 * 512 * sizeof(f16)));
+    launch_hubert_layer0((const float*)dx.p, n, (const float*)dw.p, (const float*)db.p, (const float*)dg.p, (const float*)de.p, 1e-5f,
+                         (f16*)dy.p, e->compute);
+    return hb_down(e, (const f16*)dy.p, L0, 512, out);
+}
+
+int ltk_hubert_ln_gelu_host(ltk_engine* e, const float* x, int T, const float* gamma, const float* beta, float* out) {
+    if (!e || !x || !gamma || !beta || !out || T <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    DevBuf st, dx, dg, de, dy;
+    int rc = hb_up(e, x, T, 512, &st, &dx);
+    if (!rc) rc = hb_vec(gamma, 512, &dg);
+    if (!rc) rc = hb_vec(beta, 512, &de);
+    if (rc) return rc;
+    CHK(hipMalloc(&dy.p, (size_t)T * 512 * sizeof(f16)));
+    launch_ln_gelu512((const f16*)dx.p, 0, T, 1e-5f, (const float*)dg.p, (const float*)de.p, (f16*)dy.p, 0, e->compute);
+    return hb_down(e, (const f16*)dy.p, T, 512, out);
+}
+
+int ltk_hubert_posconv_host(ltk_engine* e, const float* x, int T, const float* w, const float* bias, float* out) {
+    if (!e || !x || !w || !bias || !out || T <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    DevBuf st, dx, dw, db, dy;
+    int rc = hb_up(e, x, T, 1024, &st, &dx);
+    if (!rc) rc = hb_vec(bias, 1024, &db);
+    if (rc) return rc;
+    {
+        std::vector<f16> packed(kPosConvPackHalfs);
+        hubert_posconv_pack(w, packed.data());
+        CHK(hipMalloc(&dw.p, packed.size() * sizeof(f16)));
+        CHK(hipMemcpy(dw.p, packed.data(), packed.size() * sizeof(f16), hipMemcpyHostToDevice));
+    }
+    CHK(hipMalloc(&dy.p, (size_t)T * 1024 * sizeof(f16)));
+    launch_hubert_posconv((const f16*)dx.p, 0, T, (const f16*)dw.p, (const float*)db.p, (f16*)dy.p, 0, e->compute);
+    return hb_down(e, (const f16*)dy.p, T, 1024, out);
+}
+
+int ltk_hubert_chunks_host(ltk_engine* e, const float* feat, int T, int batch, int first_row, int row_step, int rows, float* out) {
+    if (!e || !feat || !out || T <= 0 || batch <= 0 || rows <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    DevBuf st, dx, dy;
+    const int rc = hb_up(e, feat, T, 1024, &st, &dx);
+    if (rc) return rc;
+    const size_t cnt = (size_t)batch * rows * 1024;
+    CHK(hipMalloc(&dy.p, cnt * sizeof(float)));
+    launch_hubert_chunks((const f16*)dx.p, 0, T, batch, first_row, row_step, rows, (float*)dy.p, e->compute);
+    CHK(hipGetLastError());
+    CHK(hipStreamSynchronize(e->compute));
+    CHK(hipMemcpy(out, dy.p, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    return LTK_OK;
+}
+
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "../../include/ltk.h"
 #include "conv_mfma.h"
 #include "dw_kernels.h"
+#include "hubert_kernels.h"
 #include "misc_kernels.h"
 #include "musetalk.h"
 #include "nn_kernels.h"
@@ -298,6 +299,19 @@ struct ltk_engine {
     float* d_mt_feat = nullptr;           // staging: fp32 [max_frames][50][384]
     float* d_mt_lat = nullptr;            // staging for the host-input hook: fp32 [max_frames][8][32][32]
     std::map<int, std::shared_ptr<MtAvatar>> mt_avatars;
+    // HuBERT-large (Ultralight audio features): the packed weights once (hubert_w, never run), and one program per clip length over
+    // them, at most kHubertPrograms, the least recently used dropped (a live session has one length; offline calls add the
+    // 320 080-sample clip and a tail)
+    MtGraph* hubert_w = nullptr;
+    struct HubertProg { MtGraph* g = nullptr; int n_samples = 0; unsigned long stamp = 0; };
+    std::vector<HubertProg> hubert_progs;
+    MtGraph* hubert_last = nullptr;       // the program that ran last (debug read-back)
+    unsigned long hubert_clock = 0;
+    float* d_hpcm = nullptr;              // staging: the whole utterance, fp32
+    size_t hpcm_cap = 0;                  // samples
+    float* d_hstats = nullptr;            // [2] mean, variance
+    float* d_hrows = nullptr;             // staging: fp32 rows of one clip on their way to the host
+    size_t hrows_cap = 0;                 // rows
     // ultralight: per-avatar programs over ONE activation arena of ul_frames frames (grown by a register call that asks for more)
     std::map<int, std::shared_ptr<UlAvatar>> ul_avatars;
     f16* ul_buf[kUlBufs] = {nullptr};
@@ -481,6 +495,9 @@ int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, 
 double ul_macs_per_frame(const UlAvatar& a);
 void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
 void ul_unload(ltk_engine* e);                         // engine teardown
+constexpr size_t kHubertPrograms = 3;
+MtGraph* hubert_program(ltk_engine* e, int n_samples, int* rc);                                             // mt_engine.hip, under e->mu
+void hubert_unload(ltk_engine* e);
 int mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat_ptrs, int nf, const OutList64* outs, float* d_image_f32);
 
 }  // namespace ltk

@@ -1,4 +1,4 @@
-// MuseTalk (U-Net + VAE decoder), Whisper audio features and the VAE encoder: their entry points and run_program.
+// MuseTalk (U-Net + VAE decoder), Whisper and HuBERT audio features and the VAE encoder: their entry points and run_program.
 #include "engine_internal.h"
 
 extern "C" {
@@ -221,6 +221,183 @@ int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, 
             if (hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, "whisper kernels failed to launch");
         }
         return rc;
+    });
+}
+
+}  // extern "C"
+
+// ================================================================================ HuBERT-large audio features (Ultralight)
+// The program for clips of n_samples, built on first use over the engine's packed weights; at most kHubertPrograms are kept.  A dropped
+// program takes its captured graph with it (the graph holds its buffers' addresses, and the next program may land on the same one).
+MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
+    *rc = LTK_OK;
+    for (auto& p : e->hubert_progs)
+        if (p.n_samples == n_samples) { p.stamp = ++e->hubert_clock; return p.g; }
+    if (e->hubert_progs.size() >= kHubertPrograms) {
+        size_t v = 0;
+        for (size_t i = 1; i < e->hubert_progs.size(); ++i)
+            if (e->hubert_progs[i].stamp < e->hubert_progs[v].stamp) v = i;
+        MtGraph* old = e->hubert_progs[v].g;
+        (void)hipStreamSynchronize(e->compute);
+        for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
+            if (it->first.first != (const void*)old) { ++it; continue; }
+            if (it->second.exec) (void)hipGraphExecDestroy(it->second.exec);
+            it = e->prog_graphs.graphs.erase(it);
+        }
+        if (e->hubert_last == old) e->hubert_last = nullptr;
+        mt_graph_delete(old);
+        e->hubert_progs.erase(e->hubert_progs.begin() + v);
+    }
+    MtGraph* g = mt_graph_new();
+    mt_set_sat_counter(g, e->d_sat);
+    const int brc = mt_build_hubert_program(g, e->hubert_w, n_samples);
+    if (brc) {
+        *rc = fail(brc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, std::string("hubert: ") + mt_graph_error(g));
+        mt_graph_delete(g);
+        return nullptr;
+    }
+    ltk_engine::HubertProg p;
+    p.g = g; p.n_samples = n_samples; p.stamp = ++e->hubert_clock;
+    e->hubert_progs.push_back(p);
+    return g;
+}
+
+void ltk::hubert_unload(ltk_engine* e) {
+    for (auto& p : e->hubert_progs) mt_graph_delete(p.g);
+    e->hubert_progs.clear();
+    e->hubert_last = nullptr;
+    if (e->hubert_w) { mt_graph_delete(e->hubert_w); e->hubert_w = nullptr; }
+    if (e->d_hpcm) { (void)hipFree(e->d_hpcm); e->d_hpcm = nullptr; e->hpcm_cap = 0; }
+    if (e->d_hstats) { (void)hipFree(e->d_hstats); e->d_hstats = nullptr; }
+    if (e->d_hrows) { (void)hipFree(e->d_hrows); e->d_hrows = nullptr; e->hrows_cap = 0; }
+}
+
+namespace {
+
+constexpr int kHubertKernel = 400, kHubertStride = 320, kHubertClip = 320 * 1000;      // audio2feature.py:21-23
+
+// under e->mu: the utterance on the device and its statistics (Wav2Vec2FeatureExtractor normalises over the whole input)
+int hubert_upload(ltk_engine* e, const float* pcm, long long n, hipStream_t s) {
+    if ((size_t)n > e->hpcm_cap) {
+        CHK(hipStreamSynchronize(s));
+        if (e->d_hpcm) (void)hipFree(e->d_hpcm);
+        e->d_hpcm = nullptr; e->hpcm_cap = 0;
+        const size_t cap = std::max((size_t)n, (size_t)kHubertClip + 80);
+        CHK(hipMalloc((void**)&e->d_hpcm, cap * sizeof(float)));
+        e->hpcm_cap = cap;
+    }
+    CHK(hipMemcpyAsync(e->d_hpcm, pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    launch_hubert_stats(e->d_hpcm, n, e->d_hstats, s);
+    return LTK_OK;
+}
+
+// under e->mu: one forward of samples [off, off + len) of the uploaded utterance; *prog = the program that holds the result
+int hubert_forward(ltk_engine* e, long long off, int len, MtGraph** prog) {
+    int rc;
+    MtGraph* g = hubert_program(e, len, &rc);
+    if (!g) return rc;
+    launch_hubert_normalise(e->d_hpcm + off, len, e->d_hstats, mt_hubert_pcm_in(g), e->compute);
+    rc = run_program(e, g, 1);
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, std::string("hubert: ") + mt_graph_error(g));
+    e->hubert_last = g;
+    *prog = g;
+    return LTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ltk_hubert_load(ltk_engine* e, const ltk_named_tensor* sd, int n) {
+    if (!e || !sd || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->hubert_w) return fail(LTK_E_STATE, "a HuBERT model is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* wg = mt_graph_new();
+    if (mt_build_hubert_weights(wg, sd, n)) {
+        const std::string msg = mt_graph_error(wg);
+        mt_graph_delete(wg);
+        return fail(LTK_E_INVALID, "hubert: " + msg);
+    }
+    if (!e->d_hstats && hipMalloc((void**)&e->d_hstats, 2 * sizeof(float)) != hipSuccess) {
+        mt_graph_delete(wg);
+        return fail(LTK_E_NOMEM, "hubert: hipMalloc failed");
+    }
+    e->hubert_w = wg;
+    return LTK_OK;
+}
+
+int ltk_hubert_features(ltk_engine* e, const float* pcm, long long n_samples, float* out_host, int cap_rows, int* rows) {
+    if (!e || !pcm || !out_host || !rows || cap_rows <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (n_samples < kHubertKernel || n_samples > 0x7fffffffll) return fail(LTK_E_INVALID, "n_samples must be at least 400");
+    const int expected = (int)((n_samples - (kHubertKernel - kHubertStride)) / kHubertStride);
+    if (cap_rows < expected) return fail(LTK_E_INVALID, "out_host holds " + std::to_string(cap_rows) + " rows, " + std::to_string(expected) + " are needed");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    hipStream_t s = e->compute;
+    // every return below leaves nothing queued that still reads pcm or writes out_host
+    auto drained = [&](int code) { (void)hipStreamSynchronize(s); return code; };
+    int rc = hubert_upload(e, pcm, n_samples, s);
+    if (rc) return drained(rc);
+    // audio2feature.py:24-47: clips of 320 000 samples, each forwarded with the 80 samples behind it; then the tail if it has a kernel's length
+    std::vector<std::pair<long long, int>> clips;
+    const long long n_iter = n_samples / kHubertClip;
+    for (long long i = 0; i < n_iter; ++i)
+        clips.push_back({i * kHubertClip, (int)std::min<long long>(kHubertClip - kHubertStride + kHubertKernel, n_samples - i * kHubertClip)});
+    if (n_samples - n_iter * kHubertClip >= kHubertKernel) clips.push_back({n_iter * kHubertClip, (int)(n_samples - n_iter * kHubertClip)});
+    long long total = 0;
+    for (auto& c : clips) {
+        MtGraph* prog = nullptr;
+        rc = hubert_forward(e, c.first, c.second, &prog);
+        if (rc) break;
+        const int T = mt_hubert_rows(prog);
+        const int take = (int)std::max<long long>(0, std::min<long long>(T, expected - total));
+        if (take > 0) {
+            if ((size_t)T > e->hrows_cap) {
+                (void)hipStreamSynchronize(s);
+                if (e->d_hrows) (void)hipFree(e->d_hrows);
+                e->d_hrows = nullptr; e->hrows_cap = 0;
+                if (hipMalloc((void**)&e->d_hrows, (size_t)T * 1024 * sizeof(float)) != hipSuccess) { rc = fail(LTK_E_NOMEM, "hubert: hipMalloc failed"); break; }
+                e->hrows_cap = (size_t)T;
+            }
+            int cbt, cb0;
+            const f16* h = mt_hubert_out(prog, &cbt, &cb0);
+            launch_hubert_chunks(h, cb0, T, 1, 0, 0, take, e->d_hrows, s);
+            if (hipMemcpyAsync(out_host + (size_t)total * 1024, e->d_hrows, (size_t)take * 1024 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) {
+                rc = fail(LTK_E_HIP, "hubert: copy of the rows to the host failed"); break;
+            }
+        }
+        // d_hrows and a same-length program's buffers are reused by the next clip
+        if (hipStreamSynchronize(s) != hipSuccess) { rc = fail(LTK_E_HIP, "hubert: hipStreamSynchronize failed"); break; }
+        total += T;
+    }
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "hubert kernels failed to launch");
+    if (std::llabs(total - expected) > 1)
+        return fail(LTK_E_INVALID, "hubert: " + std::to_string(total) + " rows for " + std::to_string(expected) + " expected");
+    for (long long r = total; r < expected; ++r) memset(out_host + (size_t)r * 1024, 0, 1024 * sizeof(float));      // F.pad with zero rows
+    *rows = expected;
+    return LTK_OK;
+}
+
+int ltk_hubert_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out) {
+    if (!e || !pcm || !d_out || n_samples < kHubertKernel || n_samples >= kHubertClip || batch <= 0 || rows <= 0)
+        return fail(LTK_E_INVALID, "bad arguments (400 <= n_samples < 320000, batch and rows positive)");
+    CHK(enter_device(e->device));
+    return infer_call(e, nullptr, [&]() -> int {
+        if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+        hipStream_t s = e->compute;
+        int rc = hubert_upload(e, pcm, n_samples, s);
+        if (rc) return rc;
+        MtGraph* prog = nullptr;
+        rc = hubert_forward(e, 0, n_samples, &prog);
+        if (rc) return rc;
+        int cbt, cb0;
+        const f16* h = mt_hubert_out(prog, &cbt, &cb0);
+        launch_hubert_chunks(h, cb0, mt_hubert_rows(prog), batch, first_row, row_step, rows, (float*)d_out, s);
+        if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "hubert kernels failed to launch");
+        return LTK_OK;
     });
 }
 

@@ -45,5 +45,17 @@ int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* vae_sd, int n
 // Whisper encoder graph (one 30-s window per run): input log-mel tensor = mt_latent_in(), 5 hidden states
 int mt_build_whisper_graph(MtGraph* g, const ltk_named_tensor* encoder_sd, int n);
 f16* mt_whisper_state(MtGraph* g, int i, int* cbt, int* cb0);
+// HuBERT-large (hubert.hip): the packed weights live in ONE graph that is never run (mt_build_hubert_weights, from
+// HubertModel.state_dict() with the positional conv's weight norm already folded); a program for a clip of n_samples is built
+// over it and owns its activations only.  Input: the normalised fp32 waveform in mt_hubert_pcm_in(); output: last_hidden_state,
+// CB16 [64][rows][16].
+int hubert_rows(int n_samples);                 // rows HubertModel returns for a clip of n_samples (0: shorter than the receptive field)
+int mt_build_hubert_weights(MtGraph* g, const ltk_named_tensor* sd, int n);
+int mt_build_hubert_program(MtGraph* g, const MtGraph* weights, int n_samples);
+int mt_hubert_layers(const MtGraph* g);
+int mt_hubert_rows(const MtGraph* g);
+float* mt_hubert_pcm_in(MtGraph* g);
+f16* mt_hubert_out(MtGraph* g, int* cbt, int* cb0);
+size_t mt_activation_bytes(const MtGraph* g);
 
 }  // namespace ltk

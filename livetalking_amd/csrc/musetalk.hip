@@ -28,6 +28,7 @@
 #include "musetalk.h"
 #include "nn_kernels.h"
 #include "misc_kernels.h"
+#include "hubert_kernels.h"
 
 namespace ltk {
 
@@ -69,7 +70,7 @@ struct MtTensor {
     int P() const { return H * W; }
 };
 
-enum MtOpType { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_ADDPOS, OP_VT };
+enum MtOpType { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_ADDPOS, OP_VT, OP_HB_L0, OP_LNGELU, OP_POSCONV };
 
 struct MtOp {
     MtOpType type;
@@ -91,6 +92,7 @@ struct MtOp {
     float ln_eps = 1e-5f;
     int vt_buf = -1;            // OP_ATTN: the values are already transposed in this buffer (written by the pass's OP_VT), else the shared scratch
     long long gn_slot_off = -1; // OP_GN on a map gn_coop_kernel serves: first word of this op's exchange slots in MtGraph::gn_slots
+    int wvec = -1, bvec = -1;   // OP_HB_L0 / OP_POSCONV (hubert_kernels.hip): the op's own weights and bias in MtGraph::vecs
 };
 
 // one cross-attention's share of the hoisted k | v projection (MtGraph::kv_all): its value view and where the transposed values go
@@ -126,6 +128,14 @@ struct MtGraph {
     unsigned long long* sat_ctr = nullptr;    // debug (knob SAT_CHECK): saturation counters every op's output is scanned into
     MtTensor *t_latent = nullptr, *t_ctx = nullptr, *t_unet_out = nullptr, *t_vae_out = nullptr;
     MtTensor* whisper_states = nullptr;
+    // HuBERT (mt_build_hubert): one program per clip length over ONE set of packed weights.  `share` = the graph that owns them (it
+    // is built once per engine and never run); a graph with `share` set looks its plans and vectors up there by name, copies the
+    // handles and frees none of them.  plan_of / rplan_of / vec_of: what the owner offers.
+    const MtGraph* share = nullptr;
+    std::map<std::string, int> plan_of, rplan_of, vec_of;
+    int hb_layers = 0, hb_samples = 0, hb_rows = 0;
+    int hb_pcm_buf = -1;                      // fp32 [hb_samples]: the normalised waveform of the clip
+    MtTensor* hb_out = nullptr;               // last_hidden_state
 
     MtTensor alloc(int C, int H, int W) {
         MtTensor t;
@@ -156,6 +166,21 @@ struct MtGraph {
         vecs.push_back(d);
         return (int)vecs.size() - 1;
     }
+    // a vector the programs of one model share under `name` (host = null in a graph with `share` set)
+    int add_named_vec(const std::string& name, const void* host, size_t bytes) {
+        if (share) {
+            auto it = share->vec_of.find(name);
+            if (it == share->vec_of.end()) { err = "the shared weights have no " + name; return -1; }
+            vecs.push_back(share->vecs[it->second]);
+            return (int)vecs.size() - 1;
+        }
+        float* d = nullptr;
+        if (hipMalloc((void**)&d, bytes) != hipSuccess) { err = "hipMalloc failed"; return -1; }
+        (void)hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+        vecs.push_back(d);
+        vec_of[name] = (int)vecs.size() - 1;
+        return (int)vecs.size() - 1;
+    }
     // conv / linear: weight [Cout][Cin][k][k] fp32 host, bias [Cout] or null
     // `scale` (or null = 1): per-output-channel factor of the epilogue (the LayerNorm fold passes sum_ci W'[co][ci] here)
     int add_conv(const std::string& name, const float* w, const float* bias, int Cin, int Cout, int k, int stride, int pad,
@@ -179,6 +204,7 @@ struct MtGraph {
         const int k = kh, stride = sh;
         const int kk = kh * kw;
         (void)k;
+        if (share) return add_conv_shared(name, Cin, Cout, kh, kw, sh, x, y, res, act);
         const int CoutP = up16(Cout);
         const int CinR = Cin;
         Cin = up16(Cin);                    // whole channel blocks on both sides (zero weights for the padding)
@@ -234,6 +260,30 @@ struct MtGraph {
         if (res) op.r = *res;
         // act 4 = GEGLU in the epilogue (conv3_mfma.hip): the output is half as wide as the projection
         if (up16(Cin) != x.C || (act == 4 ? CoutP / 2 : CoutP) != y.C) { err = name + ": channel mismatch (" + std::to_string(Cin) + "->" + std::to_string(Cout) + ")"; return -1; }
+        ops.push_back(op);
+        named[name] = y;
+        plan_of[name] = op.plan;
+        if (op.rplan >= 0) rplan_of[name] = op.rplan;
+        return 0;
+    }
+    // add_conv2 over the packed weights of `share`: the plan handles are copied, the row-GEMM form taken where this graph's map
+    // is small enough for it (the owner was built at a length that has one for every linear layer)
+    int add_conv_shared(const std::string& name, int Cin, int Cout, int kh, int kw, int stride, const MtTensor& x, const MtTensor& y,
+                        const MtTensor* res, int act) {
+        auto it = share->plan_of.find(name);
+        if (it == share->plan_of.end()) { err = "the shared weights have no " + name; return -1; }
+        plans.push_back(share->plans[it->second]);
+        macs += (double)Cin * Cout * kh * kw * y.P();
+        MtOp op;
+        op.type = OP_CONV; op.name = name; op.x = x; op.y = y; op.plan = (int)plans.size() - 1; op.act = act;
+        auto rt = share->rplan_of.find(name);
+        if (rt != share->rplan_of.end() && act == 0 && stride == 1 && kh == 1 && kw == 1 && x.P() <= 64 && x.P() == y.P()) {
+            rplans.push_back(share->rplans[rt->second]);
+            op.rplan = (int)rplans.size() - 1;
+            op.ksz = kh;
+        }
+        if (res) op.r = *res;
+        if (up16(Cin) != x.C || up16(Cout) != y.C) { err = name + ": channel mismatch (" + std::to_string(Cin) + "->" + std::to_string(Cout) + ")"; return -1; }
         ops.push_back(op);
         named[name] = y;
         return 0;
@@ -962,9 +1012,11 @@ int mt_graph_alloc(MtGraph& g, int frames) {
 
 void mt_graph_free(MtGraph& g) {
     for (f16* b : g.bufs) if (b) (void)hipFree(b);
-    for (ConvPlan& p : g.plans) conv_plan_destroy(&p);
-    for (RowGemmPlan& p : g.rplans) rowgemm_plan_destroy(&p);
-    for (float* v : g.vecs) if (v) (void)hipFree(v);
+    if (!g.share) {                                   // a graph over shared weights holds copies of the owner's handles
+        for (ConvPlan& p : g.plans) conv_plan_destroy(&p);
+        for (RowGemmPlan& p : g.rplans) rowgemm_plan_destroy(&p);
+        for (float* v : g.vecs) if (v) (void)hipFree(v);
+    }
     if (g.gn_partial) (void)hipFree(g.gn_partial);
     if (g.gn_slots) (void)hipFree(g.gn_slots);
     if (g.gn_err_host) (void)hipHostFree(g.gn_err_host);
@@ -1067,6 +1119,18 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
         case OP_ADDPOS:
             launch_add_pos(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.P(), g.vecs[op.gamma], s);
             break;
+        case OP_HB_L0:
+            launch_hubert_layer0(reinterpret_cast<const float*>(g.bufs[g.hb_pcm_buf]), g.hb_samples, g.vecs[op.wvec], g.vecs[op.bvec],
+                                 g.vecs[op.gamma], g.vecs[op.beta], op.eps, g.bufs[op.y.buf], s);
+            break;
+        case OP_LNGELU:
+            launch_ln_gelu512(g.bufs[op.x.buf], op.x.coff / 16, op.x.P(), op.eps, g.vecs[op.gamma], g.vecs[op.beta], g.bufs[op.y.buf],
+                              op.y.coff / 16, s);
+            break;
+        case OP_POSCONV:
+            launch_hubert_posconv(g.bufs[op.x.buf], op.x.coff / 16, op.x.P(), reinterpret_cast<const f16*>(g.vecs[op.wvec]), g.vecs[op.bvec],
+                                  g.bufs[op.y.buf], op.y.coff / 16, s);
+            break;
         case OP_GEGLU:
             launch_geglu(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.y.C, op.x.P(), g.bufs[op.y.buf], op.y.ld / 16,
                          op.y.coff / 16, s);
@@ -1126,6 +1190,7 @@ void mt_graph_delete(MtGraph* g) {
     mt_graph_free(*g);
     delete g->t_latent; delete g->t_ctx; delete g->t_unet_out; delete g->t_vae_out;
     delete[] g->whisper_states;
+    delete g->hb_out;
     delete g;
 }
 const char* mt_graph_error(const MtGraph* g) { return g->err.c_str(); }
@@ -1180,3 +1245,6 @@ int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* sd, int n, in
 double mt_macs_per_frame(const MtGraph* g) { return g->macs; }
 
 }  // namespace ltk
+
+#include "hubert_kernels.hip"      // the kernels only HuBERT-large needs
+#include "hubert.hip"              // mt_build_hubert and its wrappers: the HuBERT-large program over MtGraph

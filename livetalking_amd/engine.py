@@ -387,6 +387,104 @@ class Engine:
         _lib.check(self._lib.ltk_whisper_debug_get(self._h, name.encode(), out.ctypes.data, out.size))
         return out
 
+    # ------------------------------------------------------------------ hubert audio features (Ultralight)
+    @staticmethod
+    def fold_hubert_weight_norm(state_dict: Dict[str, object]) -> Dict[str, np.ndarray]:
+        """HubertModel.state_dict() -> the names ltk_hubert_load takes: the positional conv's weight norm folded into
+        "encoder.pos_conv_embed.conv.weight" = g * v / ||v||, the norm over dims (0, 1) for every tap (weight_norm(conv, dim=2)).
+        Both spellings are accepted: parametrizations.weight.original0 / original1 and weight_g / weight_v; a state dict that already
+        has the folded weight passes through."""
+        p = "encoder.pos_conv_embed.conv."
+        pairs = ((p + "parametrizations.weight.original0", p + "parametrizations.weight.original1"), (p + "weight_g", p + "weight_v"))
+        sd = {k: v for k, v in state_dict.items() if k != "masked_spec_embed"}
+        for gk, vk in pairs:
+            if gk in sd and vk in sd:
+                g = _as_f32(sd.pop(gk)).astype(np.float64)
+                v = _as_f32(sd.pop(vk)).astype(np.float64)
+                norm = np.sqrt((v * v).sum(axis=(0, 1), keepdims=True))
+                sd[p + "weight"] = (g.reshape(1, 1, -1) * v / norm).astype(np.float32)
+        if p + "weight" not in sd:
+            raise KeyError("state_dict has neither the positional conv's weight-norm pair (either spelling) nor its folded weight")
+        return sd
+
+    def load_hubert(self, state_dict: Dict[str, object]):
+        """avatars/ultralight/audio2feature.py:9-11: `state_dict` = HubertModel.from_pretrained(...).state_dict()."""
+        arr, n, keep = self._named_tensors(self.fold_hubert_weight_norm(state_dict))
+        _lib.check(self._lib.ltk_hubert_load(self._h, arr, n))
+        del keep
+
+    def hubert_features(self, pcm: np.ndarray) -> np.ndarray:
+        """get_hubert_from_16k_speech: 16 kHz float pcm -> float32 ((n - 80) // 320, 1024) on the host."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        expected = max((pcm.shape[0] - 80) // 320, 1)
+        out = np.empty((expected, 1024), dtype=np.float32)
+        rows = C.c_int()
+        _lib.check(self._lib.ltk_hubert_features(self._h, pcm.ctypes.data, pcm.shape[0], out.ctypes.data, expected, C.byref(rows)))
+        return out[: rows.value]
+
+    def hubert_step(self, pcm: np.ndarray, batch: int, first_row: int, d_out_ptr: int, row_step: int = 2, rows: int = 16):
+        """One forward of the step's pcm and the chunk gather into device float32 [batch][rows][1024] at d_out_ptr."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        _lib.check(self._lib.ltk_hubert_step(self._h, pcm.ctypes.data, pcm.shape[0], int(batch), int(first_row), int(row_step), int(rows),
+                                             C.c_void_p(d_out_ptr)))
+
+    def hubert_debug_get(self, name: str, shape) -> np.ndarray:
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_debug_get(self._h, name.encode(), out.ctypes.data, out.size))
+        return out
+
+    def hubert_ops(self):
+        """[(name, type)] of a HuBERT program; type as musetalk_ops(), and 7 conv layer 0 + LayerNorm + GELU, 8 LayerNorm + GELU,
+        9 positional conv."""
+        out = []
+        for i in range(self._lib.ltk_hubert_op_count(self._h)):
+            buf, t = C.create_string_buffer(160), C.c_int()
+            _lib.check(self._lib.ltk_hubert_op_name(self._h, i, buf, 160, C.byref(t)))
+            out.append((buf.value.decode(), t.value))
+        return out
+
+    def hubert_info(self) -> dict:
+        layers, progs, act = C.c_int(), C.c_int(), C.c_size_t()
+        _lib.check(self._lib.ltk_hubert_info(self._h, C.byref(layers), C.byref(progs), C.byref(act)))
+        return {"layers": layers.value, "programs": progs.value, "activation_bytes": int(act.value)}
+
+    # the HuBERT kernels on their own (include/ltk.h: unit-test hooks); token-major in, token-major out
+    def hubert_stats(self, pcm: np.ndarray):
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+        out = np.empty(2, dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_stats(self._h, pcm.ctypes.data, pcm.shape[0], out.ctypes.data))
+        return float(out[0]), float(out[1])
+
+    def hubert_layer0(self, x, w, bias, gamma, beta) -> np.ndarray:
+        x, w, bias, gamma, beta = (np.ascontiguousarray(a, dtype=np.float32) for a in (x, w, bias, gamma, beta))
+        assert w.size == 5120 and bias.size == gamma.size == beta.size == 512
+        out = np.empty((512, (x.size - 10) // 5 + 1), dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_layer0_host(self._h, x.ctypes.data, x.size, w.ctypes.data, bias.ctypes.data, gamma.ctypes.data,
+                                                    beta.ctypes.data, out.ctypes.data))
+        return np.ascontiguousarray(out.T)
+
+    def hubert_ln_gelu(self, x, gamma, beta) -> np.ndarray:
+        x, gamma, beta = (np.ascontiguousarray(a, dtype=np.float32) for a in (x, gamma, beta))
+        assert x.ndim == 2 and x.shape[1] == 512
+        out = np.empty((512, x.shape[0]), dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_ln_gelu_host(self._h, x.ctypes.data, x.shape[0], gamma.ctypes.data, beta.ctypes.data, out.ctypes.data))
+        return np.ascontiguousarray(out.T)
+
+    def hubert_posconv(self, x, w, bias) -> np.ndarray:
+        x, w, bias = (np.ascontiguousarray(a, dtype=np.float32) for a in (x, w, bias))
+        assert x.ndim == 2 and x.shape[1] == 1024 and w.shape == (1024, 64, 128) and bias.size == 1024
+        out = np.empty((1024, x.shape[0]), dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_posconv_host(self._h, x.ctypes.data, x.shape[0], w.ctypes.data, bias.ctypes.data, out.ctypes.data))
+        return np.ascontiguousarray(out.T)
+
+    def hubert_chunks(self, feat, batch: int, first_row: int, row_step: int = 2, rows: int = 16) -> np.ndarray:
+        feat = np.ascontiguousarray(feat, dtype=np.float32)
+        assert feat.ndim == 2 and feat.shape[1] == 1024
+        out = np.empty((batch, rows, 1024), dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_chunks_host(self._h, feat.ctypes.data, feat.shape[0], int(batch), int(first_row), int(row_step),
+                                                    int(rows), out.ctypes.data))
+        return out
+
     # ------------------------------------------------------------------ test / measurement hooks
     def wav2lip_forward_host(self, mel: np.ndarray, face6: np.ndarray) -> np.ndarray:
         mel = np.ascontiguousarray(mel, dtype=np.float32).reshape(-1, 80, 16)
