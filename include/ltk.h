@@ -341,6 +341,11 @@ int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6
  * under its state_dict prefix for ltk_debug_get ("inc.inconv.0.conv.0", "down1.maxpool_conv.0.double_conv.1.conv.6", "audio_model.conv3",
  * "up1.up", "outc.conv", ...): a conv's tap is the tensor after its BatchNorm, ReLU and residual add. */
 int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6, const float* feat, int B, float* pred);
+/* the launches of an Ultralight avatar's program in execution order: the tap name of each (as ltk_ultralight_forward_host lists them,
+ * and "audio_feat", the packed feature chunk) and its type: 0 dense conv (as ltk_musetalk_op_name), 10 depthwise conv, 11 upsample,
+ * 12 input conv, 13 feature pack, 14 head */
+int ltk_ultralight_op_count(ltk_engine* e, int avatar_id);
+int ltk_ultralight_op_name(ltk_engine* e, int avatar_id, int op, char* buf, int buf_len, int* type);
 /* average milliseconds of one pass of `frames` frames as ltk_ultralight_infer enqueues it (replayed graph under knob GRAPH), on
  * dummy inputs, and the MACs (dense + depthwise + head) it executes */
 int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, float* ms_per_pass, double* macs_per_pass);

@@ -89,6 +89,8 @@ SYMBOLS = {
     "ltk_hubert_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ltk_hubert_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ltk_ultralight_op_count": (C.c_int, [C.c_void_p, C.c_int]),
+    "ltk_ultralight_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_op_count": (C.c_int, [C.c_void_p]),
     "ltk_hubert_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),

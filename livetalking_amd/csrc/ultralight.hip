@@ -449,6 +449,22 @@ int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* 
     });
 }
 
+int ltk_ultralight_op_count(ltk_engine* e, int avatar_id) {
+    if (!e) return 0;
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
+    return ap && ap->prog ? (int)ap->prog->ops.size() : 0;
+}
+
+int ltk_ultralight_op_name(ltk_engine* e, int avatar_id, int op, char* buf, int buf_len, int* type) {
+    if (!e || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
+    if (!ap || !ap->prog) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    if (op < 0 || op >= (int)ap->prog->ops.size()) return fail(LTK_E_INVALID, "no such op");
+    snprintf(buf, (size_t)buf_len, "%s", ap->prog->ops[op].name.c_str());
+    if (type) *type = ap->prog->ops[op].type == UL_CONV ? 0 : 9 + ap->prog->ops[op].type;      // 0 as ltk_musetalk_op_name; 10.. its own
+    return LTK_OK;
+}
+
 int ltk_ultralight_paste_back(ltk_engine* e, int avatar_id, int idx, const void* d_pred, void* out, int out_is_device, void* stream) {
     if (!e || !d_pred || !out) return fail(LTK_E_INVALID, "bad arguments");
     const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);

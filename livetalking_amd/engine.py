@@ -246,6 +246,17 @@ class Engine:
         _lib.check(self._lib.ltk_ultralight_forward_host(self._h, int(avatar_id), img6.ctypes.data, feat.ctypes.data, B, pred.ctypes.data))
         return pred
 
+    def ultralight_ops(self, avatar_id: int):
+        """[(tap name, type)] of the avatar's launch program in execution order; type 0 dense conv (as musetalk_ops()), 10 depthwise
+        conv, 11 upsample, 12 input conv, 13 feature pack, 14 head."""
+        out = []
+        buf = C.create_string_buffer(160)
+        t = C.c_int()
+        for i in range(self._lib.ltk_ultralight_op_count(self._h, int(avatar_id))):
+            _lib.check(self._lib.ltk_ultralight_op_name(self._h, int(avatar_id), i, buf, 160, C.byref(t)))
+            out.append((buf.value.decode(), t.value))
+        return out
+
     def ultralight_time(self, avatar_id: int, frames: int, iters: int):
         ms = C.c_float()
         macs = C.c_double()

@@ -1,4 +1,5 @@
-"""Teacher-forced, op-by-op replay of the MuseTalk program (U-Net + VAE decoder) of the Wav2Lip program and of the Whisper encoder against float64.
+"""Teacher-forced, op-by-op replay of the MuseTalk program (U-Net + VAE decoder) of the Wav2Lip program, of the Whisper encoder and of the
+Ultralight program (its restatement and replay_ultralight live in tests/ultralight_ref.py) against float64.
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py); CPU code.
 
@@ -28,11 +29,22 @@ op's error and nothing upstream.  Beside `ref` the replay evaluates, in float32 
                           error of 2^-25 and more however small Phi is (the sum cancels in the negative tail), so a gelu(g) has
                           |a| |g| 2^-25 that no bound relative to |ref| covers;  in the projection's epilogue (the projection is never rounded): first-order
                           propagation of the projection's own bound, A = A_a |gelu(g)| + |a| |gelu'(g)| A_g with c = 2^-12, plus 2^-10 |ref|.
+        Ultralight (csrc/ultralight.hip, csrc/dw_kernels.hip; the ops of tests/ultralight_ref.py):
+        dense conv        the Wav2Lip layer's form (fp16 weights, BatchNorm + conv bias as an fp32 scale / shift in the epilogue) with the
+                          residual added BEHIND the affine, never folded into a tap, and a ReLU only where the op has one:
+                          A = short_sum(n) |W| (*) |x| |scale| + 4 |shift| + 4 |res|,  c = 2^-12,  s = 2^-24 sum |x| |scale|;
+        depthwise 3x3     weights, scale and shift stay fp32: no weight rounding in the model; 9 fp32 FMAs, the affine, one rounding:
+                          A = |w| (*) |x| |scale| + |shift|,  c = 2^-20,  s = 2^-24;  the same form for inc.inconv.0.conv.0 (ul_in_kernel:
+                          6 fp32 products on the float32 input);
+        upsample          evaluated in float64 on the device, one rounding: 2^-10 |ref| + 2^-24;
+        audio_feat        one fp32 -> fp16 rounding; beyond the bound the device's tensor has to EQUAL f16(input) (record "inexact");
+        outc.conv         fp32 throughout: the Wav2Lip head's bound.
         The leading 2^-10 |ref| is the output's own rounding to fp16 (2^-11) with a factor 2 of room; every bound also gets 2^-24
         absolute, the same for an output in fp16's subnormal range (spacing 2^-24).
 
 Gates (failures()):
   per element : |dev - ref| <= tol, no violator allowed (not for the fp8 convs: e4m3 operands make c = 2^-3, which says nothing);
+  exact       : an op whose model is exact (audio_feat) has to equal it;
   aggregate   : rel_l2(dev, ref) <= 2 * rel_l2(mod, ref) + 1e-4.
   The model itself has to sit inside the bound: max |mod - ref| / tol <= 0.5 (tests/test_op_replay.py).
 
@@ -57,6 +69,8 @@ AGG_FACTOR = 2.0
 AGG_FLOOR = 1e-4
 MODEL_HEADROOM = 0.5
 GELU_SLOPE = 1.13           # max |gelu'(x)| = 1.129 (at x = sqrt 2)
+C_F32 = 2.0 ** -20          # a short fp32 sum (<= 9 FMAs and an affine): 16 roundings of 2^-24
+EXACT_KINDS = ("ul_feat",)  # ops whose rounding model the device has to equal
 F16_FLOOR = 2.0 ** -24      # fp16 output below 2^-14 is subnormal: its rounding error is up to 2^-25 absolute, whatever |ref| is
 
 
@@ -187,6 +201,8 @@ class Replay:
                 mod, tol, elementwise = self.model(name, op, ref)
                 tol = tol + F16_FLOOR
             self.record(name, dev, ref, mod, tol, elementwise)
+            if op["kind"] in EXACT_KINDS:
+                self.records[-1]["inexact"] = int((dev.double() != mod.double()).sum())
         return dev
 
     # -- bookkeeping
@@ -347,17 +363,64 @@ class Replay:
                 tol = 2.0 ** -9 * ref.abs() + _tok_to_nchw(2.0 ** -23 * (a * g).abs(), op.get("hw"))
         elif kind == "w2l":
             mod, tol = self._w2l_layer(op, ref)
-        elif kind == "w2l_head":
+        elif kind in ("w2l_head", "ul_head"):
             # fp32 weights, fp32 sigmoid, fp32 result: no fp16 rounding anywhere; the bound is the conv's own through the slope of the sigmoid
+            mod, tol = self.head(op["x"].float(), op.get("p", "output_block.1"), ref)
+        elif kind == "ul_conv":
+            mod, tol = self._ul_conv(op, ref)
+        elif kind in ("ul_dw", "ul_in"):
+            # fp32 weights and fp32 affine (ul_in: on the float32 input): FMAs in fp32, ReLU, one rounding to fp16
             x = op["x"].float()
-            W, b = self.sd["output_block.1.weight"].float(), self.sd["output_block.1.bias"].float()
-            z = F.conv2d(x, W, b)
-            mod = torch.sigmoid(z)
-            A = F.conv2d(x.abs(), W.abs()) + 4 * b.abs()[None, :, None, None]
-            tol = 2.0 ** -10 * ref.abs() + C_LIN * A * (mod * (1 - mod))
+            W = self.sd[op["p"] + ".weight"].float()
+            sc, sf = self._bn_fold(op["bn"], None)
+            kw = dict(stride=op["stride"], padding=1, groups=W.shape[0]) if kind == "ul_dw" else {}
+            v = lambda t: t[None, :, None, None]
+            mod = f16(F.relu(F.conv2d(x, W, None, **kw) * v(sc) + v(sf)))
+            tol = 2.0 ** -10 * ref.abs() + C_F32 * (F.conv2d(x.abs(), W.abs(), None, **kw) * v(sc.abs()) + v(sf.abs())) + 2.0 ** -24
+        elif kind == "ul_up":
+            # the kernel interpolates in float64 from exact integer quotients: the result is float64's, rounded once
+            mod = f16(F.interpolate(op["x"].double(), scale_factor=2, mode="bilinear", align_corners=True))
+            tol = 2.0 ** -10 * ref.abs() + 2.0 ** -24
+        elif kind == "ul_feat":
+            mod = f16(op["x"].float())
+            tol = 2.0 ** -10 * ref.abs()
         else:
             raise ValueError(kind)
         return mod, tol, elementwise
+
+    def head(self, x, p, ref):
+        """-> (mod, tol) of a 1x1 conv + sigmoid that stays fp32 (Wav2Lip's output_block.1, Ultralight's outc.conv); tol without F16_FLOOR."""
+        W, b = self.sd[p + ".weight"].float(), self.sd[p + ".bias"].float()
+        mod = torch.sigmoid(F.conv2d(x, W, b))
+        A = F.conv2d(x.abs(), W.abs()) + 4 * b.abs()[None, :, None, None]
+        return mod, 2.0 ** -10 * ref.abs() + C_LIN * A * (mod * (1 - mod))
+
+    def _bn_fold(self, bn, bias):
+        """BatchNorm2d (eval, eps 1e-5) and the conv's bias as the fp32 scale / shift csrc/ultralight.hip fold_bn computes."""
+        sd = self.sd
+        sc = sd[bn + ".weight"].float() / torch.sqrt(sd[bn + ".running_var"].float() + 1e-5)
+        b = bias.float() if bias is not None else 0.0
+        return sc, (b - sd[bn + ".running_mean"].float()) * sc + sd[bn + ".bias"].float()
+
+    def _ul_conv(self, op, ref):
+        """A dense conv of the Ultralight program (1x1 expand / project, the two biased 3x3 audio convs) as conv_plan_create packs it:
+        fp16 weights, fp32 scale / shift, the residual added behind them, ReLU where the op has one, one rounding to fp16."""
+        p = op["p"]
+        x = op["x"].float()
+        W = self.sd[p + ".weight"].float()
+        sc, sf = self._bn_fold(op["bn"], self.sd.get(p + ".bias"))
+        k = W.shape[-1]
+        kw = dict(stride=op["stride"], padding=op["pad"])
+        v = lambda t: t[None, :, None, None]
+        acc = F.conv2d(x, f16(W), None, **kw) * v(sc) + v(sf)
+        A = short_sum(W.shape[1] * k * k) * F.conv2d(x.abs(), W.abs(), None, **kw) * v(sc.abs()) + 4 * v(sf.abs())
+        s = F.conv2d(x.abs().sum(1, keepdim=True), torch.ones(1, 1, k, k), None, **kw) * v(sc.abs())
+        if op.get("res") is not None:
+            r = op["res"].float()
+            acc = acc + r
+            A = A + 4 * r.abs()
+        mod = f16(F.relu(acc) if op["relu"] else acc)
+        return mod, 2.0 ** -10 * ref.abs() + C_LIN * A + 2.0 ** -24 * s
 
     def _w2l_layer(self, op, ref):
         """A Wav2Lip Conv2d / ConvTranspose2d block as csrc/w2l_program.hip packs it: fp16 weights, BatchNorm (eval) as an fp32
@@ -407,6 +470,8 @@ def failures(records: List[dict], model_too: bool = False) -> List[str]:
         why = []
         if r["elementwise"] and r["violators"]:
             why.append(f"{r['violators']} of {r['n']} elements outside the bound, worst |dev - ref| / tol = {r['dev_over_tol']:.2f} at flat index {r['worst_index']}")
+        if r.get("inexact"):
+            why.append(f"{r['inexact']} of {r['n']} elements differ from the op's exact model")
         if not (r["rel_dev"] <= AGG_FACTOR * r["rel_mod"] + AGG_FLOOR):
             why.append(f"rel_l2(dev, ref) = {r['rel_dev']:.3e} > 2 * rel_l2(mod, ref) + 1e-4 = {AGG_FACTOR * r['rel_mod'] + AGG_FLOOR:.3e}")
         if model_too and r["elementwise"] and (r["mod_violators"] or r["mod_over_tol"] > MODEL_HEADROOM):
@@ -530,11 +595,13 @@ def engine_fetch(eng, frames_total: int, frames: Optional[List[int]] = None):
 class SimDevice:
     """A stand-in for the device that the CPU tests replay against: the float32 oracle with fp16 weights whose every op output is
     rounded to fp16 and kept under the op's name.  `fused`: the names a fused program would not materialise (not rounded, not
-    kept).  `mutate`: name -> fn(t, op) applied to that op's output before the rounding - the faults the replay has to find."""
+    kept).  `mutate`: name -> fn(t, op) applied to that op's output before the rounding - the faults the replay has to find.
+    `fp32`: the names whose output the device keeps in fp32 (not rounded)."""
 
-    def __init__(self, fused=(), mutate=None):
+    def __init__(self, fused=(), mutate=None, fp32=()):
         self.t: Dict[str, Tensor] = {}
         self.fused = set(fused)
+        self.fp32 = set(fp32)
         self.mutate = mutate or {}
         self.ops = {}
 
@@ -547,7 +614,7 @@ class SimDevice:
             return None
         if name in self.mutate:
             t = self.mutate[name](t, op)
-        t = f16(t)
+        t = t if name in self.fp32 else f16(t)
         self.t[name] = t.clone()
         return t
 

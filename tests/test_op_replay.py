@@ -4,7 +4,8 @@ A SIMULATED device - the float32 oracle with fp16 weights whose every op output 
   * it passes every gate, U-Net + VAE decoder at B = 1 with the default program's fusions (LayerNorms, GEGLU projection not
     materialised), and the rounding model alone stays inside half the bound for every op (0 violators, max |mod - ref| / tol <= 0.5);
   * six faults planted into it are each found, and the failure names the faulty op and no other;
-  * the coverage walk fails when a name is missing from the compared set.
+  * the coverage walk fails when a name is missing from the compared set;
+  * the Ultralight program (tests/ultralight_ref.py, 86 ops) the same way at B = 1 and B = 2, with eight planted faults (bottom of the file).
 Measured (synthetic draw of synth_inputs): largest |mod - ref| / tol over the 422 ops of the full pass 0.42 (gate 0.5), the bound is
 0.3 % of the output's rms (median over ops).  The tanh-GELU fault (e), the subtle one, passes the aggregate gate (rel_l2 2.9e-4
 against the model's 2.1e-4) and is caught per element: 40 259 of 655 360 elements outside the bound, worst |dev - ref| / tol 102.
@@ -283,3 +284,134 @@ def test_whisper_restatement_equals_transformers_and_one_simulated_layer():
     r = rec["layers.0.fc1"]
     print(f"[op replay] tanh-GELU in fc1's epilogue: worst |dev - ref| / tol {r['dev_over_tol']:.2f}, rel_l2 {r['rel_dev']:.3e} against the model's {r['rel_mod']:.3e}")
     assert not [b for b in bad if not b.startswith("layers.0.fc1: ")]
+
+
+# ------------------------------------------------------------------------------------------------ Ultralight
+import ultralight_ref as U  # noqa: E402
+
+UL_DW = "down1.maxpool_conv.0.double_conv.0.conv.3"
+
+
+class _SimUL(R.SimDevice):
+    """The float32 restatement as the device computes it: fp16 weights for the dense convs (the state dict it is run on), fp32 for
+    the depthwise convs, inc.inconv.0.conv.0 and outc.conv, the upsample evaluated in float64 (upsample2x_kernel), every output
+    rounded to fp16 but outc.conv's."""
+
+    def __init__(self, mutate=None):
+        super().__init__(mutate=mutate, fp32=("outc.conv",))
+
+    def __call__(self, name, t):
+        if name.endswith(".up") and name not in self.mutate:
+            t = F.interpolate(self.ops[name]["x"].double(), scale_factor=2, mode="bilinear", align_corners=True).float()
+        return super().__call__(name, t)
+
+
+@pytest.fixture(scope="module")
+def ul():
+    sd = synth.ultralight_state_dict(1234)
+    dense = lambda k, v: k.endswith(".weight") and v.ndim == 4 and v.shape[1] > 1 and k not in ("inc.inconv.0.conv.0.weight", "outc.conv.weight")
+    sim_sd = {k: (v.astype(np.float16).astype(np.float32) if dense(k, v) else v) for k, v in sd.items()}
+    assert sum(dense(k, v) for k, v in sd.items()) == 81 - 26 - 2          # 26 depthwise convs, the input conv and the head stay fp32
+    return sd, sim_sd
+
+
+def _ul_records(ul, B, mutate=None):
+    sd, sim_sd = ul
+    img6, feat = synth.ultralight_inputs(B, 1234)
+    sim = _SimUL(mutate)
+    U.forward(sim_sd, img6, feat, dtype=torch.float32, force=sim)
+    rp = U.replay_ultralight(sd, img6, feat, sim.fetch)
+    assert [r["name"] for r in rp.records] == U.op_names() and len(rp.records) == 86          # 81 convs, 4 upsamples, audio_feat
+    return rp.records
+
+
+@pytest.mark.parametrize("B", [1, 2])
+def test_ultralight_simulated_device_passes_every_gate(ul, B):
+    """Measured: largest |mod - ref| / tol 0.4997 (the upsamples and audio_feat: one fp16 rounding, 2^-11, against 2^-10 |ref|),
+    0.43 over the dense convs (down4.maxpool_conv.0.double_conv.0.conv.6)."""
+    rec = _ul_records(ul, B)
+    worst = max(rec, key=lambda r: r["mod_over_tol"])
+    dense = max((r for r in rec if r["name"].endswith((".conv.0", ".conv.6", "conv3", "conv5")) and r["name"] != "inc.inconv.0.conv.0"),
+                key=lambda r: r["mod_over_tol"])
+    print(f"[op replay] ultralight B={B}: {len(rec)} ops; largest |mod - ref| / tol {worst['mod_over_tol']:.4f} ({worst['name']}), "
+          f"dense convs {dense['mod_over_tol']:.2f} ({dense['name']})")
+    bad = R.failures(rec, model_too=True)
+    assert not bad, "\n".join(bad)
+    names = [r["name"] for r in rec]
+    ops = [(n, 0) for n in U.op_names()]
+    assert R.uncovered(ops, names, {}) == []
+    assert R.uncovered(ops, [n for n in names if n != "up3.up"], {}) == ["up3.up"]
+
+
+def _bn(sd, bn, y):
+    v = lambda k: torch.from_numpy(sd[bn + k])[None, :, None, None]
+    return (y - v(".running_mean")) / torch.sqrt(v(".running_var") + U.BN_EPS) * v(".weight") + v(".bias")
+
+
+def _ul_only(ul, B, name, fn):
+    _only(R.failures(_ul_records(ul, B, {name: fn}), model_too=True), name)
+
+
+def test_ultralight_fault_1_depthwise_pads_with_the_clamped_edge(ul):
+    sd = ul[1]
+
+    def f(t, op):
+        w = torch.from_numpy(sd[UL_DW + ".weight"])
+        y = F.conv2d(F.pad(op["x"], (1, 1, 1, 1), mode="replicate"), w, stride=2, groups=w.shape[0])
+        return F.relu(_bn(sd, op["bn"], y))
+    _ul_only(ul, 1, UL_DW, f)
+
+
+def test_ultralight_fault_2_depthwise_stride_2_sampled_without_the_padding_offset(ul):
+    sd = ul[1]
+
+    def f(t, op):                              # ix = 2 ox + kx: padding 0, the map padded at the far edge to keep the size
+        w = torch.from_numpy(sd[UL_DW + ".weight"])
+        y = F.conv2d(F.pad(op["x"], (0, 2, 0, 2)), w, stride=2, groups=w.shape[0])
+        assert y.shape == t.shape
+        return F.relu(_bn(sd, op["bn"], y))
+    _ul_only(ul, 1, UL_DW, f)
+
+
+def test_ultralight_fault_3_upsample_without_align_corners(ul):
+    _ul_only(ul, 1, "up2.up", lambda t, op: F.interpolate(op["x"], scale_factor=2, mode="bilinear", align_corners=False))
+
+
+def test_ultralight_fault_4_project_conv_loses_its_residual(ul):
+    _ul_only(ul, 1, "fuse_conv.0.double_conv.1.conv.6", lambda t, op: t - op["res"])
+
+
+def test_ultralight_fault_5_residual_from_the_neighbouring_channel_block(ul):
+    _ul_only(ul, 1, "down2.maxpool_conv.0.double_conv.1.conv.6", lambda t, op: t - op["res"] + torch.roll(op["res"], 16, dims=1))
+
+
+def test_ultralight_fault_6_conv5_outer_ring_as_if_the_padding_were_1(ul):
+    sd = ul[1]
+
+    def f(t, op):                              # iy = 2 oy - 1 + ky on the ring (zeros beyond the 16 x 16 map), 2 oy - 3 + ky inside
+        w, b = torch.from_numpy(sd["audio_model.conv5.weight"]), torch.from_numpy(sd["audio_model.conv5.bias"])
+        y = F.relu(_bn(sd, op["bn"], F.conv2d(F.pad(op["x"], (1, 5, 1, 5)), w, b, stride=2)))
+        assert y.shape == t.shape == (1, 512, 10, 10)
+        y[:, :, 1:-1, 1:-1] = t[:, :, 1:-1, 1:-1]
+        return y
+    _ul_only(ul, 1, "audio_model.conv5", f)
+
+
+def test_ultralight_fault_7_stale_ragged_last_tile_at_b2(ul):
+    """200 rows (2 frames x 100 pixels) in tiles of 128: rows 128..199 - frame 1, pixels 28..99 - keep frame 0's values."""
+    def f(t, op):
+        t = t.clone()
+        t[1].reshape(t.shape[1], 100)[:, 28:] = t[0].reshape(t.shape[1], 100)[:, 28:]
+        return t
+    _ul_only(ul, 2, "down4.maxpool_conv.0.double_conv.0.conv.6", f)
+
+
+def test_ultralight_fault_8_mask_rectangle_one_row_short(ul):
+    sd = ul[1]
+
+    def f(t, op):                              # y = 149, the last masked row, keeps the image
+        x = op["x"].clone()
+        x[:, 3:, 149, 5:155] = x[:, :3, 149, 5:155]
+        y = F.conv2d(x, torch.from_numpy(sd["inc.inconv.0.conv.0.weight"]))
+        return F.relu(_bn(sd, op["bn"], y))
+    _ul_only(ul, 1, "inc.inconv.0.conv.0", f)

@@ -1,5 +1,5 @@
-"""Op-by-op replay of the MuseTalk device program (U-Net + VAE decoder), the Wav2Lip program and the Whisper encoder against float64:
-oracle/op_replay.py.
+"""Op-by-op replay of the MuseTalk device program (U-Net + VAE decoder), the Wav2Lip program, the Whisper encoder and the Ultralight
+program against float64: oracle/op_replay.py.
 
 The program runs once; every named tensor is read back (Engine.musetalk_debug_get); the float64 oracle then recomputes every op on
 the DEVICE's own inputs, so each comparison measures one op (or one fused group) and nothing upstream.  Gates, per op (bound and
@@ -21,9 +21,17 @@ everything else between 0.99 and 1.00.  Before its sums were shifted, layernorm_
 tensor outside the bound in the 64-standard-deviation case; 1.00 now.
 Wav2Lip (54 layers + head, golden batch and 16 frames): every ratio 1.00 (the fp32 head 1.06 at rel_l2 4.7e-8), largest |dev - ref| / tol 0.39.
 Whisper encoder (40 ops, the 52-chunk step): every ratio 1.00, largest |dev - ref| / tol 0.85 (layers.2.final_layer_norm).
+Ultralight (86 ops of Engine.ultralight_ops(): 81 convs, 4 upsamples, audio_feat; profiles/ultralight_op_replay.txt): host path at
+B = 1, 2, 6 (B = 6: lin_fk on the 10 x 10 Cin = 512 expand convs) and the bank path (ultralight_infer, B = 3 from index 1: gather, crop
+and mask inside ul_in_kernel, uint8 frames in place of outc.conv), every frame replayed: 0 uncovered ops in every configuration, every
+ratio 1.00, largest |dev - ref| / tol 0.50 (the ops that are one fp16 rounding of an exact or fp32 result, where the model itself
+sits: upsamples, audio_feat, depthwise and input conv), 0.46 over the dense convs (down4.maxpool_conv.0.double_conv.0.conv.6, B = 6);
+audio_feat equals f16(input); uint8 head: 0 of 230 400 bytes outside floor(v) / floor(v +- d), 1 byte not floor(v), 0.28 % of the
+bytes within d of an integer.  The four tests 18 s on the GPU box (float64 replay 1 - 1.5 s per frame).
 """
 import os
 import time
+import types
 
 import numpy as np
 import pytest
@@ -293,3 +301,118 @@ def test_whisper_encoder_step():
     assert not miss, miss
     bad = R.failures(rp.records)
     assert not bad, "\n".join(bad)
+
+
+# ------------------------------------------------------------------------------------------------ Ultralight: 86 ops
+@pytest.fixture(scope="module")
+def ul():
+    """An engine of its own with the golden's weights over the three-face bank of synth.ultralight_faces."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import ultralight_ref as U
+    from livetalking_amd.engine import Engine
+    sd = synth.ultralight_state_dict(1234)
+    faces = synth.ultralight_faces(3, 1234)
+    frames, _, coords = synth.ultralight_avatar(3, (120, 200), seed=3)
+    eng = Engine(0)
+    try:
+        aid = eng.register_ultralight_avatar(sd, faces, frames, coords, max_frames=6)
+        yield types.SimpleNamespace(eng=eng, aid=aid, sd=sd, faces=faces, U=U)
+    finally:
+        eng.close()
+
+
+def _ul_replay(config, ul, B, img6, feat, run, fused=None):
+    """run() executes one pass of B frames with the capture on; every frame of it is replayed and every op of
+    Engine.ultralight_ops() has to be compared (fused: {op: what the caller checks in its place}).  -> the Replay."""
+    eng = ul.eng
+    eng.debug_capture(True)
+    try:
+        run()
+
+        def fetch(name, ref):
+            if fused and name in fused:
+                return None
+            return torch.from_numpy(eng.debug_get(name, (B,) + tuple(ref.shape[1:]))).to(ref.dtype)
+
+        t0 = time.time()
+        rp = ul.U.replay_ultralight(ul.sd, img6, feat, fetch, fused=fused)
+        dt = time.time() - t0
+    finally:
+        eng.debug_capture(False)
+    _table("ultralight", config, rp.records)
+    ops = eng.ultralight_ops(ul.aid)
+    assert [n for n, _ in ops] == ul.U.op_names()
+    miss = R.uncovered(ops, [r["name"] for r in rp.records] + list((fused or {}).values()), fused or {})
+    top = sorted(rp.records, key=lambda r: -r["ratio"])[:5]
+    _emit([f"# {config}: {len(ops)} ops, {len(rp.records)} compared, {len(miss)} uncovered, largest |dev - ref| / tol {max(r['dev_over_tol'] for r in rp.records):.2f}, "
+           f"replay of {B} frames {dt:.0f} s; largest ratios: " + ", ".join(f"{r['name']} {r['ratio']:.2f}" for r in top)])
+    assert not miss, f"{config}: ops not compared: {miss}"
+    bad = R.failures(rp.records)
+    assert not bad, f"{config}:\n" + "\n".join(bad)
+    return rp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 2, 6])
+def test_ultralight_host_path(ul, B):
+    """ultralight_forward_host on the golden's weights and inputs, every frame replayed, every op of Engine.ultralight_ops()
+    compared.  B = 1: the 10 x 10 maps are one ragged 100-row tile; B = 2: lin_fk takes up1's Cin = 512 expand conv (800 rows);
+    B = 6: the smallest count at which it takes the 10 x 10 Cin = 512 expand convs (600 rows >= kLinFkMinRows)."""
+    img6, feat = synth.ultralight_inputs(B, 1234)
+    rp = _ul_replay(f"ul host B={B}", ul, B, img6, feat, lambda: ul.eng.ultralight_forward_host(ul.aid, img6, feat))
+    assert len(rp.records) == 86
+
+
+def _mirror(size, index):
+    turn, res = divmod(index, size)
+    return res if turn % 2 == 0 else size - res - 1
+
+
+@pytest.mark.gpu
+def test_ultralight_bank_path_and_uint8_head(ul):
+    """One ultralight_infer call with the capture on (eager: the capture disables the graph), B = 3 from index 1 over the
+    three-face bank: bank order 1, 2, 2.  inc.inconv.0.conv.0 is held to the float64 op on img6_from_faces of those faces in that
+    order (gather order, crop offset and mask rectangle per element), audio_feat to the request's features.
+
+    outc.conv has no float tap here; the uint8 frames stand for it.  On the device's own up4.conv.double_conv.1.conv.6 tensor,
+    v = 255 sigmoid(conv) in float64; a byte has to be floor(v), or, where v lies within d of an integer, floor(v - d) or
+    floor(v + d); more than 1 % of the bytes inside that zone fails the test (it would then say too little).
+    d = 255 x the head's bound.  The bound of the w2l_head kind (2^-10 |ref| + 2^-12 A s (1 - s), made for every program's table)
+    gives d = 0.25 LSB (median) and puts 41.9 % of these bytes into the zone - computed on the CPU from the float64 forward of
+    these inputs alone - so it cannot meet the 1 % condition whatever the device does.  ul_head_kernel is fp32 throughout: 32 FMAs
+    and the bias (33 roundings of 2^-24 of at most A = |W| (*) |x| + |b|: 2^-18 A, through the sigmoid's slope s (1 - s)), expf,
+    the sum, the division, the product with 255 (2^-21 s together).  The test uses that bound, asserts that it is nowhere above
+    the w2l_head bound (what it accepts the other accepts too), and gets d = 1.5e-3 LSB (median), 0.29 % of the bytes in the
+    zone on the CPU."""
+    import torch.nn.functional as F
+    U, eng = ul.U, ul.eng
+    B, index = 3, 1
+    order = [_mirror(3, index + i) for i in range(B)]
+    assert order == [1, 2, 2]
+    img6 = U.img6_from_faces([ul.faces[i] for i in order])
+    feat = synth.ultralight_inputs(B, 1234)[1]
+    d_feat = torch.from_numpy(np.ascontiguousarray(feat)).cuda()
+    d_pred = torch.zeros(B, 160, 160, 3, dtype=torch.uint8, device="cuda")
+    rp = _ul_replay("ul bank B=3", ul, B, img6, feat, lambda: eng.ultralight_infer([(ul.aid, index, B, d_feat.data_ptr(), d_pred.data_ptr())]),
+                         fused={"outc.conv": "frames"})
+    compared = [r["name"] for r in rp.records]
+    assert "outc.conv" not in compared and "inc.inconv.0.conv.0" in compared and "audio_feat" in compared
+
+    x = rp.fused["outc.conv"]["x"]                                       # the device's own tensor, float64
+    W, b = (torch.from_numpy(ul.sd["outc.conv." + k]).double() for k in ("weight", "bias"))
+    sg = torch.sigmoid(F.conv2d(x, W, b))
+    v = 255.0 * sg
+    wide = rp.head(x.float(), "outc.conv", sg)[1].double() + R.F16_FLOOR
+    tol = 2.0 ** -18 * F.conv2d(x.abs(), W.abs(), b.abs()) * sg * (1 - sg) + 2.0 ** -21 * sg
+    assert bool((tol <= wide).all())
+    d = 255.0 * tol
+    lo, hi = torch.floor(v - d), torch.floor(v + d)
+    zone = float((lo != hi).double().mean())
+    got = d_pred.cpu().permute(0, 3, 1, 2).double()
+    wrong = int(((got != torch.floor(v)) & ~((lo != hi) & ((got == lo) | (got == hi)))).sum())
+    off = int((got != torch.floor(v)).sum())
+    _emit([f"# ul bank B=3 uint8 head: {got.numel()} bytes, {wrong} outside floor(v) / floor(v +- d), {off} not floor(v); d median {float(d.median()):.2e} LSB, "
+           f"{100 * zone:.2f} % of the bytes within d of an integer"])
+    assert zone <= 0.01, f"{100 * zone:.2f} % of the bytes lie within d of an integer"
+    assert wrong == 0, f"{wrong} bytes are neither floor(v) nor inside the rounding zone"

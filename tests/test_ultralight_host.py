@@ -21,7 +21,7 @@ REFERENCE = os.environ.get("LTK_REFERENCE", "/root/reference")
 HAVE_REFERENCE = os.path.isfile(os.path.join(REFERENCE, "avatars", "ultralight_avatar.py"))
 
 NEW_ENTRIES = ["ltk_ultralight_avatar_register", "ltk_ultralight_infer", "ltk_ultralight_paste_back", "ltk_ultralight_forward_host",
-               "ltk_ultralight_time", "ltk_dwconv3x3_f16", "ltk_upsample2x_cat_f16"]
+               "ltk_ultralight_time", "ltk_dwconv3x3_f16", "ltk_upsample2x_cat_f16", "ltk_ultralight_op_count", "ltk_ultralight_op_name"]
 
 
 def _gen():
@@ -79,6 +79,8 @@ def test_null_and_garbage_arguments_are_invalid_without_a_gpu():
     assert lib.ltk_ultralight_forward_host(None, 1, buf, buf, 1, buf) == INVALID
     ms, macs = C.c_float(), C.c_double()
     assert lib.ltk_ultralight_time(None, 1, 1, 1, C.byref(ms), C.byref(macs)) == INVALID
+    assert lib.ltk_ultralight_op_count(None, 1) == 0
+    assert lib.ltk_ultralight_op_name(None, 1, 0, None, 0, None) == INVALID
     assert lib.ltk_dwconv3x3_f16(None, buf, 1, 4, 4, 16, buf, 1, None, None, 1, buf) == INVALID
     assert lib.ltk_upsample2x_cat_f16(None, buf, 1, 4, 4, 16, buf, 8, 8, 16, buf) == INVALID
 

@@ -13,6 +13,14 @@ Tap names are the state_dict prefixes of the convs; a conv's tap is the tensor a
 and the residual add where the block has one (what one launch of the engine writes).  "<block>.up" is an upsample's output,
 "outc.conv" the sigmoid output.
 
+`force` is the hook protocol of oracle/wav2lip_oracle.py and oracle/musetalk_oracle.py (the op-by-op replay, oracle/op_replay.py):
+force.describe(name, op) before an op (where it has that method), force(name, ref) -> tensor or None after it; the forward goes on
+with the tensor returned.  Names are the tap names and "audio_feat", the features as the device takes them in.  Op descriptions:
+  ul_conv  dense conv + BatchNorm: p, bn, x, stride, pad, relu, res (None or the tensor added behind the BatchNorm)
+  ul_dw    depthwise 3x3 + BatchNorm + ReLU: p, bn, x, stride          ul_in    inc.inconv.0.conv.0 (1x1 on the 6-channel input): p, bn, x
+  ul_up    bilinear x2, align_corners=True: x                          ul_feat  the feature chunk: x          ul_head  outc + sigmoid: p, x
+Without a hook the forward is what it was, bit for bit.
+
 `fp16_model=True` is the rounding model of an fp16 implementation the frame tests measure against: weights rounded to fp16,
 and the output of every BatchNorm, every biased conv and every upsample rounded to fp16; everything else stays float64.
 """
@@ -63,9 +71,9 @@ def conv_prefixes():
 
 
 class _Net:
-    def __init__(self, sd, dtype, fp16_model, taps):
+    def __init__(self, sd, dtype, fp16_model, taps, force=None):
         self.sd = {k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}
-        self.dtype, self.h, self.taps = dtype, fp16_model, taps
+        self.dtype, self.h, self.taps, self.force = dtype, fp16_model, taps, force
 
     def r16(self, t):
         return t.half().to(self.dtype) if self.h else t
@@ -80,17 +88,31 @@ class _Net:
         y = (x - m[None, :, None, None]) / torch.sqrt(v[None, :, None, None] + BN_EPS) * g[None, :, None, None] + b[None, :, None, None]
         return self.r16(y)
 
-    def tap(self, name, t):
+    def forced(self, name, t, op):
+        if self.force is None:
+            return t
+        if hasattr(self.force, "describe"):
+            self.force.describe(name, op)
+        r = self.force(name, t)
+        return t if r is None else r
+
+    def tap(self, name, t, op=None):
+        t = self.forced(name, t, op)
         if self.taps is not None:
             self.taps[name] = t.detach().to(torch.float64).numpy().copy()
         return t
 
     def ir(self, p, x, stride, residual):
-        y = self.tap(p + ".conv.0", F.relu(self.bn(F.conv2d(x, self.w(p + ".conv.0.weight")), p + ".conv.1")))
+        f = self.force is not None
+        e = self.tap(p + ".conv.0", F.relu(self.bn(F.conv2d(x, self.w(p + ".conv.0.weight")), p + ".conv.1")),
+                     f and (dict(kind="ul_in", p=p + ".conv.0", bn=p + ".conv.1", x=x) if x.shape[1] == 6 else
+                            dict(kind="ul_conv", p=p + ".conv.0", bn=p + ".conv.1", x=x, stride=1, pad=0, relu=True, res=None)))
         wd = self.w(p + ".conv.3.weight")
-        y = self.tap(p + ".conv.3", F.relu(self.bn(F.conv2d(y, wd, stride=stride, padding=1, groups=wd.shape[0]), p + ".conv.4")))
-        y = self.bn(F.conv2d(y, self.w(p + ".conv.6.weight")), p + ".conv.7")
-        return self.tap(p + ".conv.6", x + y if residual else y)
+        d = self.tap(p + ".conv.3", F.relu(self.bn(F.conv2d(e, wd, stride=stride, padding=1, groups=wd.shape[0]), p + ".conv.4")),
+                     f and dict(kind="ul_dw", p=p + ".conv.3", bn=p + ".conv.4", x=e, stride=stride))
+        y = self.bn(F.conv2d(d, self.w(p + ".conv.6.weight")), p + ".conv.7")
+        return self.tap(p + ".conv.6", x + y if residual else y,
+                        f and dict(kind="ul_conv", p=p + ".conv.6", bn=p + ".conv.7", x=d, stride=1, pad=0, relu=False, res=x if residual else None))
 
     def dconv(self, p, x, stride):
         return self.ir(p + ".double_conv.1", self.ir(p + ".double_conv.0", x, stride, False), 1, True)
@@ -101,31 +123,32 @@ class _Net:
         for p, _, _, s in DOWN:
             x = self.dconv(p, x, s)
             skips.append(x)
-        a = feat
+        a = self.forced("audio_feat", feat, dict(kind="ul_feat", x=feat))
         for item in AUDIO:
             if item[0] == "ir":
                 a = self.ir(item[1], a, 1, item[4])
             else:
                 _, conv, norm, _, _, stride, pad = item
+                a_in = a
                 a = self.r16(F.conv2d(a, self.w(conv + ".weight"), self.sd[conv + ".bias"].to(self.dtype), stride=stride, padding=pad))
-                a = self.tap(conv, F.relu(self.bn(a, norm)))
+                a = self.tap(conv, F.relu(self.bn(a, norm)), dict(kind="ul_conv", p=conv, bn=norm, x=a_in, stride=stride, pad=pad, relu=True, res=None))
         x = torch.cat([skips.pop(), a], dim=1)
         for p, _, _, s in FUSE:
             x = self.dconv(p, x, s)
         for p, _, _ in UP:
-            u = self.tap(p + ".up", self.r16(F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)))
+            u = self.tap(p + ".up", self.r16(F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)), dict(kind="ul_up", x=x))
             x = self.dconv(p + ".conv", torch.cat([u, skips.pop()], dim=1), 1)
         logits = F.conv2d(x, self.sd["outc.conv.weight"].to(self.dtype) if not self.h else self.w("outc.conv.weight"),
                           self.sd["outc.conv.bias"].to(self.dtype))
-        return self.tap("outc.conv", torch.sigmoid(logits))
+        return self.tap("outc.conv", torch.sigmoid(logits), dict(kind="ul_head", p="outc.conv", x=x))
 
 
 def forward(sd: Dict[str, np.ndarray], img6: np.ndarray, feat: np.ndarray, dtype=torch.float64, fp16_model: bool = False,
-            taps: Optional[dict] = None) -> np.ndarray:
+            taps: Optional[dict] = None, force=None) -> np.ndarray:
     """Model(6, 'hubert').forward: img6 (B, 6, 160, 160) in [0, 1], feat (B, 16, 32, 32) -> sigmoid output (B, 3, 160, 160)
-    as a float64 array, computed in `dtype`."""
+    as a float64 array, computed in `dtype`.  force: the hook of the op-by-op replay (module docstring)."""
     with torch.no_grad():
-        net = _Net(sd, dtype, fp16_model, taps)
+        net = _Net(sd, dtype, fp16_model, taps, force)
         x = torch.as_tensor(np.asarray(img6)).to(dtype)
         a = torch.as_tensor(np.asarray(feat)).to(dtype).reshape(-1, 16, 32, 32)
         if fp16_model:
@@ -156,3 +179,42 @@ def frame_stats(got_u8: np.ndarray, ref_u8: np.ndarray):
     mse = float((d.astype(np.float64) ** 2).mean())
     psnr = 99.0 if mse == 0 else float(10 * np.log10(255.0 ** 2 / mse))
     return int(d.max()), psnr, float((d != 0).mean())
+
+
+# ---------------------------------------------------------------------------------------------------- op replay
+def replay_ultralight(sd, img6, feat, fetch, only=None, fused=None):
+    """The teacher-forced float64 replay (oracle/op_replay.py) of one pass.  sd: the float32 state dict; img6 (B, 6, 160, 160) float32
+    as the pass took it in (or img6_from_faces of the bank faces it gathered); feat (B, 16, 32, 32): the float32 features the device
+    read; fetch(name, ref) -> the device's tensor of that name in ref's shape and dtype.  The consumer of a concat sees the
+    concatenation of the device's own two tensors.  fused: {name: what stands for it} for an op whose tensor the pass does not keep
+    (outc.conv when the pass writes uint8 frames): fetch returns None there and the op's description, the device's own input in it,
+    is left in Replay.fused.  -> the Replay (records, one per op)."""
+    from oracle import op_replay as R
+    rp = R.Replay({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, fetch, only=only)
+    rp.may_fuse = dict(fused or {})
+    forward(sd, np.asarray(img6, dtype=np.float32), np.asarray(feat, dtype=np.float32), force=rp)
+    return rp
+
+
+def op_names():
+    """The ops of the device program in execution order (Engine.ultralight_ops): a tap per launch."""
+    out = []
+
+    def ir(p):
+        out.extend([p + ".conv.0", p + ".conv.3", p + ".conv.6"])
+
+    def dconv(p):
+        ir(p + ".double_conv.0"); ir(p + ".double_conv.1")
+
+    ir("inc.inconv.0")
+    for p, *_ in DOWN:
+        dconv(p)
+    out.append("audio_feat")
+    for item in AUDIO:
+        ir(item[1]) if item[0] == "ir" else out.append(item[1])
+    for p, *_ in FUSE:
+        dconv(p)
+    for p, *_ in UP:
+        out.append(p + ".up")
+        dconv(p + ".conv")
+    return out + ["outc.conv"]
