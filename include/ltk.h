@@ -451,6 +451,16 @@ int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
 int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
                       int silu, int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg);
 
+/* Standalone attention O = softmax(Q K^T) V per (image, head) over channel-blocked fp16 tensors, for kernel unit tests: v_transpose_kernel into a
+ * scratch V^T of the hook's own, then the attention kernel, on the compute stream, synchronised.  q / o: device fp16 [N][cbt][Tq][16], k / v:
+ * [N][cbt][Tk][16]; every tensor has its own cbt (channel blocks in its buffer) and cb0 (first block of head 0), head h at blocks
+ * [cb0 + h * d16 / 16, + d16 / 16): views into a stacked q|k|v buffer and an output in the middle of a wider one.  d16 in {48, 64, 80, 160, 512};
+ * the 1 / sqrt(d) scale is the caller's, as in the programs (folded into q).  impl: 0 = what a program would launch under the current
+ * knobs, 1 = the per-wave kernel (attn_kernel; attn_wide_kernel at d16 = 512) even where the LDS form serves the shape, 2 = attn_lds_kernel
+ * (d16 48 / 80, Tk a multiple of 64 and >= 128); an impl that does not serve the shape is refused. */
+int ltk_attention_f16(ltk_engine* e, const void* d_q, int q_cbt, int q_cb0, const void* d_k, int k_cbt, int k_cb0, const void* d_v, int v_cbt,
+                      int v_cb0, void* d_o, int o_cbt, int o_cb0, int N, int heads, int d16, int Tq, int Tk, int impl);
+
 /* host-side fp32 -> OCP e4m3fn conversion of the weight packer (round to nearest even, saturating at +-448); no GPU needed */
 int ltk_f32_to_e4m3(const float* in, size_t n, uint8_t* out);
 

@@ -332,6 +332,31 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
     return rc;
 }
 
+int ltk_attention_f16(ltk_engine* e, const void* d_q, int q_cbt, int q_cb0, const void* d_k, int k_cbt, int k_cb0, const void* d_v, int v_cbt,
+                      int v_cb0, void* d_o, int o_cbt, int o_cb0, int N, int heads, int d16, int Tq, int Tk, int impl) {
+    if (!e || !d_q || !d_k || !d_v || !d_o || N <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (d16 != 48 && d16 != 64 && d16 != 80 && d16 != 160 && d16 != 512) return fail(LTK_E_INVALID, "attention: d16 must be 48, 64, 80, 160 or 512");
+    const int hcb = heads * (d16 / 16);
+    if (q_cb0 < 0 || k_cb0 < 0 || v_cb0 < 0 || o_cb0 < 0 || q_cb0 + hcb > q_cbt || k_cb0 + hcb > k_cbt || v_cb0 + hcb > v_cbt || o_cb0 + hcb > o_cbt)
+        return fail(LTK_E_INVALID, "attention: the heads do not fit the buffer's channel blocks");
+    if (N > 65535 || heads > 65535 || (double)N * std::max(std::max(q_cbt, o_cbt), std::max(k_cbt, v_cbt)) * 16.0 * std::max(Tq, Tk) >= 2147483647.0)
+        return fail(LTK_E_INVALID, "attention: tensor too large");
+    if (impl < 0 || impl > 2 || (impl == 2 && !attn_lds_serves(d16, Tk))) return fail(LTK_E_INVALID, "this attention kernel does not serve the shape");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    DevBuf vt;
+    CHK(hipMalloc(&vt.p, (size_t)N * heads * attn_dv32(d16) * attn_tkp(Tk) * sizeof(f16)));
+    hipStream_t s = e->compute;
+    launch_v_transpose((const f16*)d_v, N, v_cbt, v_cb0, heads, d16, Tk, (f16*)vt.p, s);
+    hipError_t le = hipGetLastError();
+    const int rc = le == hipSuccess ? launch_attention((const f16*)d_q, q_cbt, q_cb0, Tq, (const f16*)d_k, k_cbt, k_cb0, Tk, (const f16*)vt.p, (f16*)d_o,
+                                                       o_cbt, o_cb0, N, heads, d16, s, impl) : 0;
+    const hipError_t se = hipStreamSynchronize(s);       // before the V^T scratch goes
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("attention kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, "attention launch failed (head dim " + std::to_string(d16) + ")");
+    return LTK_OK;
+}
+
 // ------------------------------------------------------------------ Ultralight hooks
 int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6, const float* feat, int B, float* pred) {
     if (!e || !img6 || !feat || !pred || B <= 0) return fail(LTK_E_INVALID, "bad arguments");

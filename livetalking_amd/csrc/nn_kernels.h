@@ -47,6 +47,8 @@ void launch_layernorm(const f16* x, int N, int cbt, int cb0, int C, int P, float
 // ---- attention: O = softmax(Q K^T) V per (image, head); the 1/sqrt(d) scale is folded into the q projection.
 // q/k/o: CB16 with head h at channel blocks [cb0 + h*d16/16, +d16/16); vt: [N][heads][dv32][Tkp] fp16, keys of every
 // 16-group stored in MFMA slot order (launch_v_transpose writes it).  d16 in {48,64,80,160,512}.
+// impl: 0 = the LDS form where it serves the shape and knob ATTN_LDS is on, 1 = the per-wave / wide kernel, 2 = the LDS form (-1 where
+// it does not serve the shape); the programs pass 0, ltk_attention_f16 any of them.
 int attn_dv32(int d16);
 int attn_tkp(int Tk);
 void launch_v_transpose(const f16* v, int N, int cbt, int cb0, int heads, int d16, int Tk, f16* vt, hipStream_t s);
@@ -57,7 +59,8 @@ struct VtMulti {
 };
 void launch_v_transpose_multi(VtMulti m, int N, hipStream_t s);
 int launch_attention(const f16* q, int q_cbt, int q_cb0, int Tq, const f16* k, int k_cbt, int k_cb0, int Tk, const f16* vt,
-                     f16* o, int o_cbt, int o_cb0, int N, int heads, int d16, hipStream_t s);
+                     f16* o, int o_cbt, int o_cb0, int N, int heads, int d16, hipStream_t s, int impl = 0);
+bool attn_lds_serves(int d16, int Tk);      // attn_lds_kernel: head dims 40 / 80 (d16 48 / 80) over >= 128 keys in whole 64-key tiles
 
 // ---- GEGLU: y[c] = a[c] * gelu(gate[c]), a = channels [0,C), gate = [C,2C) of x (diffusers GEGLU, exact erf gelu)
 void launch_geglu(const f16* x, int N, int x_cbt, int x_cb0, int C, int P, f16* y, int y_cbt, int y_cb0, hipStream_t s);

@@ -990,8 +990,10 @@ __global__ __launch_bounds__(256, 2) void attn_wide_kernel(const AttnArgs a) {
     }
 }
 
+bool attn_lds_serves(int d16, int Tk) { return Tk % 64 == 0 && Tk >= 128 && (d16 == 48 || d16 == 80); }
+
 int launch_attention(const f16* q, int q_cbt, int q_cb0, int Tq, const f16* k, int k_cbt, int k_cb0, int Tk, const f16* vt,
-                     f16* o, int o_cbt, int o_cb0, int N, int heads, int d16, hipStream_t s) {
+                     f16* o, int o_cbt, int o_cb0, int N, int heads, int d16, hipStream_t s, int impl) {
     AttnArgs a;
     a.q = q; a.k = k; a.vt = vt; a.o = o;
     a.q_cbt = q_cbt; a.q_cb0 = q_cb0; a.k_cbt = k_cbt; a.k_cb0 = k_cb0; a.o_cbt = o_cbt; a.o_cb0 = o_cb0;
@@ -999,7 +1001,8 @@ int launch_attention(const f16* q, int q_cbt, int q_cb0, int Tq, const f16* k, i
     const int qtiles = (Tq + 31) / 32;
     const dim3 grid4((qtiles + 3) / 4, heads, N), grid1(qtiles, heads, N);
     // self-attention over whole 64-key tiles: K / V^T tiles shared by a block's four query tiles through LDS (knob ATTN_LDS)
-    if (knob(K_ATTN_LDS) && Tk % 64 == 0 && Tk >= 128 && (d16 == 48 || d16 == 80)) {
+    if (impl == 2 && !attn_lds_serves(d16, Tk)) return -1;
+    if ((impl == 2 || (impl == 0 && knob(K_ATTN_LDS))) && attn_lds_serves(d16, Tk)) {
         if (d16 == 48) hipLaunchKernelGGL((attn_lds_kernel<3, 2>), grid4, dim3(256), (size_t)3 * (3 * 2048 + 2 * 32 * 128), s, a);
         else {
             constexpr int lds53 = 3 * (5 * 2048 + 3 * 32 * 128);          // 66 KiB: above the 64-KiB default

@@ -596,6 +596,15 @@ class Engine:
                                                1 if silu else 0, impl, 1 if out_fp8 else 0, float(out_scale), C.c_void_p(d_y_ptr), iters, C.byref(ms)))
         return ms.value
 
+    def attention_f16(self, q, k, v, o, N, heads, d16, Tq, Tk, impl: int = 0) -> None:
+        """Standalone attention on CB16 tensors (include/ltk.h: ltk_attention_f16).  q, k, v, o: (device pointer, cbt, cb0) each - the
+        buffer, its channel blocks and the first block of head 0; impl 0 = the program's choice, 1 = the per-wave / wide kernel, 2 = the
+        LDS form.  The 1 / sqrt(d) scale is the caller's."""
+        args = []
+        for ptr, cbt, cb0 in (q, k, v, o):
+            args += [C.c_void_p(ptr), int(cbt), int(cb0)]
+        _lib.check(self._lib.ltk_attention_f16(self._h, *args, N, heads, d16, Tq, Tk, impl))
+
     def conv2d_f16(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, Cout, k, stride, pad, transposed=False,
                    out_pad=0, scale: Optional[np.ndarray] = None, shift: Optional[np.ndarray] = None,
                    d_res_ptr: int = 0, relu=True, d_y_ptr: int = 0, iters: int = 0) -> float:

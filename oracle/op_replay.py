@@ -167,6 +167,34 @@ def _gelu_grad(g: Tensor) -> Tensor:
     return 0.5 * (1 + torch.erf(g / math.sqrt(2.0))) + g * torch.exp(-0.5 * g * g) / math.sqrt(2.0 * math.pi)
 
 
+def attention_model(q: Tensor, k: Tensor, v: Tensor, subnormal_p: bool = False, scale: float = 1.0, want_ref: bool = True):
+    """softmax(scale q k^T) v per (image, head): q [B, h, Tq, d], k / v [B, h, Tk, d] (fp16 values in any float dtype; Tq != Tk is
+    fine).  q is taken as it stands - the programs fold d^-0.5 into the q projection - and `scale` multiplies the logits for a caller
+    whose q is not scaled (the replay).  -> (ref, mod, tol):
+      ref : float64 (None with want_ref=False: the replay has the oracle's own);
+      mod : the rounding model, float32 - fp32 logits and exp, probabilities rounded to fp16 in front of P V, their sum l kept in
+            fp32, the result rounded to fp16 once;
+      tol : 2^-10 |ref| + 2^-10 softmax(S) |V| (with want_ref=False only the second term: the caller adds 2^-10 |ref|), without
+            F16_FLOOR, which the gates add to every bound.
+    subnormal_p adds 2^-25 sum_k |V_k| / l.  The kernels round exp(S - max) to fp16 before the P V MFMA; below 2^-14 that is fp16's
+    subnormal range, where a probability is off by up to 2^-25 ABSOLUTE whatever its size, and a key with p ~ 1e-6 and |V| ~ 1e3
+    behind a dominant key with a small value row puts the model itself two orders of magnitude outside the relative terms
+    (tests/test_attention_host.py).  Off by default: the replays' constants stay as they are."""
+    qf, kf, vf = q.float(), k.float(), v.float()
+    S = (qf @ kf.transpose(-1, -2)) * scale
+    pr = torch.exp(S - S.amax(-1, keepdim=True))
+    l = pr.sum(-1, keepdim=True)
+    mod = f16((f16(pr) @ vf) / l)                       # probabilities go to the MFMA as fp16, their sum stays fp32
+    tol = C_ACT * (pr @ vf.abs()) / l
+    if subnormal_p:
+        tol = tol + 2.0 ** -25 * vf.abs().sum(-2, keepdim=True) / l
+    ref = None
+    if want_ref:
+        ref = torch.softmax((q.double() @ k.double().transpose(-1, -2)) * scale, -1) @ v.double()
+        tol = tol + 2.0 ** -10 * ref.abs().float()
+    return ref, mod, tol
+
+
 class Replay:
     """The `force` object of one replay.  sd: float32 state dict (U-Net and VAE keys together); fetch(name, ref) -> the device's
     tensor in ref's shape and dtype, or None when the program does not materialise it."""
@@ -340,15 +368,11 @@ class Replay:
             mod = f16(y)
             tol = 2.0 ** -10 * ref.abs() + C_ACT * A + sm
         elif kind == "attn":
-            q, k, v = op["q"].float(), op["k"].float(), op["v"].float()
+            q, k, v = op["q"], op["k"], op["v"]
             B, h, T, d = q.shape
-            S = (q @ k.transpose(-1, -2)) * (d ** -0.5)
-            pr = torch.exp(S - S.amax(-1, keepdim=True))
-            l = pr.sum(-1, keepdim=True)
-            o = (f16(pr) @ v) / l                       # probabilities go to the MFMA as fp16, their sum stays fp32
-            A = (pr @ v.abs()) / l
-            mod = _tok_to_nchw(f16(o).transpose(1, 2).reshape(B, T, h * d), op.get("hw"))
-            tol = 2.0 ** -10 * ref.abs() + C_ACT * _tok_to_nchw(A.transpose(1, 2).reshape(B, T, h * d), op.get("hw"))
+            _, o, A = attention_model(q, k, v, scale=d ** -0.5, want_ref=False)
+            mod = _tok_to_nchw(o.transpose(1, 2).reshape(B, T, h * d), op.get("hw"))
+            tol = 2.0 ** -10 * ref.abs() + _tok_to_nchw(A.transpose(1, 2).reshape(B, T, h * d), op.get("hw"))
         elif kind == "geglu":
             prod = self.fused.get(PRODUCER.get(name, ""))
             if prod is not None:                        # GEGLU in the epilogue of its projection

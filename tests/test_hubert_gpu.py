@@ -164,13 +164,22 @@ def _fetch(eng):
     return fetch
 
 
-@pytest.mark.parametrize("n", [1040, 22613])
+# rows at which the kernel choice of a program changes with the clip's length (n = 320 T + 80 samples give T rows)
+EDGE_ROWS = (1, 31, 32, 33, 51, 64, 65, 128, 129, 513)
+
+
+@pytest.mark.parametrize("n", [1040, 22613] + [320 * T + 80 for T in EDGE_ROWS])
 def test_every_op_against_float64(eng, sd2, n):
-    """2 layers at 3 rows and at 70 rows (layers 5 and 6 are the two-tap convs; 70 rows take conv3 for the linear layers, 3 rows the
-    row GEMM): every op on the device's own input, op_replay's gates, and no op of hubert_ops() left uncompared."""
+    """2 layers, every op on the device's own input, op_replay's gates, and no op of hubert_ops() left uncompared.  3 rows and 70
+    rows (layers 5 and 6 are the two-tap convs; 70 rows take conv3 for the linear layers, 3 rows the row GEMM), then the lengths
+    where a program built for another clip length takes another kernel: 1 row; 31 / 32 / 33 and 64 / 65, 128 / 129 (the attention's
+    32-key tiles and blocks of four query tiles; the linear layers leave the row GEMM for conv3 from 65 rows on); 51, the live step's
+    length; 513 (feature_projection.projection goes to lin_fk_kernel from 512 rows on, conv3's split-K choice moves with the row
+    count).  At most three programs stay alive over the sweep."""
     pcm = H.speech(n, 9)
     feat = eng.hubert_features(pcm)
     assert feat.shape == ((n - 80) // 320, 1024)
+    assert eng.hubert_info()["programs"] <= 3
     x_norm = eng.hubert_debug_get("input_values", (n,))
     assert R.rel_l2(torch.from_numpy(x_norm), torch.from_numpy(H.normalise(pcm))) <= 1e-6
     rp = H.replay(sd2, x_norm, _fetch(eng))
