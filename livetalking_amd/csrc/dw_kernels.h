@@ -21,6 +21,9 @@ constexpr int kUlMaskX0 = 5, kUlMaskX1 = 154, kUlMaskY0 = 5, kUlMaskY1 = 149;
 // fp32 accumulation, one fp16 rounding.  C % 16 == 0.
 void launch_dwconv3x3(const f16* x, int N, int x_cbt, int x_cb0, int C, int H, int W, int stride, const float* w, const float* scale,
                       const float* shift, int relu, f16* y, int y_cbt, int y_cb0, hipStream_t s);
+// The host image of those three arrays, back to back: weight fp32 [C][3][3] -> out[Cpad / 16][9][16], then scale [Cpad] (null: 1) and shift
+// [Cpad] (null: 0); the layout channels behind the first C get zero weights, scale and shift.  out: Cpad * 11 floats.
+void dw_pack(const float* weight, const float* scale, const float* shift, int C, int Cpad, float* out);
 
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) (unet.py:76): source coordinate of output pixel o is
 // o * (h - 1) / (2h - 1), formed from integers; the interpolation itself runs in fp64 (the kernel moves 5 tensor elements per

@@ -5,6 +5,14 @@
 
 namespace ltk {
 
+void dw_pack(const float* weight, const float* scale, const float* shift, int C, int Cpad, float* out) {
+    for (int c = 0; c < Cpad; ++c) {
+        for (int t = 0; t < 9; ++t) out[((size_t)(c >> 4) * 9 + t) * 16 + (c & 15)] = c < C ? weight[(size_t)c * 9 + t] : 0.f;
+        out[(size_t)Cpad * 9 + c] = c < C ? (scale ? scale[c] : 1.f) : 0.f;
+        out[(size_t)Cpad * 10 + c] = c < C && shift ? shift[c] : 0.f;
+    }
+}
+
 namespace {
 
 union H8 {

@@ -1,8 +1,7 @@
 // libltk_hip.so: engine lifetime, avatar banks, mel step and paste-back of the C ABI (include/ltk.h).  The Wav2Lip program is
 // in w2l_program.hip, its inference path in w2l_infer.hip, MuseTalk / Whisper / VAE encoder in mt_engine.hip, frame egress in
-// egress.hip, the test and measurement hooks in engine_debug.hip; engine_internal.h is what they share.  The Ultralight avatar
-// (ultralight.hip: its launch program, register / infer / paste-back; dw_kernels.hip: its VALU kernels) is included at the end of
-// this file and compiled with it.
+// egress.hip, the Ultralight avatar (launch program, register / infer / paste-back) in ultralight.hip, the test and measurement hooks
+// in engine_debug.hip; engine_internal.h is what they share.
 #include "engine_internal.h"
 
 thread_local std::string ltk::g_err;
@@ -293,5 +292,3 @@ int ltk_paste_blend(ltk_engine* e, int avatar_id, int idx, const void* d_pred, v
 }
 
 }  // extern "C"
-
-#include "ultralight.hip"

@@ -1,5 +1,5 @@
 // ------------------------------------------------------------------ test / measurement hooks of both models
-#include "engine_internal.h"
+#include "debug_util.h"
 
 extern "C" {
 
@@ -98,9 +98,6 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
     if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
-    hipEvent_t t0, t1;
-    CHK(hipEventCreate(&t0));
-    CHK(hipEventCreate(&t1));
     // the pass as ltk_wav2lip_infer runs it (pack_mel + conv stack with the bank gather and the output head fused, knob
     // HEAD_FUSED; replayed from the captured graph under knob GRAPH), same micro-batch schedule, frames going to a scratch buffer
     const int mbs = std::min(e->micro_batch, kPackMaxFrames);
@@ -139,16 +136,10 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
     rc = pass();              // warm (eager)
     if (!rc) rc = pass();     // warm (captures the graph under knob GRAPH)
     if (rc) return rc;
-    CHK(hipEventRecord(t0, e->compute));
-    for (int i = 0; i < iters && !rc; ++i) rc = pass();
-    if (rc) return rc;
-    CHK(hipEventRecord(t1, e->compute));
-    CHK(hipEventSynchronize(t1));
     float ms = 0.f;
-    CHK(hipEventElapsedTime(&ms, t0, t1));
+    if ((rc = time_iters(e->compute, iters, pass, &ms))) return rc;
     *ms_per_pass = ms / iters;
     if (macs_per_pass) *macs_per_pass = (e->macs_per_frame - (knob(K_HEAD_FUSED) ? 0.0 : 32.0 * 3 * 65536)) * frames;
-    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     return LTK_OK;
 }
 
@@ -203,68 +194,56 @@ int ltk_wav2lip_time_layers(ltk_engine* e, int frames, int iters, float* ms_per_
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
     if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
-    std::vector<hipEvent_t> evs(e->layers.size() + 1);
-    for (auto& ev : evs) CHK(hipEventCreate(&ev));
     const bool fused = knob(K_HEAD_FUSED) != 0;
     TimingIO tio;
     int rc = tio.setup(e, frames);
     if (rc) return rc;
     const OutPtrs* d_outs = fused ? &e->d_tab->outs : nullptr;
     const FacePtrs* d_faces = e->c7 ? &e->d_tab->faces : nullptr;
-    std::vector<double> acc(e->layers.size(), 0.0);
-    rc = run_convs(e, frames, e->compute, d_outs, nullptr, d_faces);     // warm
-    for (int it = 0; it < iters && !rc; ++it) {
-        rc = run_convs(e, frames, e->compute, d_outs, &evs, d_faces);
-        if (rc) break;
-        CHK(hipEventSynchronize(evs.back()));
-        for (size_t i = 0; i < e->layers.size(); ++i) {
-            float ms = 0.f;
-            CHK(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
-            acc[i] += ms;
-        }
-    }
-    for (auto& ev : evs) (void)hipEventDestroy(ev);
-    if (rc) return rc;
-    for (size_t i = 0; i < e->layers.size(); ++i) ms_per_layer[i] = (float)(acc[i] / iters);
-    return LTK_OK;
+    if ((rc = run_convs(e, frames, e->compute, d_outs, nullptr, d_faces))) return rc;     // warm
+    return time_intervals(n_layers, iters, [&](std::vector<hipEvent_t>* evs) { return run_convs(e, frames, e->compute, d_outs, evs, d_faces); },
+                          ms_per_layer);
 }
 
-int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
-                   const float* weight, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
-                   int transposed, int out_pad, const float* scale, const float* shift,
-                   const void* d_res, int relu, void* d_y, int iters, float* ms_avg) {
+namespace {
+// one conv layer on its own, fp16 operands (quant = 0) or e4m3 (conv_fp8_quant): plan, one launch, then `iters` timed ones
+int conv2d_hook(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, int kh, int kw, int sh, int sw,
+                int ph, int pw, bool transposed, int out_pad, const float* scale, const float* shift, int quant, float act_scale,
+                const void* d_res, int relu, int act, void* d_y, int iters, float* ms_avg) {
     if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
     CHK(enter_device(e->device));
     ConvPlan plan;
     std::string err;
-    int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err);
+    int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, scale, shift, &err, quant, act_scale);
     if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
     ConvIO io;
     io.partial = e->d_partial; io.partial_cap = e->partial_cap;
-    io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;
+    io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;   // (fp8: 16-bit units)
     io.y = (f16*)d_y; io.y_ld = Cout; io.y_coff = 0;
     io.res = (const f16*)d_res; io.res_ld = Cout; io.res_coff = 0;
-    io.relu = relu;
+    io.relu = relu; io.act = act;
     hipStream_t s = e->compute;
     std::lock_guard<std::mutex> g(e->mu);
-    rc = conv_launch(plan, io, s, &err);
+    auto launch = [&]() -> int { const int lrc = conv_launch(plan, io, s, &err); return lrc ? fail(lrc == -2 ? LTK_E_HIP : LTK_E_INVALID, err) : 0; };
+    rc = launch();
     if (!rc && iters > 0 && ms_avg) {
-        hipEvent_t t0, t1;
-        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
-        (void)hipEventRecord(t0, s);
-        for (int i = 0; i < iters && !rc; ++i) rc = conv_launch(plan, io, s, &err);
-        (void)hipEventRecord(t1, s);
-        (void)hipEventSynchronize(t1);
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
+        rc = time_iters(s, iters, launch, &ms);
         *ms_avg = ms / iters;
-        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     }
-    hipError_t he = hipStreamSynchronize(s);
+    const hipError_t he = hipStreamSynchronize(s);
     conv_plan_destroy(&plan);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    if (rc) return rc;
     if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
     return LTK_OK;
+}
+}  // namespace
+
+int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, int kh, int kw, int sh, int sw,
+                   int ph, int pw, int transposed, int out_pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
+                   int iters, float* ms_avg) {
+    return conv2d_hook(e, d_x, N, H, W, Cin, weight, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, 0, 1.f, d_res, relu, 0,
+                       d_y, iters, ms_avg);
 }
 
 int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
@@ -276,26 +255,18 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
     const int members = gn_coop_members(C, P, groups);
     if (impl == 0) impl = (knob(K_MT_GN1) && fits_group) ? 2 : (knob(K_GN_COOP) && members) ? 3 : 1;
     if ((impl == 2 && !fits_group) || (impl == 3 && !members) || impl < 1 || impl > 3) return fail(LTK_E_INVALID, "this GroupNorm kernel does not serve the shape");
-    float *d_gamma = nullptr, *d_beta = nullptr, *d_partial = nullptr;
-    unsigned *d_slots = nullptr, *err_host = nullptr, *err_dev = nullptr;
+    DevBuf gamma_buf, beta_buf, partial_buf, slots_buf;
+    HostWord errw;
     const int segs = gn_segments(N, C, P);
     const size_t slot_words = (size_t)N * (C / 16) * std::max(members, 1) * 8;
     hipStream_t s = e->compute;
     std::lock_guard<std::mutex> g(e->mu);
-    int rc = LTK_OK;
-    auto cleanup = [&]() {
-        if (d_gamma) (void)hipFree(d_gamma);
-        if (d_beta) (void)hipFree(d_beta);
-        if (d_partial) (void)hipFree(d_partial);
-        if (d_slots) (void)hipFree(d_slots);
-        if (err_host) (void)hipHostFree(err_host);
-    };
-    if (hipMalloc((void**)&d_gamma, C * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_beta, C * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&d_partial, (size_t)N * (C / 16) * segs * 32 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&d_slots, slot_words * sizeof(unsigned)) != hipSuccess ||
-        hipHostMalloc((void**)&err_host, sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&err_dev, err_host, 0) != hipSuccess) { cleanup(); return fail(LTK_E_HIP, "allocation failed"); }
-    *err_host = 0u;
+    if (hipMalloc(&gamma_buf.p, C * sizeof(float)) != hipSuccess || hipMalloc(&beta_buf.p, C * sizeof(float)) != hipSuccess ||
+        hipMalloc(&partial_buf.p, (size_t)N * (C / 16) * segs * 32 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&slots_buf.p, slot_words * sizeof(unsigned)) != hipSuccess || errw.create() != hipSuccess)
+        return fail(LTK_E_HIP, "allocation failed");
+    float *d_gamma = (float*)gamma_buf.p, *d_beta = (float*)beta_buf.p, *d_partial = (float*)partial_buf.p;
+    unsigned *d_slots = (unsigned*)slots_buf.p, *err_dev = errw.dev;
     (void)hipMemcpyAsync(d_gamma, gamma, C * sizeof(float), hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_beta, beta, C * sizeof(float), hipMemcpyHostToDevice, s);
     const f16* x = (const f16*)d_x;
@@ -313,23 +284,17 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
         }
     };
     run();
+    int rc = LTK_OK;
     if (iters > 0 && ms_avg) {
-        hipEvent_t t0, t1;
-        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
-        (void)hipEventRecord(t0, s);
-        for (int i = 0; i < iters; ++i) run();
-        (void)hipEventRecord(t1, s);
-        (void)hipEventSynchronize(t1);
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
+        rc = time_iters(s, iters, [&]() { run(); return 0; }, &ms);
         *ms_avg = ms / iters;
-        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     }
     const hipError_t he = hipStreamSynchronize(s);
-    if (he != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, std::string("GroupNorm kernel: ") + hipGetErrorString(he));
-    else if (*reinterpret_cast<volatile unsigned*>(err_host)) rc = fail(LTK_E_HIP, "a cooperative GroupNorm block gave up waiting for its set (gn_coop_kernel)");
-    cleanup();
-    return rc;
+    if (rc) return rc;
+    if (he != hipSuccess || hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, std::string("GroupNorm kernel: ") + hipGetErrorString(he));
+    if (*reinterpret_cast<volatile unsigned*>(errw.host)) return fail(LTK_E_HIP, "a cooperative GroupNorm block gave up waiting for its set (gn_coop_kernel)");
+    return LTK_OK;
 }
 
 int ltk_attention_f16(ltk_engine* e, const void* d_q, int q_cbt, int q_cb0, const void* d_k, int k_cbt, int k_cb0, const void* d_v, int v_cbt,
@@ -409,18 +374,9 @@ int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, flo
     CHK(hipGetLastError());
     int rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr);      // eager
     if (!rc) rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr); // captures under knob GRAPH
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (!rc && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess)) rc = fail(LTK_E_HIP, "hipEventCreate failed");
-    if (!rc) {
-        (void)hipEventRecord(t0, e->compute);
-        for (int i = 0; i < iters && !rc; ++i) rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr);
-        (void)hipEventRecord(t1, e->compute);
-    }
-    const hipError_t se = hipStreamSynchronize(e->compute);       // before the scratch buffers go
     float ms = 0.f;
-    if (!rc && se == hipSuccess) (void)hipEventElapsedTime(&ms, t0, t1);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
+    if (!rc) rc = time_iters(e->compute, iters, [&]() { return ul_pass(e, *ap, frames, true, nullptr, true, nullptr); }, &ms);
+    const hipError_t se = hipStreamSynchronize(e->compute);       // before the scratch buffers go
     if (rc) return rc;
     if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight pass: ") + hipGetErrorString(se));
     *ms_per_pass = ms / iters;
@@ -435,14 +391,10 @@ int ltk_dwconv3x3_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C
     if ((long long)N * (C / 16) > 65535 || (double)N * C * H * W >= 2147483647.0) return fail(LTK_E_INVALID, "depthwise conv: tensor too large");
     CHK(enter_device(e->device));
     std::vector<float> h((size_t)C * 11);
-    for (int c = 0; c < C; ++c) {
-        for (int t = 0; t < 9; ++t) h[((size_t)(c >> 4) * 9 + t) * 16 + (c & 15)] = weight[(size_t)c * 9 + t];
-        h[(size_t)C * 9 + c] = scale ? scale[c] : 1.f;
-        h[(size_t)C * 10 + c] = shift ? shift[c] : 0.f;
-    }
+    dw_pack(weight, scale, shift, C, C, h.data());
     DevBuf d_w;
-    CHK(hipMalloc(&d_w.p, h.size() * sizeof(float)));
-    CHK(hipMemcpy(d_w.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    const int rc = upload(h.data(), h.size() * sizeof(float), &d_w);
+    if (rc) return rc;
     std::lock_guard<std::mutex> g(e->mu);
     const float* w = (const float*)d_w.p;
     launch_dwconv3x3((const f16*)d_x, N, C / 16, 0, C, H, W, stride, w, w + (size_t)C * 9, w + (size_t)C * 10, relu, (f16*)d_y, C / 16, 0, e->compute);
@@ -482,38 +434,8 @@ int ltk_f32_to_e4m3(const float* in, size_t n, uint8_t* out) {
 int ltk_conv2d_fp8(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout,
                    const float* scale, const float* shift, float act_scale, const void* d_res, int act, void* d_y, int iters,
                    float* ms_avg) {
-    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
-    CHK(enter_device(e->device));
-    ConvPlan plan;
-    std::string err;
-    int rc = conv_plan_create(&plan, weight, Cin, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, &err, conv_fp8_quant(Cin), act_scale);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
-    ConvIO io;
-    io.partial = e->d_partial; io.partial_cap = e->partial_cap;
-    io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;   // 16-bit units
-    io.y = (f16*)d_y; io.y_ld = Cout; io.y_coff = 0;
-    io.res = (const f16*)d_res; io.res_ld = Cout; io.res_coff = 0;
-    io.relu = 0; io.act = act;
-    hipStream_t s = e->compute;
-    std::lock_guard<std::mutex> g(e->mu);
-    rc = conv_launch(plan, io, s, &err);
-    if (!rc && iters > 0 && ms_avg) {
-        hipEvent_t t0, t1;
-        (void)hipEventCreate(&t0); (void)hipEventCreate(&t1);
-        (void)hipEventRecord(t0, s);
-        for (int i = 0; i < iters && !rc; ++i) rc = conv_launch(plan, io, s, &err);
-        (void)hipEventRecord(t1, s);
-        (void)hipEventSynchronize(t1);
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, t0, t1);
-        *ms_avg = ms / iters;
-        (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
-    }
-    hipError_t he = hipStreamSynchronize(s);
-    conv_plan_destroy(&plan);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
-    if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
-    return LTK_OK;
+    return conv2d_hook(e, d_x, N, H, W, Cin, weight, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, conv_fp8_quant(Cin), act_scale, d_res, 0, act,
+                       d_y, iters, ms_avg);
 }
 
 int ltk_musetalk_forward_host(ltk_engine* e, const float* latents, const float* feat, int B, float* unet_out, float* image,
@@ -529,28 +451,20 @@ int ltk_musetalk_forward_host(ltk_engine* e, const float* latents, const float* 
     int cbt;
     f16* lat = mt_latent_in(e->mt, &cbt);
     launch_nchw_to_cb16(e->d_mt_lat, B, 8, 1024, lat, cbt, 0, s);
-    float* d_img = nullptr;
-    uint8_t* d_frames = nullptr;
-    if (image) CHK(hipMalloc((void**)&d_img, (size_t)B * 3 * 65536 * sizeof(float)));
-    if (frames) CHK(hipMalloc((void**)&d_frames, (size_t)B * 65536 * 3));
+    DevBuf d_img, d_frames;
+    if (image) CHK(hipMalloc(&d_img.p, (size_t)B * 3 * 65536 * sizeof(float)));
+    if (frames) CHK(hipMalloc(&d_frames.p, (size_t)B * 65536 * 3));
     OutList64 op;
-    for (int i = 0; i < 64; ++i) op.p[i] = (frames && i < B) ? d_frames + (size_t)i * 65536 * 3 : nullptr;
-    int rc = mt_run_locked(e, e->d_mt_feat, nullptr, B, &op, d_img);
+    for (int i = 0; i < 64; ++i) op.p[i] = (frames && i < B) ? (uint8_t*)d_frames.p + (size_t)i * 65536 * 3 : nullptr;
+    int rc = mt_run_locked(e, e->d_mt_feat, nullptr, B, &op, (float*)d_img.p);
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = fail(LTK_E_HIP, "stream sync failed");
     if (!rc && unet_out) {
         int C, ld, coff, H, W;
         f16* t = mt_named(e->mt, "conv_out", &C, &ld, &coff, &H, &W);
-        float* d_tmp = nullptr;
-        CHK(hipMalloc((void**)&d_tmp, (size_t)B * 4 * 1024 * sizeof(float)));
-        launch_nhwc_to_nchw_f32(t, B, H, W, ld, coff, 4, d_tmp, s);
-        CHK(hipStreamSynchronize(s));
-        CHK(hipMemcpy(unet_out, d_tmp, (size_t)B * 4 * 1024 * sizeof(float), hipMemcpyDeviceToHost));
-        (void)hipFree(d_tmp);
+        rc = read_cb16(e, t, B, 4, ld, coff, H, W, unet_out);          // the 4 real channels of the block
     }
-    if (!rc && image) CHK(hipMemcpy(image, d_img, (size_t)B * 3 * 65536 * sizeof(float), hipMemcpyDeviceToHost));
-    if (!rc && frames) CHK(hipMemcpy(frames, d_frames, (size_t)B * 65536 * 3, hipMemcpyDeviceToHost));
-    if (d_img) (void)hipFree(d_img);
-    if (d_frames) (void)hipFree(d_frames);
+    if (!rc && image) CHK(hipMemcpy(image, d_img.p, (size_t)B * 3 * 65536 * sizeof(float), hipMemcpyDeviceToHost));
+    if (!rc && frames) CHK(hipMemcpy(frames, d_frames.p, (size_t)B * 65536 * 3, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -559,28 +473,14 @@ int ltk_musetalk_debug_get(ltk_engine* e, const char* name, int frames, float* o
     if (!e->mt) return fail(LTK_E_STATE, "ltk_musetalk_load has not been called");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
-    int C, ld, coff, H, W;
-    f16* t = mt_named(e->mt, name, &C, &ld, &coff, &H, &W);
-    if (!t) return fail(LTK_E_STATE, std::string("no MuseTalk tensor named ") + name);
-    const size_t cnt = (size_t)frames * C * H * W;
-    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats for these frames");
-    float* d_tmp = nullptr;
-    CHK(hipMalloc((void**)&d_tmp, cnt * sizeof(float)));
-    launch_nhwc_to_nchw_f32(t, frames, H, W, ld, coff, C, d_tmp, e->compute);
-    CHK(hipStreamSynchronize(e->compute));
-    CHK(hipMemcpy(out, d_tmp, cnt * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_tmp);
-    return LTK_OK;
+    return read_named(e, e->mt, "MuseTalk", name, frames, " for these frames", out, n_floats);
 }
 
 int ltk_musetalk_op_count(ltk_engine* e) { return (e && e->mt) ? mt_op_count(e->mt) : 0; }
 
 int ltk_musetalk_op_name(ltk_engine* e, int op, char* buf, int buf_len, int* type) {
     if (!e || !e->mt || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
-    const char* n = mt_op_name(e->mt, op, type);
-    if (!n) return fail(LTK_E_INVALID, "no such op");
-    snprintf(buf, (size_t)buf_len, "%s", n);
-    return LTK_OK;
+    return copy_op_name(e->mt, op, buf, buf_len, type);
 }
 
 int ltk_musetalk_time_ops(ltk_engine* e, int frames, int iters, float* ms_per_op, int n_ops) {
@@ -590,24 +490,17 @@ int ltk_musetalk_time_ops(ltk_engine* e, int frames, int iters, float* ms_per_op
     if (n_ops != mt_op_count(e->mt)) return fail(LTK_E_INVALID, "n_ops != ltk_musetalk_op_count");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
-    std::vector<hipEvent_t> evs((size_t)n_ops + 1);
-    for (auto& ev : evs) CHK(hipEventCreate(&ev));
-    std::vector<double> acc((size_t)n_ops, 0.0);
-    int rc = mt_run(e->mt, frames, e->d_partial, e->partial_cap, e->compute);
-    for (int it = 0; it < iters && !rc; ++it) {
-        rc = mt_run_timed(e->mt, frames, e->d_partial, e->partial_cap, e->compute, &evs);
-        if (rc) break;
-        CHK(hipEventSynchronize(evs.back()));
-        for (int i = 0; i < n_ops; ++i) {
-            float ms = 0.f;
-            CHK(hipEventElapsedTime(&ms, evs[i], evs[i + 1]));
-            acc[i] += ms;
-        }
-    }
-    for (auto& ev : evs) (void)hipEventDestroy(ev);
-    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    auto run = [&](std::vector<hipEvent_t>* evs) -> int {
+        const int prc = evs ? mt_run_timed(e->mt, frames, e->d_partial, e->partial_cap, e->compute, evs)
+                            : mt_run(e->mt, frames, e->d_partial, e->partial_cap, e->compute);
+        return prc ? fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt)) : 0;
+    };
+    std::vector<float> ms((size_t)n_ops);
+    int rc = run(nullptr);                                               // warm
+    if (!rc) rc = time_intervals(n_ops, iters, run, ms.data());
+    if (rc) return rc;
     if (mt_gn_error(e->mt)) return fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
-    for (int i = 0; i < n_ops; ++i) ms_per_op[i] = (float)(acc[i] / iters);
+    memcpy(ms_per_op, ms.data(), ms.size() * sizeof(float));
     return LTK_OK;
 }
 
@@ -617,24 +510,16 @@ int ltk_musetalk_time(ltk_engine* e, int frames, int iters, float* ms_per_pass, 
     if (frames > e->mt_max_frames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
-    hipEvent_t t0, t1;
-    CHK(hipEventCreate(&t0));
-    CHK(hipEventCreate(&t1));
     // as ltk_musetalk_infer enqueues the program: eagerly the first time a frame count is seen, then captured, then replayed
-    int rc = run_program(e, e->mt, frames);
-    if (!rc) rc = run_program(e, e->mt, frames);
-    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
-    CHK(hipEventRecord(t0, e->compute));
-    for (int i = 0; i < iters && !rc; ++i) rc = run_program(e, e->mt, frames);
-    if (rc) return fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
-    CHK(hipEventRecord(t1, e->compute));
-    CHK(hipEventSynchronize(t1));
-    if (mt_gn_error(e->mt)) return fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
+    auto pass = [&]() -> int { return run_program(e, e->mt, frames) ? fail(LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt)) : 0; };
+    int rc = pass();
+    if (!rc) rc = pass();
     float ms = 0.f;
-    CHK(hipEventElapsedTime(&ms, t0, t1));
+    if (!rc) rc = time_iters(e->compute, iters, pass, &ms);
+    if (rc) return rc;
+    if (mt_gn_error(e->mt)) return fail(LTK_E_HIP, std::string("musetalk: ") + mt_graph_error(e->mt));
     *ms_per_pass = ms / iters;
     if (macs_per_pass) *macs_per_pass = mt_macs_per_frame(e->mt) * frames;
-    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     return LTK_OK;
 }
 
@@ -643,18 +528,7 @@ int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_
     if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
-    int C, ld, coff, H, W;
-    f16* t = (std::string(name) == "input_features") ? mt_named(e->whisper, "input_features", &C, &ld, &coff, &H, &W) : mt_named(e->whisper, name, &C, &ld, &coff, &H, &W);
-    if (!t) return fail(LTK_E_STATE, std::string("no Whisper tensor named ") + name);
-    const size_t cnt = (size_t)C * H * W;
-    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats");
-    float* d_tmp = nullptr;
-    CHK(hipMalloc((void**)&d_tmp, cnt * sizeof(float)));
-    launch_nhwc_to_nchw_f32(t, 1, H, W, ld, coff, C, d_tmp, e->compute);
-    CHK(hipStreamSynchronize(e->compute));
-    CHK(hipMemcpy(out, d_tmp, cnt * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_tmp);
-    return LTK_OK;
+    return read_named(e, e->whisper, "Whisper", name, 1, "", out, n_floats);
 }
 
 // ---------------------------------------------------------------- HuBERT: the program's tensors and ops, and its kernels on their own
@@ -672,17 +546,7 @@ int ltk_hubert_debug_get(ltk_engine* e, const char* name, float* out, size_t n_f
         CHK(hipMemcpy(out, mt_hubert_pcm_in(e->hubert_last), n * sizeof(float), hipMemcpyDeviceToHost));
         return LTK_OK;
     }
-    int C, ld, coff, H, W;
-    f16* t = mt_named(e->hubert_last, name, &C, &ld, &coff, &H, &W);
-    if (!t) return fail(LTK_E_STATE, std::string("no HuBERT tensor named ") + name);
-    const size_t cnt = (size_t)C * H * W;
-    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats");
-    DevBuf tmp;
-    CHK(hipMalloc(&tmp.p, cnt * sizeof(float)));
-    launch_nhwc_to_nchw_f32(t, 1, H, W, ld, coff, C, (float*)tmp.p, e->compute);
-    CHK(hipStreamSynchronize(e->compute));
-    CHK(hipMemcpy(out, tmp.p, cnt * sizeof(float), hipMemcpyDeviceToHost));
-    return LTK_OK;
+    return read_named(e, e->hubert_last, "HuBERT", name, 1, "", out, n_floats);
 }
 
 int ltk_hubert_op_count(ltk_engine* e) {
@@ -695,10 +559,7 @@ int ltk_hubert_op_name(ltk_engine* e, int op, char* buf, int buf_len, int* type)
     if (!e || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
     std::lock_guard<std::mutex> g(e->mu);
     if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
-    const char* n = mt_op_name(e->hubert_w, op, type);
-    if (!n) return fail(LTK_E_INVALID, "no such op");
-    snprintf(buf, (size_t)buf_len, "%s", n);
-    return LTK_OK;
+    return copy_op_name(e->hubert_w, op, buf, buf_len, type);
 }
 
 int ltk_hubert_info(ltk_engine* e, int* layers, int* programs, size_t* activation_bytes) {
@@ -716,9 +577,9 @@ int ltk_hubert_stats(ltk_engine* e, const float* pcm, long long n, float* mean_v
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
     DevBuf x, st;
-    CHK(hipMalloc(&x.p, (size_t)n * sizeof(float)));
+    const int rc = upload(pcm, (size_t)n * sizeof(float), &x);
+    if (rc) return rc;
     CHK(hipMalloc(&st.p, 2 * sizeof(float)));
-    CHK(hipMemcpy(x.p, pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     launch_hubert_stats((const float*)x.p, n, (float*)st.p, e->compute);
     CHK(hipGetLastError());
     CHK(hipStreamSynchronize(e->compute));
@@ -728,26 +589,12 @@ int ltk_hubert_stats(ltk_engine* e, const float* pcm, long long n, float* mean_v
 
 namespace {
 
-// host fp32 [T][C] -> a CB16 device tensor; a CB16 device tensor -> host fp32 [C][T]
+// host fp32 [T][C] -> a CB16 device tensor (back: read_cb16, host fp32 [C][T])
 int hb_up(ltk_engine* e, const float* host, int T, int C, DevBuf* stage, DevBuf* cb) {
-    CHK(hipMalloc(&stage->p, (size_t)T * C * sizeof(float)));
+    const int rc = upload(host, (size_t)T * C * sizeof(float), stage);
+    if (rc) return rc;
     CHK(hipMalloc(&cb->p, (size_t)T * C * sizeof(f16)));
-    CHK(hipMemcpy(stage->p, host, (size_t)T * C * sizeof(float), hipMemcpyHostToDevice));
     launch_tokens_to_cb16((const float*)stage->p, 1, T, C, nullptr, (f16*)cb->p, C / 16, 0, e->compute);
-    return LTK_OK;
-}
-int hb_down(ltk_engine* e, const f16* cb, int T, int C, float* host) {
-    DevBuf tmp;
-    CHK(hipMalloc(&tmp.p, (size_t)T * C * sizeof(float)));
-    launch_nhwc_to_nchw_f32(cb, 1, T, 1, C, 0, C, (float*)tmp.p, e->compute);
-    CHK(hipGetLastError());
-    CHK(hipStreamSynchronize(e->compute));
-    CHK(hipMemcpy(host, tmp.p, (size_t)T * C * sizeof(float), hipMemcpyDeviceToHost));
-    return LTK_OK;
-}
-int hb_vec(const float* host, size_t n, DevBuf* d) {
-    CHK(hipMalloc(&d->p, n * sizeof(float)));
-    CHK(hipMemcpy(d->p, host, n * sizeof(float), hipMemcpyHostToDevice));
     return LTK_OK;
 }
 
@@ -760,16 +607,16 @@ int ltk_hubert_layer0_host(ltk_engine* e, const float* x, int n, const float* w,
     std::lock_guard<std::mutex> g(e->mu);
     const int L0 = (n - 10) / 5 + 1;
     DevBuf dx, dw, db, dg, de, dy;
-    int rc = hb_vec(x, (size_t)n, &dx);
-    if (!rc) rc = hb_vec(w, 5120, &dw);
-    if (!rc) rc = hb_vec(bias, 512, &db);
-    if (!rc) rc = hb_vec(gamma, 512, &dg);
-    if (!rc) rc = hb_vec(beta, 512, &de);
+    int rc = upload(x, (size_t)n * sizeof(float), &dx);
+    if (!rc) rc = upload(w, 5120 * sizeof(float), &dw);
+    if (!rc) rc = upload(bias, 512 * sizeof(float), &db);
+    if (!rc) rc = upload(gamma, 512 * sizeof(float), &dg);
+    if (!rc) rc = upload(beta, 512 * sizeof(float), &de);
     if (rc) return rc;
     CHK(hipMalloc(&dy.p, (size_t)L0 * 512 * sizeof(f16)));
     launch_hubert_layer0((const float*)dx.p, n, (const float*)dw.p, (const float*)db.p, (const float*)dg.p, (const float*)de.p, 1e-5f,
                          (f16*)dy.p, e->compute);
-    return hb_down(e, (const f16*)dy.p, L0, 512, out);
+    return read_cb16(e, (const f16*)dy.p, 1, 512, 512, 0, L0, 1, out);
 }
 
 int ltk_hubert_ln_gelu_host(ltk_engine* e, const float* x, int T, const float* gamma, const float* beta, float* out) {
@@ -778,12 +625,12 @@ int ltk_hubert_ln_gelu_host(ltk_engine* e, const float* x, int T, const float* g
     std::lock_guard<std::mutex> g(e->mu);
     DevBuf st, dx, dg, de, dy;
     int rc = hb_up(e, x, T, 512, &st, &dx);
-    if (!rc) rc = hb_vec(gamma, 512, &dg);
-    if (!rc) rc = hb_vec(beta, 512, &de);
+    if (!rc) rc = upload(gamma, 512 * sizeof(float), &dg);
+    if (!rc) rc = upload(beta, 512 * sizeof(float), &de);
     if (rc) return rc;
     CHK(hipMalloc(&dy.p, (size_t)T * 512 * sizeof(f16)));
     launch_ln_gelu512((const f16*)dx.p, 0, T, 1e-5f, (const float*)dg.p, (const float*)de.p, (f16*)dy.p, 0, e->compute);
-    return hb_down(e, (const f16*)dy.p, T, 512, out);
+    return read_cb16(e, (const f16*)dy.p, 1, 512, 512, 0, T, 1, out);
 }
 
 int ltk_hubert_posconv_host(ltk_engine* e, const float* x, int T, const float* w, const float* bias, float* out) {
@@ -792,17 +639,16 @@ int ltk_hubert_posconv_host(ltk_engine* e, const float* x, int T, const float* w
     std::lock_guard<std::mutex> g(e->mu);
     DevBuf st, dx, dw, db, dy;
     int rc = hb_up(e, x, T, 1024, &st, &dx);
-    if (!rc) rc = hb_vec(bias, 1024, &db);
-    if (rc) return rc;
-    {
+    if (!rc) rc = upload(bias, 1024 * sizeof(float), &db);
+    if (!rc) {
         std::vector<f16> packed(kPosConvPackHalfs);
         hubert_posconv_pack(w, packed.data());
-        CHK(hipMalloc(&dw.p, packed.size() * sizeof(f16)));
-        CHK(hipMemcpy(dw.p, packed.data(), packed.size() * sizeof(f16), hipMemcpyHostToDevice));
+        rc = upload(packed.data(), packed.size() * sizeof(f16), &dw);
     }
+    if (rc) return rc;
     CHK(hipMalloc(&dy.p, (size_t)T * 1024 * sizeof(f16)));
     launch_hubert_posconv((const f16*)dx.p, 0, T, (const f16*)dw.p, (const float*)db.p, (f16*)dy.p, 0, e->compute);
-    return hb_down(e, (const f16*)dy.p, T, 1024, out);
+    return read_cb16(e, (const f16*)dy.p, 1, 1024, 1024, 0, T, 1, out);
 }
 
 int ltk_hubert_chunks_host(ltk_engine* e, const float* feat, int T, int batch, int first_row, int row_step, int rows, float* out) {

@@ -23,6 +23,7 @@
 #include "misc_kernels.h"
 #include "musetalk.h"
 #include "nn_kernels.h"
+#include "state_dict.h"
 #include "tune.h"
 
 namespace ltk {

@@ -1,4 +1,4 @@
-// HuBERT-large as a device program over MtGraph (compiled as part of musetalk.hip's translation unit, which defines MtGraph).
+// HuBERT-large as a device program over MtGraph (mt_graph.h).
 //
 // transformers HubertModel, configuration of facebook/hubert-large-ls960-ft (feat_extract_norm="layer", conv_bias,
 // do_stable_layer_norm, feat_proj_layer_norm), called as avatars/ultralight/audio2feature.py:35,45 calls it: no attention mask,
@@ -16,6 +16,11 @@
 // graph mt_build_hubert_weights builds: every program is built over it (MtGraph::share) and owns its activations and op list only.
 // Nothing is reused between the activations of a program: a 1000-row program (the 320 080-sample clip) holds 0.19 GB of
 // feature-extractor maps and 25 MB per encoder layer, 0.79 GB at 24 layers.
+#include <math.h>
+
+#include "mt_graph.h"
+#include "hubert_kernels.h"
+
 namespace ltk {
 
 namespace {
@@ -175,11 +180,6 @@ float* mt_hubert_pcm_in(MtGraph* g) { return reinterpret_cast<float*>(g->bufs[g-
 f16* mt_hubert_out(MtGraph* g, int* cbt, int* cb0) {
     *cbt = g->hb_out->ld / 16; *cb0 = g->hb_out->coff / 16;
     return g->bufs[g->hb_out->buf];
-}
-size_t mt_activation_bytes(const MtGraph* g) {
-    size_t b = 0;
-    for (size_t h : g->buf_halfs) b += h * (size_t)std::max(g->frames, 1) * sizeof(f16);
-    return b + g->vt_halfs * sizeof(f16);
 }
 
 }  // namespace ltk

@@ -1,6 +1,6 @@
 // HuBERT-large front-end kernels (hubert_kernels.h): transformers HubertModel with feat_extract_norm="layer",
 // do_stable_layer_norm=True as avatars/ultralight/audio2feature.py calls it.  The linear layers, the stride-2 convs of layers 1-6,
-// the LayerNorms of the encoder and the attention are the MuseTalk / Whisper kernels (musetalk.hip mt_build_hubert); what is here
+// the LayerNorms of the encoder and the attention are the MuseTalk / Whisper kernels (hubert.hip mt_build_hubert); what is here
 // is the rest.
 #include "hubert_kernels.h"
 

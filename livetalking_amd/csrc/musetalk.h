@@ -1,4 +1,5 @@
-// MuseTalk device program (musetalk.hip): graph construction from diffusers-named state dicts and execution.
+// The device programs over MtGraph as the engine's sources see them: the opaque handle, execution (mt_graph.hip) and graph construction
+// from a model's state dict (musetalk.hip: U-Net + VAE; whisper.hip; hubert.hip).  The graph itself is mt_graph.h.
 #pragma once
 #include <vector>
 #include <hip/hip_runtime.h>

@@ -4,9 +4,8 @@
 // eval-mode BatchNorm folded into scale / shift at register time; torch.cat is a channel-block range of a shared buffer, the
 // bilinear upsample writes straight into it.  The model is per avatar (ultralight_avatar.py:69-70), so the program is built by
 // ltk_ultralight_avatar_register and owned by the avatar; the activation arena and the pointer tables belong to the engine.
-// Compiled as part of engine.hip (included at its end), together with the kernels in dw_kernels.hip.
+// Its VALU kernels are dw_kernels.hip; what the other engine sources call is declared in engine_internal.h.
 #include "engine_internal.h"
-#include "dw_kernels.hip"
 
 namespace ltk {
 
@@ -54,33 +53,18 @@ const float kUlBnEps = 1e-5f;     // nn.BatchNorm2d default (unet.py:17,26,29)
 struct Tn { int buf, ld, coff, C, H, W; };     // a tensor = channels [coff, coff + C) of a buffer of ld channels
 
 struct Builder {
-    const ltk_named_tensor* sd;
-    int n;
+    SD sd;              // (ltk_ultralight_avatar_register has checked that every entry has a name and data)
     UlProgram* p;
 
-    const float* find(const std::string& name, size_t expect) const {
-        for (int i = 0; i < n; ++i)
-            if (sd[i].name && name == sd[i].name) {
-                if (!sd[i].data) return nullptr;
-                size_t cnt = 1;
-                for (int d = 0; d < sd[i].ndim; ++d) cnt *= (size_t)sd[i].shape[d];
-                return cnt == expect ? sd[i].data : nullptr;
-            }
-        return nullptr;
-    }
-    // BatchNorm2d eval folded: y = (x + bias - mean) / sqrt(var + eps) * gamma + beta
-    int fold_bn(const std::string& bn, int C, const float* bias, std::vector<float>* sc, std::vector<float>* sf) const {
-        const float* g = find(bn + ".weight", C);
-        const float* b = find(bn + ".bias", C);
-        const float* m = find(bn + ".running_mean", C);
-        const float* v = find(bn + ".running_var", C);
+    // the BatchNorm2d `bn` behind a conv with `bias` (or null), folded (state_dict.h)
+    int fold_bn(const std::string& bn, int C, const float* bias, std::vector<float>* sc, std::vector<float>* sf) {
+        const float* g = sd.get(bn + ".weight", C);
+        const float* b = sd.get(bn + ".bias", C);
+        const float* m = sd.get(bn + ".running_mean", C);
+        const float* v = sd.get(bn + ".running_var", C);
         if (!g || !b || !m || !v) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) the BatchNorm tensors " + bn + ".*");
         sc->resize(C); sf->resize(C);
-        for (int c = 0; c < C; ++c) {
-            const float s = g[c] / sqrtf(v[c] + kUlBnEps);
-            (*sc)[c] = s;
-            (*sf)[c] = ((bias ? bias[c] : 0.f) - m[c]) * s + b[c];
-        }
+        ltk::fold_bn(g, b, m, v, bias, kUlBnEps, C, sc->data(), sf->data());
         return 0;
     }
     void note(const UlOp& op) {
@@ -91,8 +75,8 @@ struct Builder {
     // dense conv (1x1 or 3x3) + folded BN (+ conv bias) + optional ReLU / residual
     int conv(const std::string& wname, const std::string& bn, bool has_bias, const Tn& in, int cout, int k, int stride, int pad, int relu,
              const Tn* res, int out_buf, int out_ld, int out_coff, Tn* out) {
-        const float* w = find(wname + ".weight", (size_t)cout * in.C * k * k);
-        const float* bias = has_bias ? find(wname + ".bias", cout) : nullptr;
+        const float* w = sd.get(wname + ".weight", (size_t)cout * in.C * k * k);
+        const float* bias = has_bias ? sd.get(wname + ".bias", cout) : nullptr;
         if (!w || (has_bias && !bias)) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + wname + ".weight / .bias");
         std::vector<float> sc, sf;
         int rc = fold_bn(bn, cout, bias, &sc, &sf);
@@ -116,17 +100,13 @@ struct Builder {
     // depthwise 3x3 + BN + ReLU over `Cpad` layout channels of which the first C are the reference's (the rest: zero weights)
     int dw(const std::string& wname, const std::string& bn, const Tn& in, int C, int stride, int out_buf, Tn* out) {
         const int Cpad = (C + 15) / 16 * 16;
-        const float* w = find(wname + ".weight", (size_t)C * 9);
+        const float* w = sd.get(wname + ".weight", (size_t)C * 9);
         if (!w) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + wname + ".weight");
         std::vector<float> sc, sf;
         int rc = fold_bn(bn, C, nullptr, &sc, &sf);
         if (rc) return rc;
-        std::vector<float> h((size_t)Cpad * 11, 0.f);
-        for (int c = 0; c < C; ++c) {
-            for (int t = 0; t < 9; ++t) h[((size_t)(c >> 4) * 9 + t) * 16 + (c & 15)] = w[(size_t)c * 9 + t];
-            h[(size_t)Cpad * 9 + c] = sc[c];
-            h[(size_t)Cpad * 10 + c] = sf[c];
-        }
+        std::vector<float> h((size_t)Cpad * 11);
+        dw_pack(w, sc.data(), sf.data(), C, Cpad, h.data());
         p->ops.emplace_back();
         UlOp& op = p->ops.back();
         op.type = UL_DW; op.name = wname;
@@ -148,7 +128,7 @@ struct Builder {
         Tn e1, e2;
         int rc;
         if (in.C == 6) {        // inc: the expand conv reads the bank crop itself (UL_IN); 12 channels live in one 16-channel block
-            const float* w = find(pre + ".conv.0.weight", 72);
+            const float* w = sd.get(pre + ".conv.0.weight", 72);
             if (!w) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + pre + ".conv.0.weight");
             std::vector<float> sc, sf;
             if ((rc = fold_bn(pre + ".conv.1", 12, nullptr, &sc, &sf))) return rc;
@@ -193,7 +173,7 @@ struct Builder {
 
 // unet.py:168-215 Model.forward
 int build_ul_program(UlProgram* p, const ltk_named_tensor* sd, int n) {
-    Builder b{sd, n, p};
+    Builder b{SD{sd, n, ""}, p};
     int rc;
     const int R = kUlRes;
     // ---- face path (unet.py:200-204): every level's output is the skip half of the matching Up's concat buffer
@@ -235,8 +215,8 @@ int build_ul_program(UlProgram* p, const ltk_named_tensor* sd, int n) {
     }
     if (f.H != R || f.C != 32) return fail(LTK_E_INVALID, "ultralight program: output geometry");
     // ---- outc + sigmoid (unet.py:213-214)
-    const float* hw = b.find("outc.conv.weight", 96);
-    const float* hb = b.find("outc.conv.bias", 3);
+    const float* hw = b.sd.get("outc.conv.weight", 96);
+    const float* hb = b.sd.get("outc.conv.bias", 3);
     if (!hw || !hb) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) outc.conv.{weight,bias}");
     memcpy(p->headw.w, hw, 96 * sizeof(float));
     memcpy(p->headw.b, hb, 3 * sizeof(float));

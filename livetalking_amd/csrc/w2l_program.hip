@@ -147,18 +147,6 @@ void apply_tile_table_impl(std::vector<Layer>& layers) {
 }
 
 
-const float* find_tensor(const ltk_named_tensor* sd, int n, const std::string& name, size_t expect) {
-    for (int i = 0; i < n; ++i) {
-        if (name == sd[i].name) {
-            size_t cnt = 1;
-            for (int d = 0; d < sd[i].ndim; ++d) cnt *= (size_t)sd[i].shape[d];
-            if (cnt != expect) return nullptr;
-            return sd[i].data;
-        }
-    }
-    return nullptr;
-}
-
 // `hint_hw`: pixels per image of the layer's input map.  `flat_ld` > 0: the k x k "valid" conv that collapses a
 // k x k map to 1x1 (face_encoder_blocks.7.0) is run as a 1x1 conv over the map viewed as ONE pixel of
 // k*k*cin channels (a channel-blocked k x k map is contiguous per channel block).
@@ -166,21 +154,17 @@ const float* find_tensor(const ltk_named_tensor* sd, int n, const std::string& n
 int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* sd, int n, Layer* L, int hint_hw, int flat_ld, int map_w) {
     const std::string p = d.prefix;
     const size_t wcount = (size_t)d.cin * d.cout * d.k * d.k;
-    const float* w = find_tensor(sd, n, p + ".conv_block.0.weight", wcount);
-    const float* b = find_tensor(sd, n, p + ".conv_block.0.bias", d.cout);
-    const float* g = find_tensor(sd, n, p + ".conv_block.1.weight", d.cout);
-    const float* beta = find_tensor(sd, n, p + ".conv_block.1.bias", d.cout);
-    const float* mean = find_tensor(sd, n, p + ".conv_block.1.running_mean", d.cout);
-    const float* var = find_tensor(sd, n, p + ".conv_block.1.running_var", d.cout);
+    SD dict{sd, n, ""};
+    const float* w = dict.get(p + ".conv_block.0.weight", wcount);
+    const float* b = dict.get(p + ".conv_block.0.bias", d.cout);
+    const float* g = dict.get(p + ".conv_block.1.weight", d.cout);
+    const float* beta = dict.get(p + ".conv_block.1.bias", d.cout);
+    const float* mean = dict.get(p + ".conv_block.1.running_mean", d.cout);
+    const float* var = dict.get(p + ".conv_block.1.running_var", d.cout);
     if (!w || !b || !g || !beta || !mean || !var)
         return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) tensors of layer " + p);
     std::vector<float> sc(d.cout), sf(d.cout);
-    for (int c = 0; c < d.cout; ++c) {
-        // BatchNorm2d eval: y = (x - mean)/sqrt(var+eps)*gamma + beta, x = conv + bias
-        const float s = g[c] / sqrtf(var[c] + kBnEps);
-        sc[c] = s;
-        sf[c] = (b[c] - mean[c]) * s + beta[c];
-    }
+    fold_bn(g, beta, mean, var, b, kBnEps, d.cout, sc.data(), sf.data());
     std::string err;
     int rc;
     // Residual blocks (conv.py:16-17: out = relu(bn(conv(x)) + x), x = the block's own input): with
@@ -477,8 +461,9 @@ int build_program(ltk_engine* e, const ltk_named_tensor* sd, int n) {
         e->layers.push_back(L);
     }
     // head: plain nn.Conv2d(32,3,1) (wav2lip_v2.py:90)
-    const float* hw = find_tensor(sd, n, "output_block.1.weight", 96);
-    const float* hb = find_tensor(sd, n, "output_block.1.bias", 3);
+    SD dict{sd, n, ""};
+    const float* hw = dict.get("output_block.1.weight", 96);
+    const float* hb = dict.get("output_block.1.bias", 3);
     if (!hw || !hb) return fail(LTK_E_INVALID, "state_dict is missing output_block.1.{weight,bias}");
     std::vector<float> h(99);
     memcpy(h.data(), hw, 96 * sizeof(float));

@@ -563,7 +563,14 @@ def test_kernel_resources_script_follows_the_makefile():
         for o in objs.split():
             extra.setdefault(o.replace(".o", ".hip"), []).extend(flags.split())
     assert kr.EXTRA == extra
-    assert set(kr.makefile_sources()) >= set(extra) and len(kr.makefile_sources()) == 15
+    assert set(kr.makefile_sources()) >= set(extra)
+    # every source is a translation unit of its own: all of csrc/*.hip is in SRCS (once each), and nothing includes a .hip
+    csrc = os.path.join(root, "livetalking_amd", "csrc")
+    assert sorted(kr.makefile_sources()) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")) or f == "Makefile":
+            with open(os.path.join(csrc, f)) as fh:
+                assert not re.search(r'^\s*#\s*include\s*["<][^">]*\.hip[">]', fh.read(), re.M), f
     # the name shortener on the two kinds of names the compiler's remarks carry
     assert kr.pretty("_ZN3ltk14convs2d_kernelILi2EEEvPKDF16_ii", "_ZN3ltk14convs2d_kernelILi2EEEvPKDF16_ii") == "ltk::convs2d_kernel<2>"
     assert kr.pretty("x", "void ltk::conv7_kernel<true>(ltk::C7Args, ltk::FacePtrs const*)") == "ltk::conv7_kernel<true>"
