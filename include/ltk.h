@@ -442,6 +442,39 @@ int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
                    int transposed, int out_pad, const float* scale, const float* shift,
                    const void* d_res, int relu, void* d_y, int iters, float* ms_avg);
 
+/* The same fp16 conv with the caller saying WHAT runs and the hook reporting what ran (kernel unit tests).  `opts`:
+ *   x_ld, x_coff / y_ld, y_coff / res_ld, res_coff : the tensor is channels [coff, coff + C) of a channel-blocked buffer of `ld` channels
+ *                  (multiples of 16); ld = 0: contiguous, as ltk_conv2d_f16
+ *   act          : 0 none, 1 ReLU, 2 GELU (erf), 3 SiLU (`relu` != 0 is shorthand for 1)
+ *   ups          : 0; 1 = d_x is the H/2 x W/2 source map, read through a nearest 2x upsample; 2 = the same as the four-phase plan
+ *                  (2x2 taps per output phase on the source map); H, W are the upsampled size in both
+ *   force_pxw, force_nbt, force_ksplit : the per-layer tile table's fields, handed to the launch as the programs hand theirs (0 = rule).
+ *                  A forced tile conv3 has no instantiation for is refused (LTK_E_INVALID), never replaced
+ *   family       : 0 the conv kernels; 1 rowgemm (1x1 map, 1x1 conv, <= 32 frames), 2 rowconv (3x3 pad 1, stride 1 / 2, output map
+ *                  <= 8 x 8), 3 rowconvT (ConvTranspose2d k3 s2 p1 op1, source map <= 8 x 8), their plans built from the torch-layout
+ *                  weight as the Wav2Lip program builds them
+ * `rep` (may be NULL): family as asked; conv3: kernel = the instantiation's name as ltk_debug_conv3_variants spells it, its template
+ * arguments G, NBT, PXW, NC8, T, S, the effective split factor, the work items and the grid; rowgemm / rowconv / rowconvT: kernel and
+ * the instantiation's FT / UB; kernel = "" where another kernel served the layer. */
+typedef struct ltk_conv_opts {
+    int x_ld, x_coff, y_ld, y_coff, res_ld, res_coff;
+    int act, ups;
+    int force_pxw, force_nbt, force_ksplit;
+    int family;
+} ltk_conv_opts;
+typedef struct ltk_conv_report {
+    char kernel[64];
+    int family, G, NBT, PXW, NC8, T, S, ksplit, items, grid, FT, UB;
+} ltk_conv_report;
+int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
+                      const float* weight, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                      int transposed, int out_pad, const float* scale, const float* shift,
+                      const void* d_res, int relu, void* d_y, const ltk_conv_opts* opts, ltk_conv_report* rep);
+
+/* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
+ * Returns LTK_E_INVALID when cap is too small. */
+int ltk_debug_conv3_variants(char* buf, int cap);
+
 /* Standalone GroupNorm (+ SiLU) over a channel-blocked fp16 tensor, for kernel unit tests and timing (diffusers GroupNorm as the MuseTalk U-Net / VAE
  * use it; `avatars/musetalk/models/unet.py:36-46`, `vae.py:96-108` call sites).  x, y: device fp16 [N][C/16][P][16]; gamma / beta host fp32 [C];
  * impl: 0 = what the MuseTalk program would pick for this shape, 1 = gn_stats + gn_apply (two launches, three tensor passes), 2 = gn_group_kernel

@@ -41,6 +41,16 @@ class EgressReq(C.Structure):
                 ("speaking", C.c_int), ("alpha", C.c_double), ("keep", C.c_int), ("format", C.c_int), ("chroma", C.c_int)]
 
 
+class ConvOpts(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff", "res_ld", "res_coff", "act", "ups", "force_pxw", "force_nbt",
+                                       "force_ksplit", "family")]
+
+
+class ConvReport(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64)] + [(n, C.c_int) for n in ("family", "G", "NBT", "PXW", "NC8", "T", "S", "ksplit", "items", "grid",
+                                                                     "FT", "UB")]
+
+
 # every symbol include/ltk.h declares: (restype, argtypes)
 SYMBOLS = {
     "ltk_last_error": (C.c_char_p, []),
@@ -123,6 +133,10 @@ SYMBOLS = {
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                  C.POINTER(C.c_float)]),
+    "ltk_conv2d_f16_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
+    "ltk_debug_conv3_variants": (C.c_int, [C.c_char_p, C.c_int]),
     "ltk_groupnorm_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "ltk_attention_f16": (C.c_int, [C.c_void_p] + [C.c_void_p, C.c_int, C.c_int] * 4 + [C.c_int] * 6),

@@ -41,6 +41,7 @@
 #include "tune.h"
 
 #include <hip/hip_fp16.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1306,19 +1307,41 @@ __global__ __launch_bounds__(512, 1) void lin_mp_kernel(const K3Args a, const in
 // ------------------------------------------------------------------------------------------
 typedef void (*k3_kernel_t)(const K3Args);
 
-static k3_kernel_t k3_pick(int G, int NBT, int PXW, int NC8, int T) {
-#define K3CASE(g, n, p, c, t) \
-    if (G == g && NBT == n && PXW == p && NC8 == c && T == t) return (k3_kernel_t)conv3_kernel<g, n, p, c, t>
-    K3CASE(1, 2, 4, 2, 9); K3CASE(1, 2, 2, 2, 9); K3CASE(1, 1, 4, 2, 9); K3CASE(1, 1, 2, 2, 9);
-    K3CASE(1, 2, 2, 4, 9); K3CASE(1, 1, 2, 4, 9);
-    K3CASE(1, 2, 1, 2, 9); K3CASE(1, 1, 1, 2, 9); K3CASE(1, 2, 1, 4, 9); K3CASE(1, 1, 1, 4, 9);      // 128-pixel tiles (small maps)
-    K3CASE(1, 2, 2, 8, 1); K3CASE(1, 1, 2, 8, 1); K3CASE(1, 2, 2, 2, 1); K3CASE(1, 1, 2, 2, 1);
-    K3CASE(1, 4, 2, 4, 1); K3CASE(1, 2, 2, 4, 1); K3CASE(1, 1, 2, 4, 1);
-    K3CASE(4, 1, 2, 2, 9); K3CASE(4, 1, 2, 4, 9);
-    K3CASE(4, 1, 2, 2, 16);                             // upsample + conv as four phases (ConvPlan::ups4)
+// THE table of fp16 instantiations, X(G, NBT, PXW, NC8, T, S): the pickers below and conv3_variant_names() (what a test has to
+// see launched, ltk_debug_conv3_variants) are both made of it, so an instantiation cannot be in one and not in the other.
+#define K3_F16_VARIANTS(X) \
+    X(1, 2, 4, 2, 9, 1) X(1, 2, 2, 2, 9, 1) X(1, 1, 4, 2, 9, 1) X(1, 1, 2, 2, 9, 1) \
+    X(1, 2, 2, 4, 9, 1) X(1, 1, 2, 4, 9, 1) \
+    X(1, 2, 1, 2, 9, 1) X(1, 1, 1, 2, 9, 1) X(1, 2, 1, 4, 9, 1) X(1, 1, 1, 4, 9, 1)      /* 128-pixel tiles (small maps) */ \
+    X(1, 2, 2, 8, 1, 1) X(1, 1, 2, 8, 1, 1) X(1, 2, 2, 2, 1, 1) X(1, 1, 2, 2, 1, 1) \
+    X(1, 4, 2, 4, 1, 1) X(1, 2, 2, 4, 1, 1) X(1, 1, 2, 4, 1, 1) \
+    X(4, 1, 2, 2, 9, 1) X(4, 1, 2, 4, 9, 1) \
+    X(4, 1, 2, 2, 16, 1)                                /* upsample + conv as four phases (ConvPlan::ups4) */ \
+    X(1, 2, 2, 2, 9, 2) X(1, 1, 2, 2, 9, 2)             /* 3x3 stride 2 (face-encoder / U-Net downsamples): PXW = 2 */
+
+static k3_kernel_t k3_pick_f16(int G, int NBT, int PXW, int NC8, int T, int S) {
+#define K3CASE(g, n, p, c, t, s) \
+    if (G == g && NBT == n && PXW == p && NC8 == c && T == t && S == s) return (k3_kernel_t)conv3_kernel<g, n, p, c, t, s>;
+    K3_F16_VARIANTS(K3CASE)
 #undef K3CASE
     return nullptr;
 }
+
+static std::string k3_name(int G, int NBT, int PXW, int NC8, int T, int S) {
+    char b[64];
+    snprintf(b, sizeof(b), "conv3_kernel<%d,%d,%d,%d,%d,%d>", G, NBT, PXW, NC8, T, S);
+    return b;
+}
+
+std::string conv3_variant_names() {
+    std::string out;
+#define K3NAME(g, n, p, c, t, s) out += k3_name(g, n, p, c, t, s) + "\n";
+    K3_F16_VARIANTS(K3NAME)
+#undef K3NAME
+    return out;
+}
+
+static k3_kernel_t k3_pick(int G, int NBT, int PXW, int NC8, int T) { return k3_pick_f16(G, NBT, PXW, NC8, T, 1); }
 
 static k3_kernel_t k3_pick_q8(int NBT, int PXW, int NC8) {     // fp8 operands: 3x3 stride 1
 #define K3Q(n, p, c) if (NBT == n && PXW == p && NC8 == c) return (k3_kernel_t)conv3_kernel<1, n, p, c, 9, 1, 1>
@@ -1335,8 +1358,7 @@ static k3_kernel_t k3_pick_mx(int NBT, int PXW) {     // MX-scaled fp8 operands:
 }
 
 static k3_kernel_t k3_pick_s2(int NBT, int NC8) {     // 3x3 stride 2 pad 1 (face-encoder / U-Net downsamples): PXW = 2
-    if (NC8 == 2) return NBT == 2 ? (k3_kernel_t)conv3_kernel<1, 2, 2, 2, 9, 2> : (k3_kernel_t)conv3_kernel<1, 1, 2, 2, 9, 2>;
-    return nullptr;
+    return k3_pick_f16(1, NBT, 2, NC8, 9, 2);
 }
 
 static int ceil_log2_(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
@@ -1522,6 +1544,12 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     // (1x1 / linear layers on >= 1024 pixels: below one item per CU; MuseTalk's 640-channel projections on 4096 tokens are 10 %
     // faster as 320 items of 256 px x 32 ch than as 160 of 256 x 64)
     if (NBT == 2 && blocks * ((p.lCout + 63) / 64) < ((T == 1 && blocks >= 4) ? 256 : 128) && !conv3x3 && !forced_tile) NBT = 1;
+    // the test hook names its tile: one the rules above replaced is refused there, not launched as another
+    if (io.report && ((io.force_pxw && PXW != io.force_pxw) || (io.force_nbt && NBT != io.force_nbt))) {
+        if (err) *err = "conv3: no kernel instantiation for the forced tile (pxw " + std::to_string(io.force_pxw) + ", nbt " + std::to_string(io.force_nbt) +
+                        "): this layer takes pxw " + std::to_string(PXW) + ", nbt " + std::to_string(NBT);
+        return -1;
+    }
     const int BN = NBT * 32;
     a.n_ntiles = (p.lCout + BN - 1) / BN;
     a.ablate = LTK_ABLATE_BUILD ? knob(K_ABLATE) : 0;
@@ -1556,6 +1584,7 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
             const size_t mb = (size_t)2 * 2 * 20 * 1024 + 1024 + (size_t)NSL * 4 * 4096;
             HIPCHK3((hipError_t)ensure_dyn_lds((const void*)mk, (int)mb));
             a.ksplit = 1; a.partial = nullptr;
+            if (io.report) { *io.report = ConvReport(); snprintf(io.report->kernel, sizeof(io.report->kernel), "lin_mp_kernel<%d>", NSL); }
             hipLaunchKernelGGL(mk, dim3((unsigned)(mt * ng)), dim3(512), mb, stream, a, ng, nslabs, p.Cin / 1280);
             HIPCHK3(hipGetLastError());
             return 0;
@@ -1579,6 +1608,7 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
             const size_t lbytes = (size_t)2 * ks * (p.Cin == 512 ? 16 : p.Cin == 384 ? 24 : 20) * 1024 + 512 + (ks == 2 ? 2 * 4 * 4096 : 0);
             HIPCHK3((hipError_t)ensure_dyn_lds((const void*)lk, (int)lbytes));
             a.ksplit = 1; a.partial = nullptr;
+            if (io.report) { *io.report = ConvReport(); snprintf(io.report->kernel, sizeof(io.report->kernel), "lin_fk_kernel"); }
             hipLaunchKernelGGL(lk, dim3((unsigned)grid), dim3(256 * ks), lbytes, stream, a, cpg, ngroups, nslabs);
             HIPCHK3(hipGetLastError());
             return 0;
@@ -1619,6 +1649,13 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     a.nitems = (int)nblk;
     constexpr int kPersistBlocks = 512;      // resident grid size above which a launch walks its items persistently
     const long long grid = nblk > kPersistBlocks ? kPersistBlocks : nblk;
+    if (io.report) {
+        ConvReport& r = *io.report;
+        r = ConvReport();
+        const std::string nm = head ? "conv3_head_kernel<" + std::to_string(PXW) + ">" : p.mx ? "conv3_kernel (mx)" : p.q8 ? "conv3_kernel (fp8)" : k3_name(G, NBT, PXW, NC8, T, S);
+        snprintf(r.kernel, sizeof(r.kernel), "%s", nm.c_str());
+        r.G = G; r.NBT = NBT; r.PXW = PXW; r.NC8 = NC8; r.T = T; r.S = S; r.ksplit = ksplit; r.items = (int)nblk; r.grid = (int)grid;
+    }
     if (head) {
         typedef void (*k3_head_t)(const K3Args, const HeadArgs);
         const k3_head_t kh = PXW == 4 ? (k3_head_t)conv3_head_kernel<4> : (k3_head_t)conv3_head_kernel<2>;

@@ -128,6 +128,16 @@ inline int conv_fp8_quant(int Cin) { return (Cin % 64 == 0 && Cin >= 512) ? 2 : 
 unsigned char f32_to_e4m3(float v);
 void conv_plan_destroy(ConvPlan* p);
 
+// What conv3_launch enqueued for one layer (test hook ltk_conv2d_f16_ex, through ConvIO::report): the instantiation in the spelling of
+// conv3_variant_names(), its template arguments, the split factor after the scratch-capacity halving and the "no empty split"
+// correction, the work items and the resident grid.
+struct ConvReport {
+    char kernel[64];
+    int G, NBT, PXW, NC8, T, S, ksplit, items, grid;
+};
+// every fp16 instantiation conv3_launch's pickers can return, one name per line (conv3_mfma.hip: the table the pickers are made of)
+std::string conv3_variant_names();
+
 struct ConvIO {
     const f16* x; int N, H, W; int x_ld, x_coff;
     f16* y; int y_ld, y_coff;
@@ -148,6 +158,8 @@ struct ConvIO {
     float ln_eps = 1e-5f;
     float* partial = nullptr;      // split-K scratch (fp32 slabs) and its capacity in bytes; conv3 splits the
     size_t partial_cap = 0;        // channel loop of under-filled launches only when this is large enough
+    ConvReport* report = nullptr;  // conv3, test hook only: filled with what was launched.  With it set a forced tile (force_pxw / force_nbt)
+                                   // that conv3 cannot serve as asked is refused; nullptr: nothing about the launch path changes
 };
 
 // Enqueue the layer on `stream`.  Returns 0 or a negative error (message in *err).
@@ -172,6 +184,9 @@ int rowgemm_plan_create(RowGemmPlan* p, const float* w_eff /*[J][K]*/, int J, in
 void rowgemm_plan_destroy(RowGemmPlan* p);
 int rowgemm_launch(const RowGemmPlan& p, const f16* x, int x_ld, int x_coff, f16* y, int y_ld, int y_coff, int M, int relu,
                    hipStream_t stream, std::string* err);
+// 16-frame tiles per block of the instantiation rowgemm_launch picks for M frames, and the weight fragments it keeps in flight per trip
+constexpr int rowgemm_ft(int M) { return M <= 16 ? 1 : 2; }
+constexpr int rowgemm_ub(int ft) { return ft == 1 ? 8 : 4; }
 
 // rowconv (rowgemm.hip): k x k convolutions on maps of <= 8 x 8 output pixels as the same weight-streaming GEMM, the im2col rows
 // gathered on the fly; the plan is a RowGemmPlan over W_eff[j][tap * C + c] (tap = ky * k + kx).  Launches of up to kRowConvMaxRows
@@ -188,6 +203,15 @@ struct RowConvIO {
     float ln_eps = 1e-5f;
 };
 int rowconv_launch(const RowGemmPlan& p, const RowConvIO& io, hipStream_t stream, std::string* err);
+// W_eff of a rowconv plan from the torch-layout weight w[Cout][Cin][3][3]: we[j][tap * Cin + c], tap = ky * 3 + kx (J = Cout, K = 9 Cin)
+void rowconv_weff(const float* w, int Cin, int Cout, std::vector<float>* we);
+// W_eff of phase g = py * 2 + px of a rowconvT plan from w[Cin][Cout][3][3]: we[j][(dy * (1 + px) + dx) * Cin + c] =
+// w[c][j][py + 1 - 2 dy][px + 1 - 2 dx] (J = Cout, K = (1 + py) (1 + px) Cin).  The Wav2Lip program and the test hook both build from these.
+void rowconvT_weff(const float* w, int Cin, int Cout, int g, std::vector<float>* we);
+// rowconv_kernel<FT, UB> of a launch of `rows` output pixels to J channels (rowconv_launch / rowconvT_launch): ~2 blocks per CU's
+// worth of row groups before the tiles grow
+constexpr int rowconv_ft(long long rows, int J) { return (int)((rows + 15) / 16) * (J / 32) <= 512 ? 2 : 4; }
+constexpr int rowconv_ub(int ft) { return ft == 2 ? 6 : 4; }
 // ConvTranspose2d(k3, s2, p1, op1) on a source map of <= 8 x 8 pixels: four per-phase plans p[py * 2 + px] over
 // W_eff[j][(dy * (1 + px) + dx) * C + c] = w[c][j][py + 1 - 2 dy][px + 1 - 2 dx], one launch; io.H x io.W source, io.Ho x io.Wo = 2H x 2W output
 int rowconvT_launch(const RowGemmPlan* p, const RowConvIO& io, hipStream_t stream, std::string* err);

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(512) void rowgemm_kernel(const RowGemmArgs a) {
     // U weight fragments (U KiB per wave, 8 waves per CU) in flight per trip: hipcc waits for a trip's loads before its MFMAs and
     // issues the next trip's loads behind them, so a wave pays one HBM round trip per trip - the K = 8192 layer (8.4 MB behind
     // only 32 blocks, 32 steps per wave) takes 16 us with 4, 8 or 16 steps per trip alike, so the trip depth is not what bounds it
-    constexpr int U = FT == 1 ? 8 : 4;
+    constexpr int U = rowgemm_ub(FT);
     for (; kt + U <= k1; kt += U) {
         f16x8 wa[U], xb[U][FT];
 #pragma unroll
@@ -324,6 +324,27 @@ int rowgemm_plan_create(RowGemmPlan* p, const float* w_eff, int J, int K, const 
     return 0;
 }
 
+void rowconv_weff(const float* w, int Cin, int Cout, std::vector<float>* we) {
+    const int K = 9 * Cin;
+    we->assign((size_t)Cout * K, 0.f);
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci)
+            for (int t = 0; t < 9; ++t) (*we)[(size_t)co * K + (size_t)t * Cin + ci] = w[((size_t)co * Cin + ci) * 9 + t];
+}
+
+// output pixel (2y + py, 2x + px) = sum over (dy, dx) of x[y + dy][x + dx] * w[:, :, ky, kx] with ky = py + 1 - 2 dy, kx = px + 1 - 2 dx
+// (torch ConvTranspose2d: oy = 2 iy - 1 + ky; weight layout [cin][cout][kh][kw])
+void rowconvT_weff(const float* w, int Cin, int Cout, int g, std::vector<float>* we) {
+    const int py = g >> 1, px = g & 1, ny = 1 + py, nx = 1 + px, K = ny * nx * Cin;
+    we->assign((size_t)Cout * K, 0.f);
+    for (int dy = 0; dy < ny; ++dy)
+        for (int dx = 0; dx < nx; ++dx) {
+            const int ky = py + 1 - 2 * dy, kx = px + 1 - 2 * dx, t = dy * nx + dx;
+            for (int co = 0; co < Cout; ++co)
+                for (int ci = 0; ci < Cin; ++ci) (*we)[(size_t)co * K + (size_t)t * Cin + ci] = w[((size_t)ci * Cout + co) * 9 + ky * 3 + kx];
+        }
+}
+
 void rowgemm_plan_destroy(RowGemmPlan* p) {
     if (p->d_w) (void)hipFree(p->d_w);
     if (p->d_scale) (void)hipFree(p->d_scale);
@@ -336,7 +357,7 @@ int rowgemm_launch(const RowGemmPlan& p, const f16* x, int x_ld, int x_coff, f16
     if (((x_ld | x_coff) & 7) || ((y_ld | y_coff) & 3)) { if (err) *err = "rowgemm: operand pitch / offset alignment"; return -1; }
     if (x_coff < 0 || y_coff < 0 || x_coff + p.K > x_ld || y_coff + p.J > y_ld) { if (err) *err = "rowgemm: channel range outside the row pitch"; return -1; }
     RowGemmArgs a{x, x_ld, x_coff, y, y_ld, y_coff, p.d_w, p.d_scale, p.d_shift, M, p.K, p.J, relu};
-    if (M <= 16) hipLaunchKernelGGL(rowgemm_kernel<1>, dim3((unsigned)(p.J / 16)), dim3(512), 0, stream, a);
+    if (rowgemm_ft(M) == 1) hipLaunchKernelGGL(rowgemm_kernel<1>, dim3((unsigned)(p.J / 16)), dim3(512), 0, stream, a);
     else hipLaunchKernelGGL(rowgemm_kernel<2>, dim3((unsigned)(p.J / 16)), dim3(512), 0, stream, a);
     if (hipGetLastError() != hipSuccess) { if (err) *err = "rowgemm: launch failed"; return -2; }
     return 0;
@@ -365,7 +386,7 @@ int rowconv_launch(const RowGemmPlan& p, const RowConvIO& io, hipStream_t stream
         if (err) *err = "rowconv: the LayerNorm fold is a 1x1-layer feature"; return -1;
     }
     const int tiles = (int)((M + 15) / 16);
-    const int FT = tiles * (p.J / 32) <= 512 ? 2 : 4;          // ~2 blocks per CU's worth of row groups before the tiles grow
+    const int FT = rowconv_ft(M, p.J);
     a.NR = (tiles + FT - 1) / FT;
     const unsigned grid = (unsigned)((p.J / 32) * a.NR);       // (J / 32) % 8 == 0: the XCD mapping of the kernel covers it exactly
     if (FT == 2) hipLaunchKernelGGL((rowconv_kernel<2, 6>), dim3(grid), dim3(512), 0, stream, a);
@@ -403,7 +424,7 @@ int rowconvT_launch(const RowGemmPlan* p, const RowConvIO& io, hipStream_t strea
         a.ph[g].KT = p[g].K / 32; a.ph[g].KW = 1 + px; a.ph[g].oy_add = py; a.ph[g].ox_add = px;
     }
     const int tiles = (int)((M + 15) / 16);
-    const int FT = tiles * (J / 32) <= 512 ? 2 : 4;
+    const int FT = rowconv_ft(M, J);
     a.NR = (tiles + FT - 1) / FT;
     const dim3 grid((unsigned)((J / 32) * a.NR), 4u);
     if (FT == 2) hipLaunchKernelGGL((rowconv_kernel<2, 6>), grid, dim3(512), 0, stream, a);

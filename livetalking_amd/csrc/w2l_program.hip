@@ -244,10 +244,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             // 3x3 conv whose output map is at most 8 x 8: W_eff[j][tap * Cin + c], tap = ky * 3 + kx (`w` carries the folded identity
             // of a residual layer, exactly as the conv3 plan above does)
             J = d.cout; K = 9 * d.cin;
-            we.assign((size_t)J * K, 0.f);
-            for (int co = 0; co < d.cout; ++co)
-                for (int ci = 0; ci < d.cin; ++ci)
-                    for (int t = 0; t < 9; ++t) we[(size_t)co * K + (size_t)t * d.cin + ci] = w[((size_t)co * d.cin + ci) * 9 + t];
+            rowconv_weff(w, d.cin, d.cout, &we);
             rc = rowgemm_plan_create(&L->rg, we.data(), J, K, sc.data(), sf.data(), &err);
             if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
             L->rowconv = true;
@@ -255,19 +252,10 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             L->rc_stride_w = d.sw;
         } else if (want_rowconv && map_w > 0 && map_w <= 8 && d.transposed && d.k == 3 && d.sh == 2 && d.sw == 2 && d.pad == 1 && d.out_pad == 1 &&
                    (d.cin == 256 || d.cin == 512 || d.cin == 1024) && d.cout % 256 == 0) {
-            // stride-2 transposed conv on the 4x4 / 8x8 maps: output pixel (2y + py, 2x + px) = sum over (dy, dx) of x[y + dy][x + dx] * w[:, :, ky, kx]
-            // with ky = py + 1 - 2 dy, kx = px + 1 - 2 dx (torch ConvTranspose2d: oy = 2 iy - 1 + ky; weight layout [cin][cout][kh][kw])
+            // stride-2 transposed conv on the 4x4 / 8x8 maps: one plan per output phase (rowconvT_weff, rowgemm.hip)
             for (int gph = 0; gph < 4; ++gph) {
-                const int py = gph >> 1, px = gph & 1, ny = 1 + py, nx = 1 + px;
-                J = d.cout; K = ny * nx * d.cin;
-                we.assign((size_t)J * K, 0.f);
-                for (int dy = 0; dy < ny; ++dy)
-                    for (int dx = 0; dx < nx; ++dx) {
-                        const int ky = py + 1 - 2 * dy, kx = px + 1 - 2 * dx, t = dy * nx + dx;
-                        for (int co = 0; co < d.cout; ++co)
-                            for (int ci = 0; ci < d.cin; ++ci)
-                                we[(size_t)co * K + (size_t)t * d.cin + ci] = w[((size_t)ci * d.cout + co) * 9 + ky * 3 + kx];
-                    }
+                J = d.cout; K = (1 + (gph >> 1)) * (1 + (gph & 1)) * d.cin;
+                rowconvT_weff(w, d.cin, d.cout, gph, &we);
                 rc = rowgemm_plan_create(&L->rgT[gph], we.data(), J, K, sc.data(), sf.data(), &err);
                 if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
             }

@@ -621,3 +621,32 @@ class Engine:
             sf.ctypes.data if sf is not None else None, C.c_void_p(d_res_ptr) if d_res_ptr else None,
             1 if relu else 0, C.c_void_p(d_y_ptr), iters, C.byref(ms)))
         return ms.value
+
+    def conv2d_f16_ex(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, Cout, k, stride, pad, transposed=False, out_pad=0,
+                      scale: Optional[np.ndarray] = None, shift: Optional[np.ndarray] = None, d_res_ptr: int = 0, d_y_ptr: int = 0,
+                      **opts) -> dict:
+        """One conv layer with the caller naming what runs (include/ltk.h: ltk_conv2d_f16_ex; `opts` = the fields of ltk_conv_opts:
+        x_ld, x_coff, y_ld, y_coff, res_ld, res_coff, act, ups, force_pxw, force_nbt, force_ksplit, family).  Returns the report of
+        what was launched as a dict (kernel: str, family, G, NBT, PXW, NC8, T, S, ksplit, items, grid, FT, UB)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32) if scale is not None else None
+        sf = np.ascontiguousarray(shift, dtype=np.float32) if shift is not None else None
+        kh, kw = (k, k) if isinstance(k, int) else k
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        ph, pw = (pad, pad) if isinstance(pad, int) else pad
+        o = _lib.ConvOpts(**{name: int(v) for name, v in opts.items()})
+        rep = _lib.ConvReport()
+        _lib.check(self._lib.ltk_conv2d_f16_ex(
+            self._h, C.c_void_p(d_x_ptr), N, H, W, Cin, w.ctypes.data, Cout, kh, kw, sh, sw, ph, pw, 1 if transposed else 0, out_pad,
+            sc.ctypes.data if sc is not None else None, sf.ctypes.data if sf is not None else None,
+            C.c_void_p(d_res_ptr) if d_res_ptr else None, 0, C.c_void_p(d_y_ptr), C.byref(o), C.byref(rep)))
+        out = {name: getattr(rep, name) for name, _ in _lib.ConvReport._fields_}
+        out["kernel"] = rep.kernel.decode()
+        return out
+
+    @staticmethod
+    def conv3_variants() -> list:
+        """Names of every fp16 conv3 instantiation the launch path can pick (ltk_debug_conv3_variants); no GPU needed."""
+        buf = C.create_string_buffer(8192)
+        _lib.check(_lib.load().ltk_debug_conv3_variants(buf, len(buf)))
+        return buf.value.decode().split()
