@@ -484,6 +484,37 @@ int ltk_debug_conv3_variants(char* buf, int cap);
 int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
                       int silu, int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg);
 
+/* The same GroupNorm on channel VIEWS, reporting what ran (kernel unit tests; one body with ltk_groupnorm_f16).  `opts`: x / y are channels
+ * [coff, coff + C) of a channel-blocked buffer of `ld` channels - multiples of 16, for an e4m3 y of 32; ld = 0: contiguous.  `rep` (may be
+ * NULL): impl as resolved; kernel = the instantiation, "gn_stats_kernel+gn_apply_kernel<false|true>", "gn_group_kernel<KMAX,NT,false|true>"
+ * (from gn_group_variant, the rule the launch itself switches on) or "gn_coop_kernel<false|true>"; segs (two-pass: pixel segments of the
+ * statistics), members (gn_coop: blocks per set), grid (blocks of the launch that writes y).  x and y must not overlap (both hooks refuse it:
+ * the kernels read a group's shift from x while other blocks store y). */
+typedef struct ltk_norm_opts {
+    int x_ld, x_coff, y_ld, y_coff;
+} ltk_norm_opts;
+typedef struct ltk_norm_report {
+    char kernel[64];
+    int impl, segs, members, grid;
+} ltk_norm_report;
+int ltk_groupnorm_f16_ex(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
+                         int silu, int impl, int out_fp8, float out_scale, void* d_y, const ltk_norm_opts* opts, ltk_norm_report* rep);
+
+/* The pointwise and layout kernels of csrc/nn_kernels.hip on their own (kernel unit tests): the existing launch, on the compute stream,
+ * synchronised.  N images of P pixels / tokens and C channels; `opts` as above (views of 16-channel blocks; x_* unused where x is fp32).
+ *   LAYERNORM      x, y fp16 CB16; v0 = gamma[C], v1 = beta[C] (host fp32), eps; C % 16 == 0
+ *   GEGLU          x fp16 CB16 of 2 C channels (a = [0, C), gate = [C, 2 C)), y of C; C % 16 == 0
+ *   ACT_GELU/SILU  x, y fp16 CB16; C % 16 == 0
+ *   ADD_POS        in place on y (d_x unused): y += v0[P][C] (host fp32); any C, the view spans ceil(C / 16) blocks
+ *   NCHW_TO_CB16   x device fp32 [N][C][P] -> y; padding channels of the last block zero
+ *   TOKENS_TO_CB16 x device fp32 [N][P][C] (+ v0[P][C] host fp32 when not NULL) -> y
+ *   VAE_POST       x fp16 CB16 (channels 0..2 = RGB in [-1, 1]), C = 3, N <= 64 -> y uint8 [N][P][3] BGR (y_* unused; P * 3 % 4 == 0 when N > 1)
+ * v0 / v1 are ignored by the ops that take none. */
+enum { LTK_PW_LAYERNORM = 0, LTK_PW_GEGLU = 1, LTK_PW_ACT_GELU = 2, LTK_PW_ACT_SILU = 3, LTK_PW_ADD_POS = 4, LTK_PW_NCHW_TO_CB16 = 5,
+       LTK_PW_TOKENS_TO_CB16 = 6, LTK_PW_VAE_POST = 7 };
+int ltk_pointwise_f16(ltk_engine* e, int op, const void* d_x, void* d_y, int N, int C, int P, float eps, const float* v0, const float* v1,
+                      const ltk_norm_opts* opts);
+
 /* Standalone attention O = softmax(Q K^T) V per (image, head) over channel-blocked fp16 tensors, for kernel unit tests: v_transpose_kernel into a
  * scratch V^T of the hook's own, then the attention kernel, on the compute stream, synchronised.  q / o: device fp16 [N][cbt][Tq][16], k / v:
  * [N][cbt][Tk][16]; every tensor has its own cbt (channel blocks in its buffer) and cb0 (first block of head 0), head h at blocks

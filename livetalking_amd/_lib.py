@@ -51,6 +51,14 @@ class ConvReport(C.Structure):
                                                                      "FT", "UB")]
 
 
+class NormOpts(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
+
+
+class NormReport(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64)] + [(n, C.c_int) for n in ("impl", "segs", "members", "grid")]
+
+
 # every symbol include/ltk.h declares: (restype, argtypes)
 SYMBOLS = {
     "ltk_last_error": (C.c_char_p, []),
@@ -139,6 +147,10 @@ SYMBOLS = {
     "ltk_debug_conv3_variants": (C.c_int, [C.c_char_p, C.c_int]),
     "ltk_groupnorm_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "ltk_groupnorm_f16_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_int, C.c_float, C.c_void_p, C.POINTER(NormOpts), C.POINTER(NormReport)]),
+    "ltk_pointwise_f16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.POINTER(NormOpts)]),
     "ltk_attention_f16": (C.c_int, [C.c_void_p] + [C.c_void_p, C.c_int, C.c_int] * 4 + [C.c_int] * 6),
     "ltk_f32_to_e4m3": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "ltk_conv2d_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -166,7 +178,10 @@ def load() -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
+    other_build = bool(os.environ.get("LTK_LIB"))
     for name, (res, args) in SYMBOLS.items():
+        if other_build and not hasattr(lib, name):      # an A/B against an older build: it lacks the hooks added since, bind what it has
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

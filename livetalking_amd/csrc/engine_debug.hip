@@ -360,10 +360,22 @@ int ltk_debug_conv3_variants(char* buf, int cap) {
     return LTK_OK;
 }
 
-int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
-                      int silu, int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg) {
+namespace {
+// ltk_groupnorm_f16 and ltk_groupnorm_f16_ex: one body.  `o` (may be NULL): the channel views; `rep` (may be NULL): what was launched.
+int groupnorm_hook(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta, int silu,
+                   int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg, const ltk_norm_opts* o, ltk_norm_report* rep) {
     if (!e || !d_x || !d_y || !gamma || !beta || N <= 0 || C <= 0 || P <= 0 || groups <= 0 || C % groups || C % 16 || (out_fp8 && C % 32))
         return fail(LTK_E_INVALID, "bad arguments");
+    if (rep) memset(rep, 0, sizeof(*rep));
+    const int yb = out_fp8 ? 32 : 16;                    // channels per block of y
+    const int x_ld = (o && o->x_ld) ? o->x_ld : C, x_coff = o ? o->x_coff : 0, y_ld = (o && o->y_ld) ? o->y_ld : C, y_coff = o ? o->y_coff : 0;
+    if (x_ld % 16 || x_coff % 16 || y_ld % yb || y_coff % yb) return fail(LTK_E_INVALID, "channel views are multiples of 16 channels (of 32 for an e4m3 output)");
+    if (x_coff < 0 || y_coff < 0 || x_coff + C > x_ld || y_coff + C > y_ld) return fail(LTK_E_INVALID, "channel view outside its buffer");
+    {   // the kernels read their shift from x while other blocks already store y: no GroupNorm in place
+        const char *xa = (const char*)d_x, *ya = (const char*)d_y;
+        const size_t xn = (size_t)N * (x_ld / 16) * P * 32, yn = (size_t)N * (y_ld / yb) * P * yb * (out_fp8 ? 1 : 2);
+        if (xa < ya + yn && ya < xa + xn) return fail(LTK_E_INVALID, "GroupNorm: x and y overlap");
+    }
     CHK(enter_device(e->device));
     const bool fits_group = gn_group_fits(C, P, groups);
     const int members = gn_coop_members(C, P, groups);
@@ -384,17 +396,17 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
     (void)hipMemcpyAsync(d_gamma, gamma, C * sizeof(float), hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_beta, beta, C * sizeof(float), hipMemcpyHostToDevice, s);
     const f16* x = (const f16*)d_x;
-    const int ycb = out_fp8 ? C / 32 : C / 16;
+    const int xcbt = x_ld / 16, xcb0 = x_coff / 16, ycbt = y_ld / yb, ycb0 = y_coff / yb;
     auto run = [&]() {
         if (impl == 3) {
             launch_gn_coop_reset(d_slots, slot_words, s);
-            launch_gn_coop(x, N, C / 16, 0, C, P, groups, eps, d_slots, err_dev, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, out_fp8 ? 1 : 0, out_scale, s);
+            launch_gn_coop(x, N, xcbt, xcb0, C, P, groups, eps, d_slots, err_dev, d_gamma, d_beta, silu, (f16*)d_y, ycbt, ycb0, out_fp8 ? 1 : 0, out_scale, s);
         } else if (impl == 2) {
-            launch_gn_group(x, N, C / 16, 0, C, P, groups, eps, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, out_fp8 ? 1 : 0, out_scale, s);
+            launch_gn_group(x, N, xcbt, xcb0, C, P, groups, eps, d_gamma, d_beta, silu, (f16*)d_y, ycbt, ycb0, out_fp8 ? 1 : 0, out_scale, s);
         } else {
-            launch_gn_stats(x, N, C / 16, 0, C, P, segs, d_partial, s);
-            if (out_fp8) launch_gn_apply_fp8(x, N, C / 16, 0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, out_scale, (unsigned char*)d_y, ycb, 0, s);
-            else launch_gn_apply(x, N, C / 16, 0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, (f16*)d_y, ycb, 0, s);
+            launch_gn_stats(x, N, xcbt, xcb0, C, P, groups, segs, d_partial, s);
+            if (out_fp8) launch_gn_apply_fp8(x, N, xcbt, xcb0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, out_scale, (unsigned char*)d_y, ycbt, ycb0, s);
+            else launch_gn_apply(x, N, xcbt, xcb0, C, P, groups, eps, d_partial, segs, d_gamma, d_beta, silu, (f16*)d_y, ycbt, ycb0, s);
         }
     };
     run();
@@ -408,6 +420,79 @@ int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int g
     if (rc) return rc;
     if (he != hipSuccess || hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, std::string("GroupNorm kernel: ") + hipGetErrorString(he));
     if (*reinterpret_cast<volatile unsigned*>(errw.host)) return fail(LTK_E_HIP, "a cooperative GroupNorm block gave up waiting for its set (gn_coop_kernel)");
+    if (rep) {
+        const char* f8 = out_fp8 ? "true" : "false";
+        rep->impl = impl;
+        if (impl == 3) {
+            snprintf(rep->kernel, sizeof(rep->kernel), "gn_coop_kernel<%s>", f8);
+            rep->members = members; rep->grid = N * (C / 16) * members;
+        } else if (impl == 2) {
+            const GnGroupVariant v = gn_group_variant(C, P, groups);
+            snprintf(rep->kernel, sizeof(rep->kernel), "gn_group_kernel<%d,%d,%s>", v.kmax, v.nt, f8);
+            rep->grid = N * groups;
+        } else {
+            snprintf(rep->kernel, sizeof(rep->kernel), "gn_stats_kernel+gn_apply_kernel<%s>", f8);
+            rep->segs = segs; rep->grid = N * (C / 16) * ((P + 1023) / 1024);
+        }
+    }
+    return LTK_OK;
+}
+}  // namespace
+
+int ltk_groupnorm_f16(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
+                      int silu, int impl, int out_fp8, float out_scale, void* d_y, int iters, float* ms_avg) {
+    return groupnorm_hook(e, d_x, N, C, P, groups, eps, gamma, beta, silu, impl, out_fp8, out_scale, d_y, iters, ms_avg, nullptr, nullptr);
+}
+
+int ltk_groupnorm_f16_ex(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
+                         int silu, int impl, int out_fp8, float out_scale, void* d_y, const ltk_norm_opts* opts, ltk_norm_report* rep) {
+    if (!opts) return fail(LTK_E_INVALID, "bad arguments");
+    return groupnorm_hook(e, d_x, N, C, P, groups, eps, gamma, beta, silu, impl, out_fp8, out_scale, d_y, 0, nullptr, opts, rep);
+}
+
+int ltk_pointwise_f16(ltk_engine* e, int op, const void* d_x, void* d_y, int N, int C, int P, float eps, const float* v0, const float* v1,
+                      const ltk_norm_opts* opts) {
+    if (!e || !d_y || !opts || N <= 0 || C <= 0 || P <= 0 || op < LTK_PW_LAYERNORM || op > LTK_PW_VAE_POST) return fail(LTK_E_INVALID, "bad arguments");
+    if (op != LTK_PW_ADD_POS && !d_x) return fail(LTK_E_INVALID, "bad arguments");
+    const bool f16_in = op <= LTK_PW_ACT_SILU || op == LTK_PW_VAE_POST;        // x is a channel-blocked fp16 tensor
+    const bool whole = op <= LTK_PW_ACT_SILU;                                  // kernels over whole 16-channel blocks
+    if (whole && C % 16) return fail(LTK_E_INVALID, "C must be a multiple of 16");
+    if ((op == LTK_PW_LAYERNORM && (!v0 || !v1)) || (op == LTK_PW_ADD_POS && !v0)) return fail(LTK_E_INVALID, "bad arguments");
+    if (op == LTK_PW_VAE_POST && (C != 3 || N > 64)) return fail(LTK_E_INVALID, "vae_post: 3 channels, at most 64 frames");
+    const int Cp = (C + 15) / 16 * 16, Cx = op == LTK_PW_GEGLU ? 2 * C : Cp;   // channels the view spans in y / in x
+    const int x_ld = opts->x_ld ? opts->x_ld : Cx, y_ld = opts->y_ld ? opts->y_ld : Cp;
+    if (x_ld % 16 || opts->x_coff % 16 || y_ld % 16 || opts->y_coff % 16) return fail(LTK_E_INVALID, "channel views are multiples of 16 channels");
+    if (opts->x_coff < 0 || opts->y_coff < 0 || (f16_in && opts->x_coff + Cx > x_ld) || (op != LTK_PW_VAE_POST && opts->y_coff + Cp > y_ld))
+        return fail(LTK_E_INVALID, "channel view outside its buffer");
+    if (op == LTK_PW_VAE_POST && opts->x_coff) return fail(LTK_E_INVALID, "vae_post reads the first channel block");
+    if (op == LTK_PW_VAE_POST && N > 1 && (P * 3) % 4) return fail(LTK_E_INVALID, "vae_post: frames are packed, so P * 3 must be a multiple of 4 (whole blocks are stored as dwords)");
+    CHK(enter_device(e->device));
+    const size_t n0 = op == LTK_PW_LAYERNORM ? (size_t)C : (size_t)P * C;     // gamma | pos / add table
+    DevBuf b0, b1;
+    const bool takes_v0 = op == LTK_PW_LAYERNORM || op == LTK_PW_ADD_POS || op == LTK_PW_TOKENS_TO_CB16;      // the others ignore v0 / v1
+    if (v0 && takes_v0) { const int rc = upload(v0, n0 * sizeof(float), &b0); if (rc) return rc; }
+    if (v1 && op == LTK_PW_LAYERNORM) { const int rc = upload(v1, (size_t)C * sizeof(float), &b1); if (rc) return rc; }
+    const f16* x = (const f16*)d_x;
+    f16* y = (f16*)d_y;
+    const int xcbt = x_ld / 16, xcb0 = opts->x_coff / 16, ycbt = y_ld / 16, ycb0 = opts->y_coff / 16;
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    switch (op) {
+        case LTK_PW_LAYERNORM: launch_layernorm(x, N, xcbt, xcb0, C, P, eps, (const float*)b0.p, (const float*)b1.p, y, ycbt, ycb0, s); break;
+        case LTK_PW_GEGLU: launch_geglu(x, N, xcbt, xcb0, C, P, y, ycbt, ycb0, s); break;
+        case LTK_PW_ACT_GELU: launch_act(x, N, xcbt, xcb0, C, P, 2, y, ycbt, ycb0, s); break;
+        case LTK_PW_ACT_SILU: launch_act(x, N, xcbt, xcb0, C, P, 3, y, ycbt, ycb0, s); break;
+        case LTK_PW_ADD_POS: launch_add_pos(y, N, ycbt, ycb0, C, P, (const float*)b0.p, s); break;
+        case LTK_PW_NCHW_TO_CB16: launch_nchw_to_cb16((const float*)d_x, N, C, P, y, ycbt, ycb0, s); break;
+        case LTK_PW_TOKENS_TO_CB16: launch_tokens_to_cb16((const float*)d_x, N, P, C, (const float*)b0.p, y, ycbt, ycb0, s); break;
+        default: {
+            OutList64 outs;
+            for (int i = 0; i < 64; ++i) outs.p[i] = i < N ? (uint8_t*)d_y + (size_t)i * P * 3 : nullptr;
+            launch_vae_post(x, xcbt, N, P, outs, nullptr, s);
+        }
+    }
+    const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(s);       // before the uploaded vectors go
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("pointwise kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
     return LTK_OK;
 }
 

@@ -160,6 +160,8 @@ int MtGraph::add_gn(const std::string& name, SD& sd, const std::string& prefix, 
     const float* g = sd.get(prefix + ".weight", x.C);
     const float* b = sd.get(prefix + ".bias", x.C);
     if (!g || !b) { err = sd.err; return -1; }
+    // the kernels read a group's shift from x while other blocks already store y (nn_kernels.hip: gn_shift)
+    if (x.buf == y.buf && x.coff < y.coff + y.C && y.coff < x.coff + x.C) { err = "GroupNorm " + name + " in place"; return -1; }
     MtOp op;
     op.type = OP_GN; op.name = name; op.x = x; op.y = y; op.eps = eps; op.silu = silu; op.groups = 32;
     op.gamma = add_vec(g, x.C); op.beta = add_vec(b, x.C);
@@ -303,7 +305,7 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
                 break;
             }
             const int segs = gn_segments(nf, op.x.C, P);
-            launch_gn_stats(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, P, segs, g.gn_partial, s);
+            launch_gn_stats(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, P, op.groups, segs, g.gn_partial, s);
             if (op.y.q8)
                 launch_gn_apply_fp8(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, P, op.groups, op.eps, g.gn_partial, segs,
                                     g.vecs[op.gamma], g.vecs[op.beta], op.silu, g.fp8_ascale, (unsigned char*)g.bufs[op.y.buf],

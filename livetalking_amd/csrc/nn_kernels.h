@@ -10,9 +10,11 @@
 namespace ltk {
 
 // ---- GroupNorm (diffusers ResnetBlock2D.norm1/2, Transformer2DModel.norm, AutoencoderKL norms)
-// stats: partial [N][C/16][segs][16][2] fp32 (sum, sum of squares) over `segs` pixel segments
+// stats: partial [N][C/16][segs][16][2] fp32 (sum, sum of squares of x - k, k = the median of three samples of the channel's (image, group)) over
+// `segs` pixel segments; every GroupNorm kernel here forms mean = k + S / n, var = Q / n - (S / n)^2 from such shifted sums (nn_kernels.hip:
+// gn_shift).  gn_apply reads k from x again: x and y must not overlap.
 int gn_segments(int N, int C, int P);
-void launch_gn_stats(const f16* x, int N, int cbt, int cb0, int C, int P, int segs, float* partial, hipStream_t s);
+void launch_gn_stats(const f16* x, int N, int cbt, int cb0, int C, int P, int groups, int segs, float* partial, hipStream_t s);
 // y = (x - mean_g) * rstd_g * gamma + beta, optional SiLU; groups of C/groups consecutive channels
 void launch_gn_apply(const f16* x, int N, int x_cbt, int x_cb0, int C, int P, int groups, float eps, const float* partial,
                      int segs, const float* gamma, const float* beta, int silu, f16* y, int y_cbt, int y_cb0, hipStream_t s);
@@ -27,6 +29,8 @@ void launch_gn_apply_fp8(const f16* x, int N, int x_cbt, int x_cb0, int C, int P
 // channels per group, pixels x channels-per-group <= 30 720).  fp8 != 0: e4m3 output as launch_gn_apply_fp8 (y_cbt / y_cb0 in
 // 32-channel blocks)
 bool gn_group_fits(int C, int P, int groups);
+struct GnGroupVariant { int kmax, nt; };        // gn_group_kernel<kmax, nt, fp8>
+GnGroupVariant gn_group_variant(int C, int P, int groups);
 void launch_gn_group(const f16* x, int N, int x_cbt, int x_cb0, int C, int P, int groups, float eps, const float* gamma, const float* beta,
                      int silu, f16* y, int y_cbt, int y_cb0, int fp8, float out_scale, hipStream_t s);
 

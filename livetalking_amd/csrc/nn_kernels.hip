@@ -32,7 +32,22 @@ int gn_segments(int N, int C, int P) {
     return segs;
 }
 
-__global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x, int cbt, int cb0, int CB, int P, int segs,
+// Statistics are sums of (x - k) with one k per (image, group) (gn_shift): var = E[(x-k)^2] - E[x-k]^2 then cancels digits in proportion to
+// ((mean - k) / std)^2 instead of (mean / std)^2.  The un-shifted sums left rstd 4e-3 and more off where a group's mean is 256 standard deviations
+// (tests/test_norm_gpu.py, family offset256; profiles/norm_parity.txt), as layernorm_kernel's had.  k is the MEDIAN of three samples spread over
+// the group - (first channel, pixel 0), (middle channel, pixel P / 2), (last channel, pixel P - 1) -, not one raw sample: a single sample that is
+// itself an outlier of 3e4 in a unit-variance group of n values puts (mean - k) / std at sqrt(n), worse than no shift at all (family outlier0);
+// the median of three is inside the bulk of the data unless two of the three samples are outliers.  Every block of a group reads the same
+// three elements, so the partial sums of segments and members shift by the same value and simply add.
+__device__ __forceinline__ float gn_shift(const f16* __restrict__ xn, int P, int c, int cpg) {       // xn: channel 0, pixel 0 of the image's view
+    const int g0 = (c / cpg) * cpg, c1 = g0 + cpg / 2, c2 = g0 + cpg - 1;
+    const float a = (float)xn[(size_t)(g0 >> 4) * P * 16 + (g0 & 15)];
+    const float b = (float)xn[((size_t)(c1 >> 4) * P + P / 2) * 16 + (c1 & 15)];
+    const float d = (float)xn[((size_t)(c2 >> 4) * P + P - 1) * 16 + (c2 & 15)];
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), d));
+}
+
+__global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x, int cbt, int cb0, int CB, int P, int cpg, int segs,
                                                         float* __restrict__ partial) {
     __shared__ float red[4][2][16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -41,9 +56,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
     const int seglen = (P + segs - 1) / segs;
     const int p0 = seg * seglen, p1 = min(P, p0 + seglen);
     const f16* base = x + ((size_t)(n * cbt + cb0 + cb) * P) * 16 + half * 8;
-    float s[8], q[8];
+    float s[8], q[8], k[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) { s[c] = 0.f; q[c] = 0.f; }
+    for (int c = 0; c < 8; ++c) { s[c] = 0.f; q[c] = 0.f; k[c] = gn_shift(x + ((size_t)(n * cbt + cb0) * P) * 16, P, cb * 16 + half * 8 + c, cpg); }
     int p = p0 + pl;
     for (; p + 384 < p1; p += 512) {          // four independent loads in flight per thread
         const f16x8 v0 = *reinterpret_cast<const f16x8*>(base + (size_t)p * 16);
@@ -52,7 +67,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
         const f16x8 v3 = *reinterpret_cast<const f16x8*>(base + (size_t)(p + 384) * 16);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float f0 = (float)v0[c], f1 = (float)v1[c], f2 = (float)v2[c], f3 = (float)v3[c];
+            const float f0 = (float)v0[c] - k[c], f1 = (float)v1[c] - k[c], f2 = (float)v2[c] - k[c], f3 = (float)v3[c] - k[c];
             s[c] += (f0 + f1) + (f2 + f3);
             q[c] += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
         }
@@ -60,7 +75,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
     for (; p < p1; p += 128) {
         const f16x8 v = *reinterpret_cast<const f16x8*>(base + (size_t)p * 16);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) { const float f = (float)v[c]; s[c] += f; q[c] += f * f; }
+        for (int c = 0; c < 8; ++c) { const float f = (float)v[c] - k[c]; s[c] += f; q[c] += f * f; }
     }
     // reduce over the 32 lanes of this wave that share `half` (lane bit 0)
 #pragma unroll
@@ -80,9 +95,9 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const f16* __restrict__ x
     }
 }
 
-void launch_gn_stats(const f16* x, int N, int cbt, int cb0, int C, int P, int segs, float* partial, hipStream_t s) {
+void launch_gn_stats(const f16* x, int N, int cbt, int cb0, int C, int P, int groups, int segs, float* partial, hipStream_t s) {
     const int CB = C / 16;
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(N * CB, segs), dim3(256), 0, s, x, cbt, cb0, CB, P, segs, partial);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(N * CB, segs), dim3(256), 0, s, x, cbt, cb0, CB, P, C / groups, segs, partial);
 }
 
 // v * rcp(1 + exp(-v)): v_rcp_f32 (1 ulp) instead of the correctly rounded division (v_div_scale x2, v_rcp, five fma, v_div_fmas, v_div_fixup: 11 more
@@ -119,8 +134,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const f16* __restrict__ x
 #pragma unroll
         for (int i = 0; i < 16; ++i) { S += red[0][tid][i]; Q += red[1][tid][i]; }
         const float cnt = (float)cpg * (float)P;
-        const float mean = S / cnt;
-        const float var = fmaxf(Q / cnt - mean * mean, 0.f);
+        const float dm = S / cnt;                   // S, Q: sums of (x - k), gn_stats_kernel
+        const float mean = gn_shift(x + ((size_t)(n * x_cbt + x_cb0) * P) * 16, P, c, cpg) + dm;
+        const float var = fmaxf(Q / cnt - dm * dm, 0.f);
         const float rstd = rsqrtf(var + eps);
         const float a = gamma[c] * rstd;
         ab[0][tid] = a;
@@ -238,13 +254,16 @@ __global__ __launch_bounds__(NT) void gn_group_kernel(const f16* __restrict__ x,
     unsigned v[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) v[k] = (k < iters) ? xp[k * stride] : 0u;
+    const float kk = gn_shift(x + ((size_t)(n * x_cbt + x_cb0) * P) * 16, P, g * cpg, cpg);      // sums of (x - kk): see gn_shift
     float s = 0.f, q = 0.f;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const __half2 h = *reinterpret_cast<const __half2*>(&v[k]);
-        const float f0 = __low2float(h), f1 = __high2float(h);
-        s += f0 + f1;
-        q += f0 * f0 + f1 * f1;
+        if (k < iters) {                                // (a slot without a pixel holds 0, not kk)
+            const __half2 h = *reinterpret_cast<const __half2*>(&v[k]);
+            const float f0 = __low2float(h) - kk, f1 = __high2float(h) - kk;
+            s += f0 + f1;
+            q += f0 * f0 + f1 * f1;
+        }
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) { s += __shfl_xor(s, m); q += __shfl_xor(q, m); }
@@ -254,8 +273,9 @@ __global__ __launch_bounds__(NT) void gn_group_kernel(const f16* __restrict__ x,
 #pragma unroll
     for (int w = 0; w < NW; ++w) { S += red[w][0]; Q += red[w][1]; }          // fixed order
     const float cnt = (float)cpg * (float)P;
-    const float mean = S / cnt;
-    const float rstd = rsqrtf(fmaxf(Q / cnt - mean * mean, 0.f) + eps);
+    const float dm = S / cnt;
+    const float mean = kk + dm;
+    const float rstd = rsqrtf(fmaxf(Q / cnt - dm * dm, 0.f) + eps);
     const float a0 = gamma[c] * rstd, a1 = gamma[c + 1] * rstd;
     const float b0 = beta[c] - mean * a0, b1 = beta[c + 1] - mean * a1;
     const int slot0 = live ? slot : 0;
@@ -288,16 +308,24 @@ bool gn_group_fits(int C, int P, int groups) {
     return ((long long)P << gn_group_log2L(cpg)) <= 16 * 1024;        // <= 16 dwords per thread of a 1024-thread block
 }
 
+// the instantiation of gn_group_kernel that serves a shape: 256-thread blocks for small maps (<= 8 dwords per thread); 1024-thread blocks for the
+// 32^2 / 16^2 maps, so that a thread's chain of loads stays <= 16 deep (256-thread blocks with 32..64 loads per thread measured 17-24 us per
+// launch on the 32^2 level).  launch_gn_group switches on it and the test hook reports it: one rule.
+GnGroupVariant gn_group_variant(int C, int P, int groups) {
+    const long long work = (long long)P << gn_group_log2L(C / groups);           // thread slots one (image, group) needs
+    if (work <= 2048) return {8, 256};
+    if (work <= 8192) return {8, 1024};
+    return {16, 1024};
+}
+
 void launch_gn_group(const f16* x, int N, int x_cbt, int x_cb0, int C, int P, int groups, float eps, const float* gamma, const float* beta,
                      int silu, f16* y, int y_cbt, int y_cb0, int fp8, float out_scale, hipStream_t s) {
     const int cpg = C / groups, l2 = gn_group_log2L(cpg);
-    const long long work = (long long)P << l2;           // thread slots one (image, group) needs
+    const GnGroupVariant v = gn_group_variant(C, P, groups);
     const dim3 grid((unsigned)(N * groups));
 #define GNG(K, NT, F) hipLaunchKernelGGL((gn_group_kernel<K, NT, F>), grid, dim3(NT), 0, s, x, x_cbt, x_cb0, P, cpg, l2, eps, gamma, beta, silu, y, y_cbt, y_cb0, out_scale, groups)
-    // small maps: 256-thread blocks (<= 8 dwords per thread); the 32^2 / 16^2 maps: 1024-thread blocks, so that a thread's chain of
-    // loads stays <= 16 deep (256-thread blocks with 32..64 loads per thread measured 17-24 us per launch on the 32^2 level)
-    if (fp8) { if (work <= 2048) GNG(8, 256, true); else if (work <= 8192) GNG(8, 1024, true); else GNG(16, 1024, true); }
-    else { if (work <= 2048) GNG(8, 256, false); else if (work <= 8192) GNG(8, 1024, false); else GNG(16, 1024, false); }
+    if (fp8) { if (v.nt == 256) GNG(8, 256, true); else if (v.kmax == 8) GNG(8, 1024, true); else GNG(16, 1024, true); }
+    else { if (v.nt == 256) GNG(8, 256, false); else if (v.kmax == 8) GNG(8, 1024, false); else GNG(16, 1024, false); }
 #undef GNG
 }
 
@@ -358,19 +386,21 @@ __global__ __launch_bounds__(256) void gn_coop_kernel(const f16* __restrict__ x,
     float sq[8];                                           // [0..3] sums of the channel quarters, [4..7] sums of squares
 #pragma unroll
     for (int i = 0; i < 8; ++i) sq[i] = 0.f;
-    // v_dot2c_f32_f16: sum and sum of squares of a channel PAIR in one instruction each (exact fp16 products, fp32 accumulation) - a third of the
-    // convert / add / fma sequence; the kernel's VALU time is of the order of its memory time (r06_gn_coop_ab.txt)
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2 ones = {(_Float16)1.f, (_Float16)1.f};
+    // sums of (x - k) per channel quarter, k = the first element of the quarter's (image, group) - pixel 0 of the IMAGE, so that every member of
+    // the set shifts by the same value and the exchanged words add up (gn_shift).  fp32 convert / subtract / add / fma per element: the
+    // v_dot2c_f32_f16 pair sums this loop had (a third of the VALU work) can only form the un-shifted sums; cost in profiles/norm_gn_shift_ab.txt
+    float kq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) kq[i] = gn_shift(x + ((size_t)(n * x_cbt + x_cb0) * P) * 16, P, cb * 16 + 4 * i, cpg);
 #pragma unroll
     for (int k = 0; k < 8; ++k)
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int c2 = 0; c2 < 4; ++c2) {
-                const h2 pr = {v[k][h][2 * c2], v[k][h][2 * c2 + 1]};
-                sq[2 * h + (c2 >> 1)] = __builtin_amdgcn_fdot2(pr, ones, sq[2 * h + (c2 >> 1)], false);
-                sq[4 + 2 * h + (c2 >> 1)] = __builtin_amdgcn_fdot2(pr, pr, sq[4 + 2 * h + (c2 >> 1)], false);
+            for (int c = 0; c < 8; ++c) {
+                const float f = (float)v[k][h][c] - kq[2 * h + (c >> 2)];
+                sq[2 * h + (c >> 2)] += f;
+                sq[4 + 2 * h + (c >> 2)] = fmaf(f, f, sq[4 + 2 * h + (c >> 2)]);
             }
 #pragma unroll
     for (int i = 0; i < 8; ++i)
@@ -405,8 +435,9 @@ __global__ __launch_bounds__(256) void gn_coop_kernel(const f16* __restrict__ x,
         for (int m = 0; m < M; ++m)
             for (int i = 0; i < nq; ++i) { S += part[m][q0 + i]; Q += part[m][4 + q0 + i]; }
         const float cnt = (float)cpg * (float)P;
-        const float mean = S / cnt;
-        const float rstd = rsqrtf(fmaxf(Q / cnt - mean * mean, 0.f) + eps);
+        const float dm = S / cnt;
+        const float mean = (tid < 4 ? kq[0] : tid < 8 ? kq[1] : tid < 12 ? kq[2] : kq[3]) + dm;       // (k from the first read: members may have stored y by now)
+        const float rstd = rsqrtf(fmaxf(Q / cnt - dm * dm, 0.f) + eps);
         const float a = gamma[cb * 16 + tid] * rstd;
         ab[0][tid] = a;
         ab[1][tid] = beta[cb * 16 + tid] - mean * a;
@@ -1218,8 +1249,13 @@ __global__ __launch_bounds__(256) void vae_post_kernel(const f16* __restrict__ x
     ob[1] = (unsigned char)rintf(rgb[1] * 255.f);
     ob[2] = (unsigned char)rintf(rgb[0] * 255.f);
     __syncthreads();
-    if (out.p[f] && threadIdx.x < 192 && (blockIdx.x * 256 + 255) < P)
-        reinterpret_cast<unsigned*>(out.p[f] + (size_t)blockIdx.x * 768)[threadIdx.x] = obytes[threadIdx.x];
+    if (!out.p[f]) return;
+    if ((blockIdx.x * 256 + 255) < P) {              // a whole block: its 768 bytes as 192 dwords
+        if (threadIdx.x < 192) reinterpret_cast<unsigned*>(out.p[f] + (size_t)blockIdx.x * 768)[threadIdx.x] = obytes[threadIdx.x];
+    } else if (p < P) {                              // the ragged last block of a frame with P % 256 != 0: a pixel's three bytes per thread
+        unsigned char* o = out.p[f] + (size_t)p * 3;
+        o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
+    }
 }
 
 void launch_vae_post(const f16* x, int x_cbt, int nframes, int P, const OutList64& out, float* out_f32_nchw, hipStream_t s) {

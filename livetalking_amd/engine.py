@@ -596,6 +596,34 @@ class Engine:
                                                1 if silu else 0, impl, 1 if out_fp8 else 0, float(out_scale), C.c_void_p(d_y_ptr), iters, C.byref(ms)))
         return ms.value
 
+    def groupnorm_f16_ex(self, d_x_ptr: int, N, C_, P, groups, eps, gamma: np.ndarray, beta: np.ndarray, silu: bool, d_y_ptr: int, impl: int = 0,
+                         out_fp8: bool = False, out_scale: float = 1.0, **opts) -> dict:
+        """GroupNorm(+SiLU) on channel views with a report of what ran (include/ltk.h: ltk_groupnorm_f16_ex; `opts` = the fields of
+        ltk_norm_opts: x_ld, x_coff, y_ld, y_coff).  Returns the report as a dict (kernel: str, impl, segs, members, grid)."""
+        ga = np.ascontiguousarray(gamma, dtype=np.float32)
+        be = np.ascontiguousarray(beta, dtype=np.float32)
+        o = _lib.NormOpts(**{name: int(v) for name, v in opts.items()})
+        rep = _lib.NormReport()
+        _lib.check(self._lib.ltk_groupnorm_f16_ex(self._h, C.c_void_p(d_x_ptr), N, C_, P, groups, float(eps), ga.ctypes.data, be.ctypes.data,
+                                                  1 if silu else 0, impl, 1 if out_fp8 else 0, float(out_scale), C.c_void_p(d_y_ptr), C.byref(o),
+                                                  C.byref(rep)))
+        out = {name: getattr(rep, name) for name, _ in _lib.NormReport._fields_}
+        out["kernel"] = rep.kernel.decode()
+        return out
+
+    POINTWISE_OPS = ("layernorm", "geglu", "gelu", "silu", "add_pos", "nchw_to_cb16", "tokens_to_cb16", "vae_post")
+
+    def pointwise_f16(self, op: str, d_x_ptr: int, d_y_ptr: int, N, C_, P, eps: float = 0.0, v0: Optional[np.ndarray] = None,
+                      v1: Optional[np.ndarray] = None, **opts) -> None:
+        """One pointwise / layout kernel of csrc/nn_kernels.hip on its own (include/ltk.h: ltk_pointwise_f16); op: a name of
+        POINTWISE_OPS, v0 / v1: gamma / beta of the LayerNorm, the position or additive table; `opts` = the fields of ltk_norm_opts."""
+        a0 = np.ascontiguousarray(v0, dtype=np.float32) if v0 is not None else None
+        a1 = np.ascontiguousarray(v1, dtype=np.float32) if v1 is not None else None
+        o = _lib.NormOpts(**{name: int(v) for name, v in opts.items()})
+        _lib.check(self._lib.ltk_pointwise_f16(self._h, self.POINTWISE_OPS.index(op), C.c_void_p(d_x_ptr) if d_x_ptr else None, C.c_void_p(d_y_ptr),
+                                               N, C_, P, float(eps), a0.ctypes.data if a0 is not None else None,
+                                               a1.ctypes.data if a1 is not None else None, C.byref(o)))
+
     def attention_f16(self, q, k, v, o, N, heads, d16, Tq, Tk, impl: int = 0) -> None:
         """Standalone attention on CB16 tensors (include/ltk.h: ltk_attention_f16).  q, k, v, o: (device pointer, cbt, cb0) each - the
         buffer, its channel blocks and the first block of head 0; impl 0 = the program's choice, 1 = the per-wave / wide kernel, 2 = the

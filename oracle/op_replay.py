@@ -25,6 +25,9 @@ op's error and nothing upstream.  Beside `ref` the replay evaluates, in float32 
                           s = 2^-24 ceil(log2 n) |gamma| rstd |mean|: x - mean is taken in fp32 from a mean that is a tree sum of n
                           fp32 terms (n = C, or the group's channels x pixels), one rounding of 2^-24 |mean| per level; it
                           matters where x_hat is near 0 and |mean| / std is large, and nothing relative to |x_hat| covers it;
+                          no term for the variance: a device that sums x - k (k an element of the set) loses ((mean - k) / std)^2 2^-24 per
+                          rounding, inside the terms above also at |mean| = 256 std (tests/test_norm_host.py); un-shifted sums lose
+                          (mean / std)^2 2^-24 and are a fault the bound is there to catch (tests/norm_cases.py, `unshifted`);
         GEGLU             A = |ref|,  c = 2^-10,  s = 2^-23 |a| |g|: Phi(g) = (1 + erf(g / sqrt 2)) / 2 evaluated in fp32 carries an absolute
                           error of 2^-25 and more however small Phi is (the sum cancels in the negative tail), so a gelu(g) has
                           |a| |g| 2^-25 that no bound relative to |ref| covers;  in the projection's epilogue (the projection is never rounded): first-order

@@ -7,6 +7,8 @@
 #                                  256-frame and MuseTalk (fp16 / fp8) workloads -> gpurun_out/<tag>/ ; summarise with make_profile_summary.py
 #   layers <knob-settings...> -- <frames...>   scripts/layer_times.py: per-layer times under knob settings, interleaved rounds
 #   ab-lib <tag> <a.so> <b.so> ... in-job A/B of several builds of libltk_hip.so (LTK_LIB), two interleaved rounds (MT=0 skips MuseTalk)
+#   gn-ab <tag> <a.so> <b.so> ...  in-job A/B of the GroupNorm kernels between builds (scripts/gn_lib_ab.py: single ops + the 16-frame MuseTalk pass), three
+#                                  interleaved rounds, medians -> gn_ab_<tag>.txt in the output directory
 #   ablate [small|big]             conv3 ablation masks per layer (needs ab_libs/libltk_hip_ablate.so: scripts/build_variant.sh ablate -DLTK_ABLATE_BUILD=1)
 #   pmc-layer                      SQ counters of single-layer launches (conv_ablate.py under rocprofv3 --pmc)
 #   clock [layers...]              scripts/conv_clock.py: the real conv3 kernel on random / constant / zero operands, un-profiled (HIP events) and under
@@ -67,6 +69,15 @@ ab-lib)
     fi
   done; done
   cat $LOG ;;
+gn-ab)
+  TAG=$1; shift; LOG=$O/gn_ab_$TAG.log; : > $LOG
+  for rnd in 1 2 3; do for lib in "$@"; do
+    echo "######## round $rnd lib $lib" >> $LOG
+    LTK_LIB=$R/$lib timeout -k 10 240 python scripts/gn_lib_ab.py 16 20 > $O/gn_ab_run.log 2>&1; rc=$?
+    grep "^gn-ab" $O/gn_ab_run.log >> $LOG
+    if [ $rc -ne 0 ]; then echo "round $rnd $lib: exit $rc, stopping"; tail -5 $O/gn_ab_run.log; exit $rc; fi     # nothing more on a GPU that may have faulted
+  done; done
+  python scripts/gn_lib_ab.py --summary $LOG | tee $O/gn_ab_$TAG.txt ;;
 ablate)
   LTK_LIB=$R/ab_libs/libltk_hip_ablate.so ABLATE_SET=$1 SWEEP_FRAMES=${FRAMES:-16} ABLATE_MASKS=${MASKS:-0,1,2,3,4,7,16,64,68} timeout 900 python scripts/conv_ablate.py 2>&1 | tee $O/ablate_${TAG:-run}.txt ;;
 pmc-layer)
