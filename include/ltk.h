@@ -471,6 +471,13 @@ int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int C
                       int transposed, int out_pad, const float* scale, const float* shift,
                       const void* d_res, int relu, void* d_y, const ltk_conv_opts* opts, ltk_conv_report* rep);
 
+/* What ltk_conv2d_f16_ex decides about the same call before it allocates or enqueues anything, on the host alone (no engine, no GPU):
+ * the option and view checks, the plan's route (conv_route), conv3's launch plan (conv3_plan_launch) with the split-K scratch taken as
+ * unbounded, the row families' shape checks.  `has_res`: a residual would be passed.  `rep` as above.  Refusals that only a launcher
+ * makes (more rows or frames than a row kernel is built for) are not seen here. */
+int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                        int transposed, int out_pad, int has_res, int relu, const ltk_conv_opts* opts, ltk_conv_report* rep);
+
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */
 int ltk_debug_conv3_variants(char* buf, int cap);

@@ -144,6 +144,7 @@ SYMBOLS = {
     "ltk_conv2d_f16_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
+    "ltk_debug_conv_plan": (C.c_int, [C.c_int] * 15 + [C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
     "ltk_debug_conv3_variants": (C.c_int, [C.c_char_p, C.c_int]),
     "ltk_groupnorm_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),

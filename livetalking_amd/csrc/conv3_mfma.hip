@@ -6,7 +6,9 @@
 //   * ConvTranspose2d(k3,s2,p1,op1): all four sub-pixel phases in ONE block       G = 4
 //     (the (TH+1)x(TW+1) input patch is staged once per channel chunk and its four
 //     shifted MFMA operands feed the 1/2/2/4 taps of the four phases)
-// What changed against conv_mfma.hip (kept for the 7x7 / strided layers):
+// Host side, at the end of this file: conv3_plan_launch decides everything about a launch without touching the device (checks, the
+// tile rule k3_choose_tile over k3_tile, split-K, the lin_fk / lin_mp diversion, LDS bytes, kernel, report); conv3_launch enqueues it.
+// What changed against conv_mfma.hip (the first generation, kept for the 7x7 / strided layers; plans for both: conv_plan.hip):
 //   * staging is global_load_lds_dwordx4 straight into LDS (no staging VGPRs, no
 //     ds_write pass), two LDS stages, one barrier per channel chunk;
 //   * a wave owns PXW x 32 pixels x NBT x 32 output channels (G = 1: 128 px x 64 ch =
@@ -36,7 +38,7 @@
 // 256-B windows a 16-lane group touches use four different unit slots.  The permutation stays inside 64 B of a row, so the LDS-DMA
 // still moves whole lines; the patch row pitch is even for S = 2.  (Conflict-free when a lane group reads ONE patch row - 32-pixel-wide
 // tiles; on 16- / 8-pixel-wide tiles a group spans several rows whose offsets the key does not see and part of the conflicts remain.)
-#include "conv_mfma.h"
+#include "conv_host.h"
 #include "misc_kernels.h"
 #include "tune.h"
 
@@ -1361,18 +1363,6 @@ static k3_kernel_t k3_pick_s2(int NBT, int NC8) {     // 3x3 stride 2 pad 1 (fac
     return k3_pick_f16(1, NBT, 2, NC8, 9, 2);
 }
 
-static int ceil_log2_(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-static unsigned magic_u16_(int d) { return (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
-
-#define HIPCHK3(expr)                                                                 \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess) {                                                       \
-            if (err) *err = std::string(#expr) + ": " + hipGetErrorString(_e);        \
-            return -2;                                                                \
-        }                                                                             \
-    } while (0)
-
 constexpr int kMaxKSplit = 32;
 
 bool conv3_lin_fk_k(int Cin) { return Cin == 320 || Cin == 640 || Cin == 512 || Cin == 384 || Cin == 1280; }
@@ -1431,7 +1421,99 @@ size_t conv3_partial_bytes(const ConvPlan& p, int N, int H, int W) {
     return (size_t)kMaxKSplit * N * Ho * Wo * p.CoutPad * sizeof(float);
 }
 
-int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std::string* err) {
+// ---- the tile
+// The pixel tile of a launch at tile width `pxw` (128 * pxw output pixels per block) over N images of Ho x Wo output pixels
+struct K3Tile {
+    int l2w, l2h, NB;                // 2^l2w x 2^l2h pixels of NB images
+    int PH, PW, npix, SLOTS;         // the input patch, its pixels over the NB images, 16-byte slots per channel-block image
+    int swz_x, swz_row;              // K3Args
+    int tiles_x, tiles_y, tiles_n;
+    long long blocks;                // pixel tiles of the launch
+    bool fit;                        // the patch fits the staging budget of the instantiations at this pxw
+};
+
+// `S` stride, `ext` halo pixels of the patch beyond the tile (both directions together)
+static K3Tile k3_tile(int pxw, int N, int Ho, int Wo, int S, int ext, int NC8, int T) {
+    K3Tile t;
+    const int M = 128 * pxw;
+    const int lm = ceil_log2(M);
+    t.l2w = std::min(5, ceil_log2(Wo));
+    t.l2h = std::min(lm - t.l2w, ceil_log2(Ho));
+    t.NB = M >> (t.l2w + t.l2h);
+    t.NB = std::max(1, std::min(t.NB, N));
+    t.PH = ((1 << t.l2h) - 1) * S + 1 + ext; t.PW = ((1 << t.l2w) - 1) * S + 1 + ext;
+    if (S == 2) t.PW = (t.PW + 1) & ~1;                  // the stride-2 LDS image permutes units inside aligned pixel pairs of a row
+    // stride-1 images: column key on 32-pixel tile rows, row key below (header); 8-pixel rows with a halo need a row pitch of 12 pixels for it
+    t.swz_x = 1; t.swz_row = 0;
+    if (S == 1 && t.l2w <= 4) {
+        t.swz_x = 0; t.swz_row = 1;
+        if (t.l2w == 3 && ext > 0) t.PW = 12;
+    }
+    // tiny maps: the halo makes NB patches larger than the staging budget -> fewer images per tile
+    while (t.NB > 1 && (NC8 / 2) * ((2 * t.NB * t.PH * t.PW + 63) / 64 * 64) > k3_maxa(pxw, NC8, S, T) * 256) --t.NB;
+    t.npix = t.NB * t.PH * t.PW;
+    t.SLOTS = (2 * t.npix + 63) / 64 * 64;
+    t.tiles_x = (Wo + (1 << t.l2w) - 1) >> t.l2w; t.tiles_y = (Ho + (1 << t.l2h) - 1) >> t.l2h;
+    t.tiles_n = (N + t.NB - 1) / t.NB;
+    t.blocks = (long long)t.tiles_x * t.tiles_y * t.tiles_n;
+    t.fit = (NC8 / 2) * t.SLOTS <= k3_maxa(pxw, NC8, S, T) * 256 && t.npix < 32768;
+    return t;
+}
+
+// The tile rule (does not change any output element's summation order): *PXW / *NBT come in as the defaults after the knobs and leave
+// as the choice; returns its tile (fit = false: nothing can be staged).  kn_pxw / kn_nbt: the caller's per-layer choice or the sweep
+// knobs, 0 = the rule; `head`: the fused output head is asked for.
+static K3Tile k3_choose_tile(const ConvPlan& p, int N, int Ho, int Wo, int ext, int nchunks, int kn_pxw, int kn_nbt, bool forced_tile, bool head,
+                             int* PXW, int* NBT) {
+    const int G = p.v3_G, T = p.v3_T, NC8 = p.NC8, S = p.v3_S;
+    if (G == 1 && T == 9 && S == 1 && kn_pxw == 0 && kn_nbt == 0) {
+        // 3x3 stride 1: the largest tile that still gives the chip ~1.5 items per CU.  Measured per layer and frame count
+        // (scripts/conv_sweep2.py, profiles/r02_conv_sweep.txt): with fewer items a launch runs one wave per SIMD and
+        // cannot hide its own DMA latency -- at 16 frames 128 ch @32^2 takes 22.8 us as 128 items of 256 px x 64 ch and
+        // 10.7 us as 512 items of 128 px x 32 ch -- while smaller tiles than needed re-read the weight slab for nothing.
+        static const int cand[6][2] = {{4, 2}, {4, 1}, {2, 2}, {2, 1}, {1, 2}, {1, 1}};      // {PXW, NBT}
+        K3Tile best = {};
+        for (int ci = 0; ci < 6; ++ci) {
+            const int pxw = cand[ci][0], nbt = cand[ci][1];
+            // 512 px x 32 ch only for the layers that have no more than 32 output channels
+            if ((pxw == 4 && NC8 != 2) || (nbt == 2 && p.lCout < 64) || (pxw == 4 && nbt == 1 && p.lCout >= 64)) continue;
+            // the fused output head exists for the 512- and 256-pixel tiles only: a one-frame launch (--batch_size 1, or the
+            // one-frame remainder of a micro-batched call) would otherwise settle on 128-pixel tiles and be rejected below
+            if (head && pxw == 1) continue;
+            const K3Tile t = k3_tile(pxw, N, Ho, Wo, S, ext, NC8, T);
+            if (!t.fit) continue;
+            best = t; *PXW = pxw; *NBT = nbt;
+            // (640 input channels and more: ~1 item per CU is enough - a 40-chunk item hides its own start-up, and the larger tile
+            // re-reads less: MuseTalk's 640-channel 16^2 convs 67 -> 48 us as 320 items of 128 px x 64 ch instead of 640 of 128 x 32)
+            if (t.blocks * ((p.lCout + 32 * nbt - 1) / (32 * nbt)) >= (nchunks >= 40 ? 256 : 384)) break;
+        }
+        return best;
+    }
+    K3Tile t = k3_tile(*PXW, N, Ho, Wo, S, ext, NC8, T);
+    if (*PXW == 4) {
+        const long long nt = (p.lCout + 32 * *NBT - 1) / (32 * *NBT);
+        constexpr int kPxw4MinItems = 448;      // a forced 512-pixel tile only when it still gives this many items
+        if (!t.fit || (!forced_tile && t.blocks * nt < kPxw4MinItems)) { *PXW = 2; t = k3_tile(*PXW, N, Ho, Wo, S, ext, NC8, T); }
+    }
+    return t;
+}
+
+// ---- the launch plan
+// What conv3_plan_launch decides: the kernel of one of four families, its launch dimensions, and K3Args with everything but the
+// pointers (conv3_launch fills those from the plan and the ConvIO)
+struct K3Launch {
+    enum Family { CONV3, HEAD, LIN } family;     // (K3Args) / (K3Args, HeadArgs) / (K3Args, int, int, int): lin_fk_kernel and lin_mp_kernel
+    const void* kernel;
+    unsigned grid, block;
+    size_t lds;                                  // dynamic LDS of the launch
+    int lds_attr;                                // ... and what the instantiation is allowed (ensure_dyn_lds)
+    int lin[3];                                  // LIN: the kernel's scalar arguments
+    K3Args a;
+};
+
+int conv3_plan_launch(const ConvPlan& p, const ConvIO& io_in, K3Launch* k3, std::string* err) {
+    K3Launch local;
+    K3Launch& L = k3 ? *k3 : local;
     // four-phase upsample-conv: the caller describes the conv on the UPSAMPLED map (io.H x io.W, ups = 1); the kernel works on
     // the source map and writes the four phases of every source pixel, exactly like the merged transposed conv
     ConvIO io = io_in;
@@ -1439,10 +1521,9 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         if (!io.ups || ((io.H | io.W) & 1)) { if (err) *err = "conv3: a four-phase upsample-conv plan needs ups = 1 and even H, W"; return -1; }
         io.H /= 2; io.W /= 2; io.ups = 0;
     }
-    K3Args a;
+    K3Args& a = L.a;
     memset(&a, 0, sizeof(a));
     const int G = p.v3_G, T = p.v3_T, NC8 = p.NC8;
-    a.x = io.x; a.w = p.d_w; a.scale = p.d_scale; a.shift = p.d_shift; a.res = io.res; a.y = io.y;
     a.N = io.N; a.H = io.H; a.W = io.W; a.x_cbt = io.x_ld >> 4; a.x_cb0 = io.x_coff >> 4;
     a.res_cbt = io.res_ld >> 4; a.res_cb0 = io.res_coff >> 4;
     int y_ld = io.y_ld;
@@ -1472,73 +1553,21 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     }
     a.nchunks = (p.Cin / 8) / NC8;
     a.Mtot = (long long)io.N * a.HoA * a.WoA;
+    const bool head = io.head_w != nullptr && io.head_outs != nullptr;
 
-    // tile selection (does not change any output element's summation order)
+    // the tile
     int NBT = (G == 4) ? 1 : ((p.lCout >= 64) ? 2 : 1);
     int PXW = (G == 1 && T == 9 && NC8 == 2 && S == 1) ? 4 : 2;
-    // a caller's per-layer choice wins over the sweep knobs; 0 = the rule below
+    // a caller's per-layer choice wins over the sweep knobs; 0 = the rule
     const int kn_pxw = io.force_pxw ? io.force_pxw : knob(K_CONV_PXW), kn_nbt = io.force_nbt ? io.force_nbt : knob(K_CONV3_NBT);
     if (kn_pxw == 2 || (kn_pxw == 1 && G == 1 && T == 9 && S == 1) || (kn_pxw == 4 && PXW == 4)) PXW = kn_pxw;
     if (kn_nbt == 1) NBT = 1;
     const bool forced_tile = io.force_pxw != 0 && io.force_nbt != 0;
-    int l2w = 0, l2h = 0, NB = 1, PH = 1, PW = 1, npix = 0, SLOTS = 0, swz_x = 1, swz_row = 0;
-    long long blocks = 0;
-    auto geom = [&](int pxw) -> bool {
-        const int M = 128 * pxw;
-        const int lm = ceil_log2_(M);
-        l2w = std::min(5, ceil_log2_(a.Wo));
-        l2h = std::min(lm - l2w, ceil_log2_(a.Ho));
-        NB = M >> (l2w + l2h);
-        NB = std::max(1, std::min(NB, io.N));
-        PH = ((1 << l2h) - 1) * S + 1 + ext; PW = ((1 << l2w) - 1) * S + 1 + ext;
-        if (S == 2) PW = (PW + 1) & ~1;                      // the stride-2 LDS image permutes units inside aligned pixel pairs of a row
-        // stride-1 images: column key on 32-pixel tile rows, row key below (header); 8-pixel rows with a halo need a row pitch of 12 pixels for it
-        swz_x = 1; swz_row = 0;
-        if (S == 1 && l2w <= 4) {
-            swz_x = 0; swz_row = 1;
-            if (l2w == 3 && ext > 0) PW = 12;
-        }
-        // tiny maps: the halo makes NB patches larger than the staging budget -> fewer images per tile
-        while (NB > 1 && (NC8 / 2) * ((2 * NB * PH * PW + 63) / 64 * 64) > k3_maxa(pxw, NC8, S, T) * 256) --NB;
-        npix = NB * PH * PW;
-        SLOTS = (2 * npix + 63) / 64 * 64;
-        const int tiles_x = (a.Wo + (1 << l2w) - 1) >> l2w, tiles_y = (a.Ho + (1 << l2h) - 1) >> l2h;
-        const int tiles_n = (io.N + NB - 1) / NB;
-        blocks = (long long)tiles_x * tiles_y * tiles_n;
-        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tiles_n = tiles_n;
-        return (NC8 / 2) * SLOTS <= k3_maxa(pxw, NC8, S, T) * 256 && npix < 32768;
-    };
     const bool conv3x3 = G == 1 && T == 9 && S == 1;
-    bool fit;
-    if (conv3x3 && kn_pxw == 0 && kn_nbt == 0) {
-        // 3x3 stride 1: the largest tile that still gives the chip ~1.5 items per CU.  Measured per layer and frame count
-        // (scripts/conv_sweep2.py, profiles/r02_conv_sweep.txt): with fewer items a launch runs one wave per SIMD and
-        // cannot hide its own DMA latency -- at 16 frames 128 ch @32^2 takes 22.8 us as 128 items of 256 px x 64 ch and
-        // 10.7 us as 512 items of 128 px x 32 ch -- while smaller tiles than needed re-read the weight slab for nothing.
-        static const int cand[6][2] = {{4, 2}, {4, 1}, {2, 2}, {2, 1}, {1, 2}, {1, 1}};      // {PXW, NBT}
-        fit = false;
-        for (int ci = 0; ci < 6; ++ci) {
-            const int pxw = cand[ci][0], nbt = cand[ci][1];
-            // 512 px x 32 ch only for the layers that have no more than 32 output channels
-            if ((pxw == 4 && NC8 != 2) || (nbt == 2 && p.lCout < 64) || (pxw == 4 && nbt == 1 && p.lCout >= 64)) continue;
-            // the fused output head exists for the 512- and 256-pixel tiles only: a one-frame launch (--batch_size 1, or the
-            // one-frame remainder of a micro-batched call) would otherwise settle on 128-pixel tiles and be rejected below
-            if (io.head_w != nullptr && io.head_outs != nullptr && pxw == 1) continue;
-            if (!geom(pxw)) continue;
-            fit = true; PXW = pxw; NBT = nbt;
-            // (640 input channels and more: ~1 item per CU is enough - a 40-chunk item hides its own start-up, and the larger tile
-            // re-reads less: MuseTalk's 640-channel 16^2 convs 67 -> 48 us as 320 items of 128 px x 64 ch instead of 640 of 128 x 32)
-            if (blocks * ((p.lCout + 32 * nbt - 1) / (32 * nbt)) >= (a.nchunks >= 40 ? 256 : 384)) break;
-        }
-    } else {
-        fit = geom(PXW);
-        if (PXW == 4) {
-            const long long nt = (p.lCout + 32 * NBT - 1) / (32 * NBT);
-            constexpr int kPxw4MinItems = 448;      // a forced 512-pixel tile only when it still gives this many items
-            if (!fit || (!forced_tile && blocks * nt < kPxw4MinItems)) { PXW = 2; fit = geom(PXW); }
-        }
-    }
-    if (!fit) { if (err) *err = "conv3: patch does not fit the staging budget"; return -1; }
+    const K3Tile tile = k3_choose_tile(p, io.N, a.Ho, a.Wo, ext, a.nchunks, kn_pxw, kn_nbt, forced_tile, head, &PXW, &NBT);
+    if (!tile.fit) { if (err) *err = "conv3: patch does not fit the staging budget"; return -1; }
+    const long long blocks = tile.blocks;
+    a.tiles_x = tile.tiles_x; a.tiles_y = tile.tiles_y; a.tiles_n = tile.tiles_n;
     // 1x1 convs (plain GEMMs): a 128-cout block halves the A traffic per MAC (the A tile has no tap reuse to amortise it)
     if (T == 1 && NC8 == 4 && G == 1 && p.lCout % 128 == 0 && ((blocks * (p.lCout / 128) >= 384 && kn_nbt == 0) || kn_nbt == 4)) NBT = 4;
     // (1x1 / linear layers on >= 1024 pixels: below one item per CU; MuseTalk's 640-channel projections on 4096 tokens are 10 %
@@ -1553,12 +1582,13 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     const int BN = NBT * 32;
     a.n_ntiles = (p.lCout + BN - 1) / BN;
     a.ablate = LTK_ABLATE_BUILD ? knob(K_ABLATE) : 0;
-    // LTK_SPLITK=0: never split (batch-size independent summation order); LTK_KSPLIT=n forces a factor (sweeps)
+
+    // split-K.  LTK_SPLITK=0: never split (batch-size independent summation order); LTK_KSPLIT=n forces a factor (sweeps)
     int ksplit = knob(K_SPLITK) ? k3_ksplit(blocks * a.n_ntiles, a.nchunks, T == 1 ? 0 : (G == 4 ? 8 : 4)) : 1;
     const int fks = io.force_ksplit ? io.force_ksplit : knob(K_KSPLIT);
     if (fks > 0 && knob(K_SPLITK)) ksplit = std::max(1, std::min(std::min(fks, kMaxKSplit), a.nchunks));
-    if (io.head_w != nullptr && io.head_outs != nullptr) ksplit = 1;      // the fused head finishes in the epilogue: no partial slabs
-    a.ln_out = io.ln_out; a.ln_in = io.ln_in; a.ln_out_tiles = io.ln_out_tiles; a.ln_in_tiles = io.ln_in_tiles; a.ln_eps = io.ln_eps;
+    if (head) ksplit = 1;      // the fused head finishes in the epilogue: no partial slabs
+    a.ln_out_tiles = io.ln_out_tiles; a.ln_in_tiles = io.ln_in_tiles; a.ln_eps = io.ln_eps;
     if (io.ln_out || io.ln_in) {                                          // LayerNorm fold: 1x1 layers, the epilogue sees whole sums
         if (!(G == 1 && T == 1 && !p.q8) || (io.ln_out && (p.lCout % 32 || io.ln_out_tiles != p.lCout / 32)) || (io.ln_in && io.ln_in_tiles <= 0)) {
             if (err) *err = "conv3: the LayerNorm fold is a 1x1-layer feature (32-channel tiles)"; return -1;
@@ -1569,27 +1599,28 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         if (!(G == 1 && T == 1 && !p.q8 && p.lCout % 32 == 0 && !io.res)) { if (err) *err = "conv3: the GEGLU epilogue is a 1x1-layer feature"; return -1; }
         ksplit = 1;
     }
+
     // short-K linear layers on many tokens: lin_fk_kernel (A rows in registers, full-K weight slabs through LDS)
     const int mp_nsl = (G == 1 && T == 1 && S == 1) ? conv3_lin_mp_nsl(p.Cin, a.Mtot, p.lCout) : 0;
     if (G == 1 && T == 1 && S == 1 && !p.q8 && !p.mx && !a.ups && !p.gemm_1x1_expand && knob(K_LIN_FK) && (conv3_lin_fk_k(p.Cin) || mp_nsl) &&
         a.nchunks * NC8 * 8 == p.Cin && a.Mtot >= kLinFkMinRows && a.ablate == 0 && p.lCout % 16 == 0 &&
         (a.relu == 0 || a.relu == 1 || a.relu == 4)) {
+        typedef void (*lin_t)(const K3Args, int, int, int);
         const int nslabs = (p.lCout + 31) / 32;
+        const long long mtiles = (a.Mtot + 127) / 128;
+        L.family = K3Launch::LIN;
+        a.ksplit = 1;
         if (mp_nsl) {          // lin_mp_kernel: passes of 1280 channels, NSL slabs' accumulators per block
             const int NSL = mp_nsl;
-            const long long mt = (a.Mtot + 127) / 128;
             const int ng = (nslabs + NSL - 1) / NSL;
-            typedef void (*mp_t)(const K3Args, int, int, int);
-            const mp_t mk = NSL == 2 ? (mp_t)lin_mp_kernel<2> : (mp_t)lin_mp_kernel<3>;
-            const size_t mb = (size_t)2 * 2 * 20 * 1024 + 1024 + (size_t)NSL * 4 * 4096;
-            HIPCHK3((hipError_t)ensure_dyn_lds((const void*)mk, (int)mb));
-            a.ksplit = 1; a.partial = nullptr;
+            L.kernel = (const void*)(NSL == 2 ? (lin_t)lin_mp_kernel<2> : (lin_t)lin_mp_kernel<3>);
+            L.lds = (size_t)2 * 2 * 20 * 1024 + 1024 + (size_t)NSL * 4 * 4096;
+            L.lds_attr = (int)L.lds;
+            L.grid = (unsigned)(mtiles * ng); L.block = 512;
+            L.lin[0] = ng; L.lin[1] = nslabs; L.lin[2] = p.Cin / 1280;
             if (io.report) { *io.report = ConvReport(); snprintf(io.report->kernel, sizeof(io.report->kernel), "lin_mp_kernel<%d>", NSL); }
-            hipLaunchKernelGGL(mk, dim3((unsigned)(mt * ng)), dim3(512), mb, stream, a, ng, nslabs, p.Cin / 1280);
-            HIPCHK3(hipGetLastError());
             return 0;
         }
-        const long long mtiles = (a.Mtot + 127) / 128;
         // blocks a launch aims at: the output channels are split into groups of slabs until the grid has this many
         // (K = 1280: one 8-wave block per CU)
         constexpr int kLinFkBlocks = 512;
@@ -1599,21 +1630,21 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         ngroups = (nslabs + cpg - 1) / cpg;
         const long long grid = mtiles * ngroups;
         if (grid > 0 && grid <= 0x7fffffffll) {
-            typedef void (*lin_t)(const K3Args, int, int, int);
             // K = 320 / 640: MuseTalk's 32^2 / 16^2 transformer levels; 512: the VAE mid-block attention; 384: the stacked k | v projection of the audio context
             // 1280: the 8^2 level's projections and ff.net.2 of the 32^2 level (two waves per pixel subtile, K halves)
             const lin_t lk = p.Cin == 320 ? (lin_t)lin_fk_kernel<20, 20, 1> : p.Cin == 640 ? (lin_t)lin_fk_kernel<40, 20, 1> : p.Cin == 512 ? (lin_t)lin_fk_kernel<32, 16, 1>
                            : p.Cin == 384 ? (lin_t)lin_fk_kernel<24, 24, 1> : (lin_t)lin_fk_kernel<40, 20, 2>;
             const int ks = p.Cin == 1280 ? 2 : 1;
-            const size_t lbytes = (size_t)2 * ks * (p.Cin == 512 ? 16 : p.Cin == 384 ? 24 : 20) * 1024 + 512 + (ks == 2 ? 2 * 4 * 4096 : 0);
-            HIPCHK3((hipError_t)ensure_dyn_lds((const void*)lk, (int)lbytes));
-            a.ksplit = 1; a.partial = nullptr;
+            L.kernel = (const void*)lk;
+            L.lds = (size_t)2 * ks * (p.Cin == 512 ? 16 : p.Cin == 384 ? 24 : 20) * 1024 + 512 + (ks == 2 ? 2 * 4 * 4096 : 0);
+            L.lds_attr = (int)L.lds;
+            L.grid = (unsigned)grid; L.block = 256 * ks;
+            L.lin[0] = cpg; L.lin[1] = ngroups; L.lin[2] = nslabs;
             if (io.report) { *io.report = ConvReport(); snprintf(io.report->kernel, sizeof(io.report->kernel), "lin_fk_kernel"); }
-            hipLaunchKernelGGL(lk, dim3((unsigned)grid), dim3(256 * ks), lbytes, stream, a, cpg, ngroups, nslabs);
-            HIPCHK3(hipGetLastError());
             return 0;
         }
     }
+
     if (ksplit > 1) {   // fall back to fewer splits when the caller's scratch is smaller
         while (ksplit > 1 && (!io.partial || io.partial_cap < (size_t)ksplit * a.Mtot * p.CoutPad * sizeof(float))) ksplit /= 2;
     }
@@ -1623,20 +1654,20 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         ksplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
         a.ksplit = ksplit;
     }
-    a.log2TW = l2w; a.log2TH = l2h; a.NB = NB; a.PH = PH; a.PW = PW; a.npix = npix; a.SLOTS = SLOTS;
-    a.swz_x = swz_x; a.swz_row = swz_row;
-    a.magicPW = magic_u16_(PW); a.magicPHW = magic_u16_(PH * PW);
+    a.log2TW = tile.l2w; a.log2TH = tile.l2h; a.NB = tile.NB; a.PH = tile.PH; a.PW = tile.PW; a.npix = tile.npix; a.SLOTS = tile.SLOTS;
+    a.swz_x = tile.swz_x; a.swz_row = tile.swz_row;
+    a.magicPW = magic_u16(tile.PW); a.magicPHW = magic_u16(tile.PH * tile.PW);
 
-    if (ksplit > 1) a.partial = io.partial;
-
+    // the LDS budget
     const size_t a_bytes = (size_t)(NC8 / 2) * a.SLOTS * 16, b_bytes = (size_t)T * NC8 * BN * 16;
     size_t lds = 2 * (a_bytes + b_bytes);
     lds = (lds + 255) / 256 * 256;
     a.lds_scale_off = (int)lds;
     if (T != 1) lds += 2 * BN * sizeof(float);
     if (lds > 160 * 1024) { if (err) *err = "conv3: LDS budget exceeded"; return -1; }
+
+    // the kernel
     if (p.q8 && !(G == 1 && T == 9 && S == 1)) { if (err) *err = "conv3: fp8 operands are implemented for 3x3 stride-1 convs"; return -1; }
-    const bool head = io.head_w != nullptr && io.head_outs != nullptr;
     if (head && !(G == 1 && T == 9 && S == 1 && !p.q8 && NC8 == 2 && NBT == 1 && p.lCout == 32 && (PXW == 4 || PXW == 2) && ksplit == 1)) {
         if (err) *err = "conv3: fused head needs the 3x3 stride-1 32-cout configuration";
         return -1;
@@ -1645,10 +1676,16 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
     if (!k) { if (err) *err = "conv3: no kernel instantiation"; return -1; }
     const long long nblk = blocks * a.n_ntiles * ksplit;
     if (nblk <= 0 || nblk > 0x7fffffffll) { if (err) *err = "bad grid"; return -1; }
-    HIPCHK3((hipError_t)ensure_dyn_lds((const void*)k, 160 * 1024));
     a.nitems = (int)nblk;
     constexpr int kPersistBlocks = 512;      // resident grid size above which a launch walks its items persistently
     const long long grid = nblk > kPersistBlocks ? kPersistBlocks : nblk;
+    L.family = head ? K3Launch::HEAD : K3Launch::CONV3;
+    L.kernel = (const void*)k;
+    if (head) {
+        typedef void (*k3_head_t)(const K3Args, const HeadArgs);
+        L.kernel = (const void*)(PXW == 4 ? (k3_head_t)conv3_head_kernel<4> : (k3_head_t)conv3_head_kernel<2>);
+    }
+    L.grid = (unsigned)grid; L.block = 256; L.lds = lds; L.lds_attr = 160 * 1024;
     if (io.report) {
         ConvReport& r = *io.report;
         r = ConvReport();
@@ -1656,25 +1693,39 @@ int conv3_launch(const ConvPlan& p, const ConvIO& io_in, hipStream_t stream, std
         snprintf(r.kernel, sizeof(r.kernel), "%s", nm.c_str());
         r.G = G; r.NBT = NBT; r.PXW = PXW; r.NC8 = NC8; r.T = T; r.S = S; r.ksplit = ksplit; r.items = (int)nblk; r.grid = (int)grid;
     }
-    if (head) {
-        typedef void (*k3_head_t)(const K3Args, const HeadArgs);
-        const k3_head_t kh = PXW == 4 ? (k3_head_t)conv3_head_kernel<4> : (k3_head_t)conv3_head_kernel<2>;
-        HIPCHK3((hipError_t)ensure_dyn_lds((const void*)kh, 160 * 1024));
+    return 0;
+}
+
+int conv3_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
+    K3Launch L;
+    if (const int rc = conv3_plan_launch(p, io, &L, err)) return rc;
+    K3Args& a = L.a;
+    a.x = io.x; a.w = p.d_w; a.scale = p.d_scale; a.shift = p.d_shift; a.res = io.res; a.y = io.y;
+    a.ln_out = io.ln_out; a.ln_in = io.ln_in;
+    a.partial = a.ksplit > 1 ? io.partial : nullptr;
+    HIPCHK((hipError_t)ensure_dyn_lds(L.kernel, L.lds_attr));
+    switch (L.family) {
+    case K3Launch::LIN:
+        hipLaunchKernelGGL((void (*)(const K3Args, int, int, int))L.kernel, dim3(L.grid), dim3(L.block), L.lds, stream, a, L.lin[0], L.lin[1], L.lin[2]);
+        break;
+    case K3Launch::HEAD: {
         HeadArgs h;
         h.w = io.head_w;
         h.outs = reinterpret_cast<const OutPtrs*>(io.head_outs);
-        hipLaunchKernelGGL(kh, dim3((unsigned)grid), dim3(256), lds, stream, a, h);
-        HIPCHK3(hipGetLastError());
-        return 0;
+        hipLaunchKernelGGL((void (*)(const K3Args, const HeadArgs))L.kernel, dim3(L.grid), dim3(L.block), L.lds, stream, a, h);
+        break;
     }
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, stream, a);
-    HIPCHK3(hipGetLastError());
-    if (ksplit > 1) {
+    case K3Launch::CONV3:
+        hipLaunchKernelGGL((k3_kernel_t)L.kernel, dim3(L.grid), dim3(L.block), L.lds, stream, a);
+        break;
+    }
+    HIPCHK(hipGetLastError());
+    if (a.ksplit > 1) {
         const long long items = a.Mtot * (p.lCout >> 3);
         hipLaunchKernelGGL(conv3_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream,
-                           (const float*)io.partial, ksplit, a.Mtot, a.HoA * a.WoA, p.CoutPad, p.lCout, (const float*)p.d_scale,
+                           (const float*)io.partial, a.ksplit, a.Mtot, a.HoA * a.WoA, p.CoutPad, p.lCout, (const float*)p.d_scale,
                            (const float*)p.d_shift, io.res, a.res_cbt, a.res_cb0, io.y, a.y_cbt, a.y_cb0, a.relu);
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     return 0;
 }

@@ -1,10 +1,13 @@
 // Implicit-GEMM fp16 convolution on gfx950 MFMA (v_mfma_f32_32x32x16_f16) over channel-blocked activations
-// (CB16: [N][C/16][H][W][16]; network inputs of <= 8 channels are [N][H][W][8]).  Host-side plan + launch interface
-// shared by conv_mfma.hip (register-staged first-generation kernel) and conv3_mfma.hip (LDS-DMA kernel); DESIGN.md §2-3.
+// (CB16: [N][C/16][H][W][16]; network inputs of <= 8 channels are [N][H][W][8]).  Host-side plan + launch interface: conv_plan.hip
+// builds a plan in steps (conv_route decides, the rest packs and uploads) and dispatches a launch to conv_mfma.hip (register-staged
+// first-generation kernel, conv1_launch) or conv3_mfma.hip (LDS-DMA kernel: conv3_plan_launch decides, conv3_launch enqueues);
+// DESIGN.md §2-3.  conv_route and conv3_plan_launch are pure: the CPU suite holds them to tests/conv_cases.py through ltk_debug_conv_plan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace ltk {
@@ -27,44 +30,6 @@ __device__ __forceinline__ float gelu_as(float x) {
 }
 
 constexpr int kConvBM = 256;       // output pixels per workgroup (4 waves x 64)
-constexpr int kMaxTaps = 52;       // 7x7 = 49 (+ pairing pad)
-constexpr int kMaxPhases = 4;      // sub-pixel phases of a stride-2 transposed conv
-
-// One sub-pixel phase of a (transposed) convolution: a tap list over the input
-// patch, its own packed weight slab and output pixel offset.
-struct ConvPhase {
-    int T;                  // taps
-    int ooy, oox;           // output pixel = (oy*osy + ooy, ox*osx + oox)
-    int w_off16;            // offset of this phase's packed weights, in 16-byte units
-    short tapoff[kMaxTaps]; // dy*PW + dx per tap (patch-pixel units); unused entries 0
-};
-
-struct ConvArgs {
-    const f16* x;           // input CB16 buffer of x_ld channels; this tensor = channels [x_coff, x_coff+Cin)
-    const f16* w;           // packed weights (see pack_weights)
-    const float* scale;     // [Cout] folded BN scale
-    const float* shift;     // [Cout] folded BN shift (+conv bias)
-    const f16* res;         // residual (same pixel mapping as y) or nullptr
-    f16* y;                 // output CB16 buffer of y_ld channels, written at [y_coff, y_coff+Cout)
-    int N, H, W;
-    int x_ld, x_coff;
-    int Ho, Wo;             // logical output grid one phase covers
-    int y_ld, y_coff, HoA, WoA, osy, osx;
-    int res_ld, res_coff;
-    int Cin8;               // Cin / 8 (channel planes of 8 halfs)
-    int Cout;
-    int sh, sw, pad_y, pad_x;
-    int PH, PW;             // input patch per image tile
-    int NPIXP;              // padded pixels per LDS channel plane
-    int log2TW, log2TH, NB; // tile = NB images x TH x TW output pixels (<= 256)
-    int tiles_x, tiles_y, tiles_n, n_ntiles, nphase;
-    unsigned magicPW, magicPHW;
-    int nchunks;            // ceil(Cin8 / NC8)
-    int Tp;                 // taps per packed chunk slab (T, or T rounded up to even when NC8==1)
-    int relu;
-    ConvPhase ph[kMaxPhases];
-};
-
 // Static description of a conv layer (weights already packed on device).
 struct ConvPlan {
     // geometry
@@ -96,7 +61,6 @@ struct ConvPlan {
     // fp16 MFMA on gfx950): 64 e4m3 channels per chunk (NC8 = 4) = ONE MFMA per tap and tile pair; lane half hh contracts the
     // 32-byte cell 2*chunk + hh.  Same tensors, weight bytes and scales as q8.
     bool mx = false;
-    ConvPhase phase[kMaxPhases];
     // device data
     f16* d_w = nullptr;
     float* d_scale = nullptr;
@@ -106,9 +70,24 @@ struct ConvPlan {
     void out_dims(int H, int W, int* Ho, int* Wo) const;
 };
 
-// Build a plan: choose kernel configuration, pack weights (fp32 torch layout ->
-// fp16 [ntile][chunk][tap][plane][cout][8]) and upload.  `weight` is
-// [Cout][Cin][kh][kw] (conv) or [Cin][Cout][kh][kw] (transposed).
+// conv_route's answer beside the ConvPlan fields: per phase, the taps in pack order - weight element (ky, kx) read at patch offset
+// (dy, dx) - and the phase's output pixel offset (ooy, oox)
+struct ConvTap { int ky, kx, dy, dx; };
+struct ConvRoute {
+    std::vector<std::vector<ConvTap>> phases;
+    std::vector<std::pair<int, int>> phase_off;
+};
+// the knobs a plan is built under (tune.h), read once per plan by conv_plan_knobs()
+struct ConvPlanKnobs { bool v3_on; int conv3_nc8; };
+ConvPlanKnobs conv_plan_knobs();
+// Which kernel family serves the layer and in what configuration.  Pure (no HIP call): fills the geometry / config fields of *p
+// (everything above `device data`) and *r; returns 0, or -1 with the refusal in *err.
+int conv_route(ConvPlan* p, ConvRoute* r, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, bool transposed, int out_pad,
+               int quant, int ups4, const ConvPlanKnobs& knobs, std::string* err);
+
+// Build a plan (conv_plan.hip): conv_route, then the weight view (fp32 torch layout; the four-phase upsample-conv's pre-summed
+// weights; the fp8 scales), the slab packer (-> fp16 [ntile][chunk][tap][plane][cout][8]), the folded scale / shift and the upload.
+// `weight` is [Cout][Cin][kh][kw] (conv) or [Cin][Cout][kh][kw] (transposed).
 // Cin is padded up to a multiple of 8 with zero weights (CinPad = plan.Cin).
 int conv_plan_create(ConvPlan* p, const float* weight, int Cin, int Cout, int kh, int kw,
                      int sh, int sw, int ph, int pw, bool transposed, int out_pad,
@@ -128,14 +107,14 @@ inline int conv_fp8_quant(int Cin) { return (Cin % 64 == 0 && Cin >= 512) ? 2 : 
 unsigned char f32_to_e4m3(float v);
 void conv_plan_destroy(ConvPlan* p);
 
-// What conv3_launch enqueued for one layer (test hook ltk_conv2d_f16_ex, through ConvIO::report): the instantiation in the spelling of
+// What conv3_plan_launch chose for one layer (test hooks ltk_conv2d_f16_ex / ltk_debug_conv_plan, through ConvIO::report): the instantiation in the spelling of
 // conv3_variant_names(), its template arguments, the split factor after the scratch-capacity halving and the "no empty split"
 // correction, the work items and the resident grid.
 struct ConvReport {
     char kernel[64];
     int G, NBT, PXW, NC8, T, S, ksplit, items, grid;
 };
-// every fp16 instantiation conv3_launch's pickers can return, one name per line (conv3_mfma.hip: the table the pickers are made of)
+// every fp16 instantiation conv3_plan_launch's pickers can return, one name per line (conv3_mfma.hip: the table the pickers are made of)
 std::string conv3_variant_names();
 
 struct ConvIO {
@@ -158,14 +137,20 @@ struct ConvIO {
     float ln_eps = 1e-5f;
     float* partial = nullptr;      // split-K scratch (fp32 slabs) and its capacity in bytes; conv3 splits the
     size_t partial_cap = 0;        // channel loop of under-filled launches only when this is large enough
-    ConvReport* report = nullptr;  // conv3, test hook only: filled with what was launched.  With it set a forced tile (force_pxw / force_nbt)
+    ConvReport* report = nullptr;  // conv3, test hooks only: filled with what the planner chose.  With it set a forced tile (force_pxw / force_nbt)
                                    // that conv3 cannot serve as asked is refused; nullptr: nothing about the launch path changes
 };
 
 // Enqueue the layer on `stream`.  Returns 0 or a negative error (message in *err).
 int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err);
+// conv_launch up to the point where it would touch the device: conv3's planner (its report through io.report), or what the
+// first-generation path refuses before it looks at the tile.  Pure.
+int conv_launch_dry(const ConvPlan& p, const ConvIO& io, std::string* err);
 
-// conv3_mfma.hip
+// conv3_mfma.hip: conv3_launch = conv3_plan_launch (pure: checks, tile, split, kernel, grid, LDS bytes, K3Args geometry, report; no
+// HIP call, no device pointer dereferenced) + the enqueue.  `k3` may be null when only the verdict and the report are wanted.
+struct K3Launch;
+int conv3_plan_launch(const ConvPlan& p, const ConvIO& io, K3Launch* k3, std::string* err);
 int conv3_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err);
 // upper bound of the split-K scratch a launch of `N` images of H x W may use
 size_t conv3_partial_bytes(const ConvPlan& p, int N, int H, int W);

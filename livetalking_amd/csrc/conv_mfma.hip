@@ -1,6 +1,7 @@
 // Implicit-GEMM fp16 convolution for gfx950 (CDNA4) on MFMA, first generation (register-staged); activations are
 // channel-blocked CB16 ([N][C/16][H][W][16]), inputs of <= 8 channels [N][H][W][8].  Today it runs the 7x7, the
-// shallow strided 3x3 and the valid-padding layers; conv3_mfma.hip runs the rest.
+// shallow strided 3x3 and the valid-padding layers; conv3_mfma.hip runs the rest.  This file holds the kernel, its picker and its
+// launcher (conv1_launch, what conv_launch calls for a plan that is not conv3's); plans are built in conv_plan.hip.
 //
 // Replaces the torch.nn.Conv2d / ConvTranspose2d + BatchNorm2d(eval) + residual
 // + ReLU blocks of the reference generator (avatars/wav2lip/models/conv.py:5-44,
@@ -26,7 +27,7 @@
 //
 // LDS (dynamic, one array - keeps hipcc from draining vmcnt per k-step):
 //   [2 x A planes][2 x B slab][tap table]
-#include "conv_mfma.h"
+#include "conv_host.h"
 #include "tune.h"
 
 #include <hip/hip_fp16.h>
@@ -34,9 +35,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <cmath>
-#include <thread>
-#include <vector>
 
 namespace ltk {
 
@@ -44,11 +42,6 @@ typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct PhaseMeta {
-    int T, ooy, oox, w_off16;
-    signed char dy[kMaxTaps], dx[kMaxTaps];
-};
 
 struct KArgs {
     const f16* x; const f16* w; const float* scale; const float* shift; const f16* res; f16* y;
@@ -72,7 +65,6 @@ struct KArgs {
 
 // A-patch staging registers per thread (16-byte items): the largest variant a configuration has.
 constexpr int max_a_items(int NC8) { return NC8 == 4 ? 6 : (NC8 == 1 ? 5 : 10); }
-constexpr int kMaxBItems = 9;   // 16-byte weight items a thread stages per chunk
 constexpr int kTapTableBytes = 128;
 constexpr int kLdsLimit = 160 * 1024;
 
@@ -370,7 +362,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
 typedef void (*conv_kernel_t)(const KArgs);
 
 // `need` = 16-byte A items per thread this launch stages; returns the smallest instantiation that holds them.
-// A launch runs blocks of at most 64 output channels (NBT <= 2, conv_launch).
+// A launch runs blocks of at most 64 output channels (NBT <= 2, conv1_launch).
 static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int need) {
 #define KERNEL(nc8, nbt, maxa) (tt9 ? (conv_kernel_t)conv_mfma_kernel<nc8, nbt, true, maxa> : (conv_kernel_t)conv_mfma_kernel<nc8, nbt, false, maxa>)
     if (NC8 == 1) return (NBT == 1 && need <= 5) ? (conv_kernel_t)conv_mfma_kernel<1, 1, false, 5> : nullptr;
@@ -390,337 +382,9 @@ static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int need) {
     return nullptr;
 }
 
-static int ceil_log2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
+bool conv1_has_kernel(int NC8, int NBT, bool tt9) { return pick_kernel(NC8, NBT, tt9, 1) != nullptr; }
 
-void ConvPlan::out_dims(int H, int W, int* Ho, int* Wo) const {
-    if (!transposed) {   // out_pad on a plain conv = extra zero rows/columns at the bottom/right (diffusers Downsample2D
-                         // with padding=0: F.pad(x, (0,1,0,1)) then a stride-2 "valid" conv)
-        *Ho = (H + 2 * ph + out_pad - kh) / sh + 1;
-        *Wo = (W + 2 * pw + out_pad - kw) / sw + 1;
-    } else {
-        *Ho = (H - 1) * sh - 2 * ph + kh + out_pad;
-        *Wo = (W - 1) * sw - 2 * pw + kw + out_pad;
-    }
-}
-
-double ConvPlan::macs_per_image(int H, int W) const {
-    int Ho, Wo;
-    out_dims(H, W, &Ho, &Wo);
-    if (!transposed) return (double)Cout * kh * kw * Ho * Wo;  // x real Cin applied by caller
-    return (double)Cout * kh * kw * H * W;
-}
-
-#define HIPCHK(expr)                                                                  \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess) {                                                       \
-            if (err) *err = std::string(#expr) + ": " + hipGetErrorString(_e);        \
-            return -2;                                                                \
-        }                                                                             \
-    } while (0)
-
-unsigned char f32_to_e4m3(float v) {
-    // OCP e4m3fn: 1-4-3, bias 7, max 448 (0x7E), no infinities; subnormal step 2^-9
-    unsigned char sign = 0;
-    if (v < 0.f) { sign = 0x80; v = -v; }
-    if (!(v == v)) return 0x7F;                      // NaN
-    if (v >= 448.f) return sign | 0x7E;              // saturate (incl. the half-way case above 448)
-    if (v < 0.0009765625f) return sign;              // < 2^-10: rounds to zero (2^-10 itself is a tie -> even = 0)
-    int e;
-    (void)std::frexp(v, &e);                         // v = m * 2^e, m in [0.5, 1)
-    int E = e - 1;                                   // v = 1.x * 2^E
-    if (E < -6) E = -6;                              // subnormal range shares the exponent of the smallest normal
-    const float q = std::ldexp(v, 3 - E);            // in units of the spacing 2^(E-3)
-    float r = std::nearbyint(q);                     // round half to even (default rounding mode)
-    int mant = (int)r;                               // normals: 8..16, subnormals: 0..8
-    int be = E + 7;
-    if (E == -6 && mant < 8) return sign | (unsigned char)mant;             // subnormal (biased exponent 0)
-    if (mant == 16) { mant = 8; ++be; }
-    if (be > 15 || (be == 15 && mant - 8 > 6)) return sign | 0x7E;
-    return sign | (unsigned char)((be << 3) | (mant - 8));
-}
-
-int conv_plan_create(ConvPlan* p, const float* weight, int CinArg, int Cout, int kh, int kw,
-                     int sh, int sw, int ph, int pw, bool transposed, int out_pad,
-                     const float* scale, const float* shift, std::string* err, int quant, float act_scale, int ups4) {
-    *p = ConvPlan();
-    if (quant) {
-        if (transposed || kh != 3 || kw != 3 || sh != 1 || sw != 1 || ph != 1 || pw != 1 || CinArg % 32 != 0) {
-            if (err) *err = "fp8 operands: 3x3 stride-1 pad-1 convs with Cin % 32 == 0 only";
-            return -1;
-        }
-        p->q8 = true;
-        if (quant == 2) {
-            if (CinArg % 64 != 0) { if (err) *err = "MX fp8 operands: Cin % 64 == 0"; return -1; }
-            p->mx = true;
-        }
-    }
-    p->CinReal = CinArg;
-    // fp8: two channels per 16-bit unit; everything below (chunking, pack order, launch geometry) sees CinArg / 2 "channels"
-    const int CinReal = quant ? CinArg / 2 : CinArg;
-    // channel-blocked layout: whole 16-channel blocks; inputs of <= 8 channels are plain [N][H][W][8]
-    const int Cin = CinReal <= 8 ? 8 : (CinReal + 15) / 16 * 16;
-    p->kh = kh; p->kw = kw; p->sh = sh; p->sw = sw; p->ph = ph; p->pw = pw;
-    p->transposed = transposed; p->out_pad = out_pad;
-    p->Cin = Cin; p->Cout = Cout;
-
-    // logical conv the kernel executes
-    int lCout = Cout;        // output channels of the executed conv
-    int lsh = sh, lsw = sw;  // input stride
-    struct Tap { int ky, kx, dy, dx; };
-    std::vector<std::vector<Tap>> phases;
-    std::vector<std::pair<int, int>> phase_off;
-    const bool v3_on = knob(K_CONV_V3) != 0;
-    const bool is_convT_s2 = transposed && kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && out_pad == 1;
-    // Upsample2D = F.interpolate(scale_factor=2, nearest) + Conv2d(3x3, pad 1).  Output pixel (2y+py, 2x+px) reads upsampled rows
-    // 2y+py+ky-1, i.e. source rows y + floor((py+ky-1)/2): phase py=0 sees rows {y-1 <- ky 0, y <- ky 1,2}, phase py=1 rows
-    // {y <- ky 0,1, y+1 <- ky 2} (columns alike).  So every phase is a 2x2 conv on the SOURCE map whose weights are sums of the
-    // 3x3 taps: 16 (operand, phase) products per source pixel instead of 36.  Operands (dy,dx) in 0..2 address the 3x3 source
-    // neighbourhood (patch origin y-1, x-1); the kernel walks them row-major and feeds phases g = (py<<1)|px in ascending order.
-    std::vector<float> weff;
-    const float* wsrc = weight;
-    int wkh = kh, wkw = kw;
-    if (ups4 && v3_on && !transposed && !quant && kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 &&
-        out_pad == 0 && Cin % 16 == 0) {
-        p->v3 = true; p->v3_G = 4; p->v3_T = 16; p->ups4 = true;
-        lsh = lsw = 1;
-        std::vector<Tap> taps;
-        weff.assign((size_t)Cout * CinReal * 16, 0.f);
-        int t = 0;
-        for (int dy = 0; dy < 3; ++dy)
-            for (int dx = 0; dx < 3; ++dx)
-                for (int py = 0; py < 2; ++py)
-                    for (int px = 0; px < 2; ++px) {
-                        if (dy != py && dy != py + 1) continue;
-                        if (dx != px && dx != px + 1) continue;
-                        // 3x3 taps of this phase that land on source offset (dy, dx)
-                        int kys[2], nky = 0, kxs[2], nkx = 0;
-                        for (int ky = 0; ky < 3; ++ky) if (1 + ((py + ky - 1) >> 1) == dy) kys[nky++] = ky;     // floor((py+ky-1)/2) + 1
-                        for (int kx = 0; kx < 3; ++kx) if (1 + ((px + kx - 1) >> 1) == dx) kxs[nkx++] = kx;
-                        for (int co = 0; co < Cout; ++co)
-                            for (int ci = 0; ci < CinReal; ++ci) {
-                                float acc = 0.f;
-                                for (int a = 0; a < nky; ++a)
-                                    for (int b = 0; b < nkx; ++b) acc += weight[(((size_t)co * CinReal + ci) * 3 + kys[a]) * 3 + kxs[b]];
-                                weff[((size_t)co * CinReal + ci) * 16 + t] = acc;
-                            }
-                        taps.push_back({t >> 2, t & 3, dy, dx});
-                        ++t;
-                    }
-        if (t != 16) { if (err) *err = "ups4 tap table"; return -1; }
-        phases.push_back(taps);
-        phase_off.push_back({0, 0});
-        wsrc = weff.data(); wkh = 4; wkw = 4;
-    } else if (v3_on && is_convT_s2 && Cin % 16 == 0) {
-        // conv3 merged transposed conv: ONE phase of 9 taps over a 2x2 input neighbourhood, in the tap order the
-        // kernel's static table expects (offset (0,0): phases 0..3, (0,1): 1,3, (1,0): 2,3, (1,1): 3)
-        p->v3 = true; p->v3_G = 4; p->v3_T = 9;
-        lsh = lsw = 1;
-        phases.push_back({{1, 1, 0, 0}, {1, 2, 0, 0}, {2, 1, 0, 0}, {2, 2, 0, 0},
-                          {1, 0, 0, 1}, {2, 0, 0, 1}, {0, 1, 1, 0}, {0, 2, 1, 0}, {0, 0, 1, 1}});
-        phase_off.push_back({0, 0});
-    } else if (!transposed) {
-        std::vector<Tap> taps;
-        for (int y = 0; y < kh; ++y)
-            for (int x = 0; x < kw; ++x) taps.push_back({y, x, y, x});
-        phases.push_back(taps);
-        phase_off.push_back({0, 0});
-    } else if (sh == 1 && sw == 1 && ph == 0 && pw == 0 && out_pad == 0) {
-        // k x k transposed conv: only the 1x1-input case is supported (a GEMM to k*k*Cout channels)
-        p->gemm_1x1_expand = true;
-        lCout = kh * kw * Cout;
-        phases.push_back({{0, 0, 0, 0}});
-        phase_off.push_back({0, 0});
-    } else if (kh == 3 && kw == 3 && sh == 2 && sw == 2 && ph == 1 && pw == 1 && out_pad == 1) {
-        lsh = lsw = 1;
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-                std::vector<std::pair<int, int>> ys, xs;  // (k index, input offset)
-                if (py == 0) ys = {{1, 0}}; else ys = {{0, 1}, {2, 0}};
-                if (px == 0) xs = {{1, 0}}; else xs = {{0, 1}, {2, 0}};
-                std::vector<Tap> taps;
-                for (auto& yy : ys)
-                    for (auto& xx : xs) taps.push_back({yy.first, xx.first, yy.second, xx.second});
-                phases.push_back(taps);
-                phase_off.push_back({py, px});
-            }
-    } else {
-        if (err) *err = "unsupported transposed conv configuration";
-        return -1;
-    }
-
-    if (v3_on && !p->v3 && !transposed && Cin % 16 == 0 && kh == 3 && kw == 3 && sh == 2 && sw == 2 &&
-        ((ph == 1 && pw == 1 && out_pad == 0) || (ph == 0 && pw == 0 && out_pad == 1)) &&
-        // measured in the pass (profiles/r04_s2_conflict_free.txt; conv3's stride-2 LDS image is bank-conflict free since round 4), register-
-        // staged kernel -> conv3, 16 / 256 frames: 64->128 @64^2 16.9 -> 16.4 / 127 -> 94 us, 128->256 @32^2 20.4 -> 17.2 / 93 -> 69 us: conv3 from
-        // 64 input channels on.  The wide, shallow ones stay register-staged: 16->32 @256^2 22.7 -> 30.5 / 249 -> 389 us (one 16-channel chunk per
-        // item: 18 MFMAs per wave behind a 36-KB patch copy), 32->64 @128^2 15.0 -> 16.9 at 16 frames (-52 us at 256: a per-launch choice would
-        // need both weight packs).  The asymmetric-pad form exists only in conv3.
-        (Cin >= 64 || out_pad == 1)) {
-        p->v3 = true; p->v3_G = 1; p->v3_T = 9; p->v3_S = 2;
-    }
-    if (v3_on && !p->v3 && Cin % 16 == 0 && lsh == 1 && lsw == 1) {
-        if (!transposed && kh == 3 && kw == 3 && ph == 1 && pw == 1) { p->v3 = true; p->v3_G = 1; p->v3_T = 9; }
-        if ((!transposed && kh == 1 && kw == 1 && ph == 0 && pw == 0) || p->gemm_1x1_expand) { p->v3 = true; p->v3_G = 1; p->v3_T = 1; }
-    }
-    const int Cin8 = Cin / 8;
-    int NC8, NBT;
-    const int Tmax = (int)std::max_element(phases.begin(), phases.end(),
-                                           [](const std::vector<Tap>& a, const std::vector<Tap>& b) { return a.size() < b.size(); })->size();
-    const bool strided = (lsh > 1 || lsw > 1);
-    if (Cin8 == 1) {
-        NC8 = 1; NBT = 1;
-        if (lCout > 32) { if (err) *err = "Cin<=8 layers support Cout<=32"; return -1; }
-    } else {
-        if (Cin8 % 2) { if (err) *err = "Cin must be 8 or a multiple of 16"; return -1; }
-        NBT = lCout >= 128 ? 4 : (lCout >= 64 ? 2 : 1);
-        NC8 = (Cin8 >= 4) ? 4 : 2;
-        if (strided || Tmax > 9) { NC8 = 2; NBT = std::min(NBT, 2); }   // large patches: 10 staging items, 2 planes
-        // weight slab of one chunk must fit the staging registers (9 x 16 B per thread)
-        while (((NC8 == 1) ? ((Tmax + 1) / 2 * 2) : Tmax) * NC8 * NBT * 32 > kMaxBItems * 256) {
-            if (NC8 > 2) NC8 /= 2; else if (NBT > 1) NBT /= 2; else break;
-        }
-    }
-    if (p->v3) {
-        // 1x1: 64-channel chunks; wide outputs take 32-channel chunks so that a 128-cout block (conv3_launch) still fits two
-        // resident blocks per CU
-        if (p->v3_T == 1) NC8 = (Cin % 32 == 0 && lCout >= 128 && lCout % 128 == 0) ? 4 : (Cin % 64 == 0) ? 8 : 2;
-        else if (p->ups4) NC8 = 2;          // 16 weight matrices per chunk: 16-channel chunks keep two blocks per CU
-        else if (p->v3_G == 4) NC8 = (Cin % 32 == 0) ? 4 : 2;
-        // 16-channel chunks everywhere: measured (profiles/r02_conv_sweep.txt) equal or better than 32-channel chunks on
-        // every 3x3 layer at 16 frames and 25-28 % better on the 256/512-channel 8^2..16^2 maps at 256 frames (the
-        // smaller stage leaves room for two resident blocks and allows 512-pixel tiles); sweeps force 32 through knob CONV3_NC8
-        else NC8 = (knob(K_CONV3_NC8) == 4 && Cin % 32 == 0) ? 4 : 2;
-        if (p->v3_S == 2) NC8 = 2;
-        if (p->mx) NC8 = 4;                 // 4 planes of 16 e4m3 channels = the 64 channels one MX MFMA contracts
-        NBT = 2;
-    }
-    p->NC8 = NC8; p->NBT = NBT;      // NBT here = the widest block the staging registers allow
-    p->tt9 = (!transposed && kh == 3 && kw == 3 && NC8 >= 2);
-    p->nphase = (int)phases.size();
-    const int Tp = (NC8 == 1) ? ((Tmax + 1) / 2 * 2) : Tmax;
-    p->Tp = Tp;
-    if (!p->v3) {
-        if (Tp * NC8 * NBT * 32 > kMaxBItems * 256) { if (err) *err = "weight slab too large for staging registers"; return -1; }
-        if (!pick_kernel(NC8, std::min(NBT, 2), p->tt9, 1)) { if (err) *err = "no kernel instantiation for this configuration"; return -1; }
-    }
-
-    const int CoutPad = (lCout + 127) / 128 * 128;   // any block width <= 128 tiles it evenly
-    p->CoutPad = CoutPad;
-    p->lCout = lCout;
-    const int n_sub = CoutPad / 32;
-    const int nchunks = (Cin8 + NC8 - 1) / NC8;
-    const size_t slab_halfs = (size_t)Tp * NC8 * 32 * 8;
-    const size_t phase_halfs = (size_t)n_sub * nchunks * slab_halfs;
-    std::vector<f16> packed(phase_halfs * phases.size(), (f16)0.f);
-
-    auto wval = [&](int co, int ci, int ky, int kx) -> float {
-        if (ci >= CinReal) return 0.f;
-        if (!transposed) return wsrc[(((size_t)co * CinReal + ci) * wkh + ky) * wkw + kx];
-        return wsrc[(((size_t)ci * Cout + co) * wkh + ky) * wkw + kx];
-    };
-    // fp8: per-output-channel scale, and the 16-bit unit (two consecutive input channels, low byte first)
-    std::vector<float> wq_scale;
-    if (quant) {
-        wq_scale.assign(Cout, 1.f);
-        const size_t per = (size_t)CinArg * 9;
-        for (int co = 0; co < Cout; ++co) {
-            float m = 0.f;
-            for (size_t i = 0; i < per; ++i) m = std::max(m, std::fabs(weight[(size_t)co * per + i]));
-            if (m > 0.f) wq_scale[co] = 224.f / m;
-        }
-    }
-    auto wbits = [&](int co, int ci, int ky, int kx) -> uint16_t {
-        if (!quant) { const f16 h = (f16)wval(co, ci, ky, kx); uint16_t u; memcpy(&u, &h, 2); return u; }
-        if (ci >= CinReal) return 0;
-        const float s = wq_scale[co];
-        const float lo = weight[(((size_t)co * CinArg + 2 * ci) * 3 + ky) * 3 + kx] * s;
-        const float hi = weight[(((size_t)co * CinArg + 2 * ci + 1) * 3 + ky) * 3 + kx] * s;
-        return (uint16_t)(f32_to_e4m3(lo) | (f32_to_e4m3(hi) << 8));
-    };
-
-    std::vector<PhaseMeta> metas(phases.size());
-    for (size_t pi = 0; pi < phases.size(); ++pi) {
-        PhaseMeta& m = metas[pi];
-        memset(&m, 0, sizeof(m));
-        m.T = (int)phases[pi].size();
-        m.ooy = phase_off[pi].first;
-        m.oox = phase_off[pi].second;
-        m.w_off16 = (int)(pi * phase_halfs / 8);
-        for (int t = 0; t < m.T; ++t) { m.dy[t] = (signed char)phases[pi][t].dy; m.dx[t] = (signed char)phases[pi][t].dx; }
-        p->phase[pi].T = m.T; p->phase[pi].ooy = m.ooy; p->phase[pi].oox = m.oox; p->phase[pi].w_off16 = m.w_off16;
-        f16* base = packed.data() + pi * phase_halfs;
-        // the 32-cout sub-slabs are written to disjoint ranges: packed by a few host threads when the layer is large (a MuseTalk load
-        // packs 0.9 G weights: 16 s on one thread)
-        auto pack_range = [&](int nt0, int nt1) {
-        for (int nt = nt0; nt < nt1; ++nt)
-            for (int c = 0; c < nchunks; ++c)
-                for (int t = 0; t < m.T; ++t)
-                    for (int pl = 0; pl < NC8; ++pl) {
-                        const int c8 = c * NC8 + pl;
-                        if (c8 >= Cin8) continue;
-                        for (int n = 0; n < 32; ++n) {
-                            const int lco = nt * 32 + n;
-                            if (lco >= lCout) continue;
-                            int co = lco, ky = phases[pi][t].ky, kx = phases[pi][t].kx;
-                            if (p->gemm_1x1_expand) {
-                                // output channel order (cout block, position, 16): the result [N][k*k*Cout/16][1][1][16]
-                                // IS the channel-blocked k x k map [N][Cout/16][k][k][16]
-                                const int c16 = lco & 15, tt = lco >> 4, pos = tt % (kh * kw);
-                                co = (tt / (kh * kw)) * 16 + c16; ky = pos / kw; kx = pos % kw;
-                            }
-                            f16* dst = base + ((((size_t)(nt * nchunks + c) * Tp + t) * NC8 + pl) * 32 + n) * 8;
-                            for (int j = 0; j < 8; ++j) { const uint16_t u = wbits(co, c8 * 8 + j, ky, kx); memcpy(&dst[j], &u, 2); }
-                        }
-                    }
-        };
-        const size_t work = (size_t)n_sub * nchunks * m.T * NC8 * 256;
-        const int nthr = work < (size_t)4 << 20 ? 1 : std::max(1, std::min({(int)std::thread::hardware_concurrency(), 16, n_sub}));
-        if (nthr <= 1) pack_range(0, n_sub);
-        else {
-            std::vector<std::thread> th;
-            for (int k = 0; k < nthr; ++k) th.emplace_back(pack_range, (int)((long long)n_sub * k / nthr), (int)((long long)n_sub * (k + 1) / nthr));
-            for (std::thread& t : th) t.join();
-        }
-    }
-
-    // folded BN parameters (padded to CoutPad; replicated per position for the 1x1-expand case)
-    std::vector<float> sc(CoutPad, 0.f), sf(CoutPad, 0.f);
-    for (int i = 0; i < lCout; ++i) {
-        const int co = p->gemm_1x1_expand ? ((i >> 4) / (kh * kw)) * 16 + (i & 15) : i;
-        sc[i] = scale ? scale[co] : 1.f; sf[i] = shift ? shift[co] : 0.f;
-        if (quant) sc[i] /= wq_scale[co] * act_scale;        // acc = sum (w s_w)(x s_a)
-    }
-
-    p->w_bytes = packed.size() * sizeof(f16);
-    HIPCHK(hipMalloc((void**)&p->d_w, p->w_bytes + metas.size() * sizeof(PhaseMeta) + 256));
-    HIPCHK(hipMemcpy(p->d_w, packed.data(), p->w_bytes, hipMemcpyHostToDevice));
-    // phase metadata lives behind the weights (16-byte aligned)
-    {
-        const size_t off = (p->w_bytes + 15) / 16 * 16;
-        HIPCHK(hipMemcpy((char*)p->d_w + off, metas.data(), metas.size() * sizeof(PhaseMeta), hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc((void**)&p->d_scale, CoutPad * sizeof(float) * 2));
-    p->d_shift = p->d_scale + CoutPad;
-    HIPCHK(hipMemcpy(p->d_scale, sc.data(), CoutPad * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(p->d_shift, sf.data(), CoutPad * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-
-void conv_plan_destroy(ConvPlan* p) {
-    if (p->d_w) (void)hipFree(p->d_w);
-    if (p->d_scale) (void)hipFree(p->d_scale);
-    p->d_w = nullptr; p->d_scale = nullptr; p->d_shift = nullptr;
-}
-
-static unsigned magic_u16(int d) { return (unsigned)((0x100000000ull + (unsigned long long)d - 1) / (unsigned long long)d); }
-
-int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
-    if (p.v3) return conv3_launch(p, io, stream, err);
+int conv1_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
     KArgs a;
     memset(&a, 0, sizeof(a));
     const int NC8 = p.NC8;
@@ -732,7 +396,6 @@ int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::st
     a.res_cbt = io.res_ld >> 4; a.res_cb0 = io.res_coff >> 4;
     a.Cin8 = p.Cin / 8;
     a.relu = io.relu ? 1 : io.act;
-    if (io.ups) { if (err) *err = "input upsampling is a conv3 feature (3x3 s1 p1 / 1x1 layers)"; return -1; }
     int y_ld = io.y_ld;
     int kext_y, kext_x;
     if (p.gemm_1x1_expand) {

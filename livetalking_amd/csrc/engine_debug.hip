@@ -215,7 +215,7 @@ int conv2d_hook(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, co
     ConvPlan plan;
     std::string err;
     int rc = conv_plan_create(&plan, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, scale, shift, &err, quant, act_scale);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+    if (rc) return conv_status(rc, err);
     ConvIO io;
     io.partial = e->d_partial; io.partial_cap = e->partial_cap;
     io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = plan.Cin; io.x_coff = 0;   // (fp8: 16-bit units)
@@ -224,7 +224,7 @@ int conv2d_hook(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, co
     io.relu = relu; io.act = act;
     hipStream_t s = e->compute;
     std::lock_guard<std::mutex> g(e->mu);
-    auto launch = [&]() -> int { const int lrc = conv_launch(plan, io, s, &err); return lrc ? fail(lrc == -2 ? LTK_E_HIP : LTK_E_INVALID, err) : 0; };
+    auto launch = [&]() -> int { const int lrc = conv_launch(plan, io, s, &err); return lrc ? conv_status(lrc, err) : 0; };
     rc = launch();
     if (!rc && iters > 0 && ms_avg) {
         float ms = 0.f;
@@ -252,105 +252,157 @@ struct ConvPlanOwner { ConvPlan p; ~ConvPlanOwner() { conv_plan_destroy(&p); } }
 struct RowPlansOwner { RowGemmPlan p[4]; ~RowPlansOwner() { for (RowGemmPlan& q : p) rowgemm_plan_destroy(&q); } };
 }  // namespace
 
-int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, int kh, int kw, int sh, int sw,
-                      int ph, int pw, int transposed, int out_pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
-                      const ltk_conv_opts* opts, ltk_conv_report* rep) {
-    if (!e || !d_x || !weight || !d_y || !opts || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail(LTK_E_INVALID, "bad arguments");
+namespace {
+// What ltk_conv2d_f16_ex and ltk_debug_conv_plan derive from their arguments
+struct ConvHookCall {
+    int act = 0, x_ld = 0, y_ld = 0, res_ld = 0;
+    ConvIO io;                   // family 0: the launch without its pointers and scratch
+    int Ho = 0, Wo = 0;          // rowconv / rowconvT: the output map
+};
+
+void conv_report_copy(const ConvReport& cr, ltk_conv_report* rep) {
+    memcpy(rep->kernel, cr.kernel, sizeof(rep->kernel));
+    rep->G = cr.G; rep->NBT = cr.NBT; rep->PXW = cr.PXW; rep->NC8 = cr.NC8; rep->T = cr.T; rep->S = cr.S;
+    rep->ksplit = cr.ksplit; rep->items = cr.items; rep->grid = cr.grid;
+}
+
+// Everything ltk_conv2d_f16_ex decides before it allocates or enqueues, on the host alone: the options and the channel views; family
+// 0: conv_route and, for a conv3 plan, conv3_plan_launch with the split-K scratch taken as unbounded; the row families: their shape
+// refusals.  *rep (may be NULL) = what a launch of this call reports.
+int conv_hook_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad, bool has_res,
+                   int relu, const ltk_conv_opts* opts, ltk_conv_report* rep, ConvHookCall* c) {
+    if (!opts || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail(LTK_E_INVALID, "bad arguments");
     const ltk_conv_opts& o = *opts;
     if (o.family < 0 || o.family > 3 || o.act < 0 || o.act > 3 || o.ups < 0 || o.ups > 2 || (relu && o.act > 1)) return fail(LTK_E_INVALID, "bad options");
     if (rep) { memset(rep, 0, sizeof(*rep)); rep->family = o.family; }
+    const int act = c->act = relu ? 1 : o.act;
+    const int CinP = Cin <= 8 ? 8 : (Cin + 15) / 16 * 16;
+    const int x_ld = c->x_ld = o.x_ld ? o.x_ld : CinP, y_ld = c->y_ld = o.y_ld ? o.y_ld : Cout, res_ld = c->res_ld = o.res_ld ? o.res_ld : Cout;
+    if (o.x_coff < 0 || o.y_coff < 0 || o.res_coff < 0 || o.x_coff + CinP > x_ld || o.y_coff + Cout > y_ld || (has_res && o.res_coff + Cout > res_ld))
+        return fail(LTK_E_INVALID, "channel view outside its buffer");
+    std::string err;
+    if (o.family == 0) {
+        ConvPlan plan;
+        ConvRoute route;
+        const int rc = conv_route(&plan, &route, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, 0, o.ups == 2 ? 1 : 0, conv_plan_knobs(), &err);
+        if (rc) return conv_status(rc, err);
+        if (o.ups == 2 && !plan.ups4) return fail(LTK_E_INVALID, "conv3: the four-phase upsample-conv serves 3x3 stride-1 pad-1 layers");
+        static const f16 there = (f16)0.f;        // the planner asks whether a residual / a scratch exists, never what it holds
+        ConvReport cr;
+        memset(&cr, 0, sizeof(cr));
+        ConvIO& io = c->io;
+        io = ConvIO();
+        io.x = nullptr; io.N = N; io.H = H; io.W = W; io.x_ld = x_ld; io.x_coff = o.x_coff;
+        io.y = nullptr; io.y_ld = y_ld; io.y_coff = o.y_coff;
+        io.res = has_res ? &there : nullptr; io.res_ld = res_ld; io.res_coff = o.res_coff;
+        io.relu = act == 1; io.act = act == 1 ? 0 : act;
+        io.ups = o.ups ? 1 : 0;
+        io.force_pxw = o.force_pxw; io.force_nbt = o.force_nbt; io.force_ksplit = o.force_ksplit;
+        io.partial = const_cast<float*>(reinterpret_cast<const float*>(&there)); io.partial_cap = ~(size_t)0;
+        io.report = &cr;
+        const int lrc = conv_launch_dry(plan, io, &err);
+        io.res = nullptr; io.partial = nullptr; io.partial_cap = 0; io.report = nullptr;
+        if (lrc) return conv_status(lrc, err);
+        if (rep) conv_report_copy(cr, rep);
+        return LTK_OK;
+    }
+    // the row kernels: plans over W_eff built from the torch-layout weight as w2l_program.hip builds them
+    if (act > 1 || o.ups || o.force_pxw || o.force_nbt || o.force_ksplit) return fail(LTK_E_INVALID, "the row kernels take no activation but ReLU, no upsample and no tile");
+    if (Cin % 32 || Cout % 16) return fail(LTK_E_INVALID, "the row kernels need Cin % 32 == 0 and Cout % 16 == 0");
+    if (o.family == 1) {
+        if (transposed || kh != 1 || kw != 1 || H != 1 || W != 1 || has_res) return fail(LTK_E_INVALID, "rowgemm: a 1x1 conv on a one-pixel map, no residual");
+        if (rep) { snprintf(rep->kernel, sizeof(rep->kernel), "rowgemm_kernel<%d>", rowgemm_ft(N)); rep->FT = rowgemm_ft(N); rep->UB = rowgemm_ub(rep->FT); rep->grid = Cout / 16; }
+        return LTK_OK;
+    }
+    if (o.family == 2) {
+        if (transposed || kh != 3 || kw != 3 || ph != 1 || pw != 1 || sh < 1 || sw < 1) return fail(LTK_E_INVALID, "rowconv: a 3x3 pad-1 conv");
+        c->Ho = (H + 2 - 3) / sh + 1; c->Wo = (W + 2 - 3) / sw + 1;
+        if (rep) {
+            rep->FT = rowconv_ft((long long)N * c->Ho * c->Wo, Cout); rep->UB = rowconv_ub(rep->FT);
+            snprintf(rep->kernel, sizeof(rep->kernel), "rowconv_kernel<%d,%d>", rep->FT, rep->UB);
+        }
+        return LTK_OK;
+    }
+    if (!transposed || kh != 3 || kw != 3 || sh != 2 || sw != 2 || ph != 1 || pw != 1 || out_pad != 1 || has_res)
+        return fail(LTK_E_INVALID, "rowconvT: ConvTranspose2d(k3, s2, p1, op1), no residual");
+    c->Ho = 2 * H; c->Wo = 2 * W;
+    if (rep) {
+        rep->FT = rowconv_ft((long long)N * H * W, Cout); rep->UB = rowconv_ub(rep->FT);
+        snprintf(rep->kernel, sizeof(rep->kernel), "rowconv_kernel<%d,%d> x 4 phases", rep->FT, rep->UB);
+    }
+    return LTK_OK;
+}
+}  // namespace
+
+int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad,
+                        int has_res, int relu, const ltk_conv_opts* opts, ltk_conv_report* rep) {
+    ConvHookCall c;
+    return conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, has_res != 0, relu, opts, rep, &c);
+}
+
+int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, int kh, int kw, int sh, int sw,
+                      int ph, int pw, int transposed, int out_pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
+                      const ltk_conv_opts* opts, ltk_conv_report* rep) {
+    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ConvHookCall c;
+    int rc = conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, d_res != nullptr, relu, opts, rep, &c);
+    if (rc) return rc;
+    const ltk_conv_opts& o = *opts;
     CHK(enter_device(e->device));
     std::vector<float> ones, zeros;
     if (!scale) { ones.assign(Cout, 1.f); scale = ones.data(); }
     if (!shift) { zeros.assign(Cout, 0.f); shift = zeros.data(); }
-    const int act = relu ? 1 : o.act;
-    const int CinP = Cin <= 8 ? 8 : (Cin + 15) / 16 * 16;
-    const int x_ld = o.x_ld ? o.x_ld : CinP, y_ld = o.y_ld ? o.y_ld : Cout, res_ld = o.res_ld ? o.res_ld : Cout;
-    if (o.x_coff < 0 || o.y_coff < 0 || o.res_coff < 0 || o.x_coff + CinP > x_ld || o.y_coff + Cout > y_ld || (d_res && o.res_coff + Cout > res_ld))
-        return fail(LTK_E_INVALID, "channel view outside its buffer");
     std::string err;
     hipStream_t s = e->compute;
-    auto done = [&](int rc) -> int {       // the launch's error wins; the stream is drained either way
+    auto done = [&](int lrc) -> int {       // the launch's error wins; the stream is drained either way
         const hipError_t he = hipStreamSynchronize(s);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+        if (lrc) return conv_status(lrc, err);
         if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
         return LTK_OK;
     };
     if (o.family == 0) {
         ConvPlanOwner po;
-        int rc = conv_plan_create(&po.p, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, 0, 1.f, o.ups == 2 ? 1 : 0);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
-        if (o.ups == 2 && !po.p.ups4) return fail(LTK_E_INVALID, "conv3: the four-phase upsample-conv serves 3x3 stride-1 pad-1 layers");
+        rc = conv_plan_create(&po.p, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, 0, 1.f, o.ups == 2 ? 1 : 0);
+        if (rc) return conv_status(rc, err);
         ConvReport cr;
         memset(&cr, 0, sizeof(cr));
-        ConvIO io;
+        ConvIO io = c.io;
         io.partial = e->d_partial; io.partial_cap = e->partial_cap;
-        io.x = (const f16*)d_x; io.N = N; io.H = H; io.W = W; io.x_ld = x_ld; io.x_coff = o.x_coff;
-        io.y = (f16*)d_y; io.y_ld = y_ld; io.y_coff = o.y_coff;
-        io.res = (const f16*)d_res; io.res_ld = res_ld; io.res_coff = o.res_coff;
-        io.relu = act == 1; io.act = act == 1 ? 0 : act;
-        io.ups = o.ups ? 1 : 0;
-        io.force_pxw = o.force_pxw; io.force_nbt = o.force_nbt; io.force_ksplit = o.force_ksplit;
+        io.x = (const f16*)d_x; io.y = (f16*)d_y; io.res = (const f16*)d_res;
         io.report = &cr;
         std::lock_guard<std::mutex> g(e->mu);
         rc = done(conv_launch(po.p, io, s, &err));
-        if (rep && !rc) {
-            memcpy(rep->kernel, cr.kernel, sizeof(rep->kernel));
-            rep->G = cr.G; rep->NBT = cr.NBT; rep->PXW = cr.PXW; rep->NC8 = cr.NC8; rep->T = cr.T; rep->S = cr.S;
-            rep->ksplit = cr.ksplit; rep->items = cr.items; rep->grid = cr.grid;
-        }
+        if (rep && !rc) conv_report_copy(cr, rep);      // what ran: the split under the engine's own scratch
         return rc;
     }
-    // the row kernels: plans over W_eff built from the torch-layout weight as w2l_program.hip builds them
-    if (act > 1 || o.ups || o.force_pxw || o.force_nbt || o.force_ksplit) return fail(LTK_E_INVALID, "the row kernels take no activation but ReLU, no upsample and no tile");
-    if (Cin % 32 || Cout % 16) return fail(LTK_E_INVALID, "the row kernels need Cin % 32 == 0 and Cout % 16 == 0");
     RowPlansOwner ro;
     std::vector<float> we;
-    int rc = 0;
     if (o.family == 1) {
-        if (transposed || kh != 1 || kw != 1 || H != 1 || W != 1 || d_res) return fail(LTK_E_INVALID, "rowgemm: a 1x1 conv on a one-pixel map, no residual");
         rc = rowgemm_plan_create(&ro.p[0], weight, Cout, Cin, scale, shift, &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+        if (rc) return conv_status(rc, err);
         std::lock_guard<std::mutex> g(e->mu);
-        rc = done(rowgemm_launch(ro.p[0], (const f16*)d_x, x_ld, o.x_coff, (f16*)d_y, y_ld, o.y_coff, N, act, s, &err));
-        if (rep && !rc) { snprintf(rep->kernel, sizeof(rep->kernel), "rowgemm_kernel<%d>", rowgemm_ft(N)); rep->FT = rowgemm_ft(N); rep->UB = rowgemm_ub(rep->FT); rep->grid = Cout / 16; }
-        return rc;
+        return done(rowgemm_launch(ro.p[0], (const f16*)d_x, c.x_ld, o.x_coff, (f16*)d_y, c.y_ld, o.y_coff, N, c.act, s, &err));
     }
     RowConvIO rio;
-    rio.x = (const f16*)d_x; rio.x_ld = x_ld; rio.x_coff = o.x_coff; rio.H = H; rio.W = W;
-    rio.y = (f16*)d_y; rio.y_ld = y_ld; rio.y_coff = o.y_coff;
-    rio.N = N; rio.relu = act;
+    rio.x = (const f16*)d_x; rio.x_ld = c.x_ld; rio.x_coff = o.x_coff; rio.H = H; rio.W = W;
+    rio.y = (f16*)d_y; rio.y_ld = c.y_ld; rio.y_coff = o.y_coff; rio.Ho = c.Ho; rio.Wo = c.Wo;
+    rio.N = N; rio.relu = c.act;
     if (o.family == 2) {
-        if (transposed || kh != 3 || kw != 3 || ph != 1 || pw != 1 || sh < 1 || sw < 1) return fail(LTK_E_INVALID, "rowconv: a 3x3 pad-1 conv");
         rowconv_weff(weight, Cin, Cout, &we);
         rc = rowgemm_plan_create(&ro.p[0], we.data(), Cout, 9 * Cin, scale, shift, &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
-        rio.Ho = (H + 2 - 3) / sh + 1; rio.Wo = (W + 2 - 3) / sw + 1;
-        rio.res = (const f16*)d_res; rio.res_ld = res_ld; rio.res_coff = o.res_coff;
+        if (rc) return conv_status(rc, err);
+        rio.res = (const f16*)d_res; rio.res_ld = c.res_ld; rio.res_coff = o.res_coff;
         rio.KW = 3; rio.stride = sh; rio.stride_w = sw; rio.pad = 1;
         std::lock_guard<std::mutex> g(e->mu);
-        rc = done(rowconv_launch(ro.p[0], rio, s, &err));
-        if (rep && !rc) {
-            rep->FT = rowconv_ft((long long)N * rio.Ho * rio.Wo, Cout); rep->UB = rowconv_ub(rep->FT);
-            snprintf(rep->kernel, sizeof(rep->kernel), "rowconv_kernel<%d,%d>", rep->FT, rep->UB);
-        }
-        return rc;
+        return done(rowconv_launch(ro.p[0], rio, s, &err));
     }
-    if (!transposed || kh != 3 || kw != 3 || sh != 2 || sw != 2 || ph != 1 || pw != 1 || out_pad != 1 || d_res)
-        return fail(LTK_E_INVALID, "rowconvT: ConvTranspose2d(k3, s2, p1, op1), no residual");
     for (int gph = 0; gph < 4; ++gph) {
         rowconvT_weff(weight, Cin, Cout, gph, &we);
         rc = rowgemm_plan_create(&ro.p[gph], we.data(), Cout, (1 + (gph >> 1)) * (1 + (gph & 1)) * Cin, scale, shift, &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err);
+        if (rc) return conv_status(rc, err);
     }
-    rio.Ho = 2 * H; rio.Wo = 2 * W;
     std::lock_guard<std::mutex> g(e->mu);
-    rc = done(rowconvT_launch(ro.p, rio, s, &err));
-    if (rep && !rc) {
-        rep->FT = rowconv_ft((long long)N * H * W, Cout); rep->UB = rowconv_ub(rep->FT);
-        snprintf(rep->kernel, sizeof(rep->kernel), "rowconv_kernel<%d,%d> x 4 phases", rep->FT, rep->UB);
-    }
-    return rc;
+    return done(rowconvT_launch(ro.p, rio, s, &err));
 }
 
 int ltk_debug_conv3_variants(char* buf, int cap) {
@@ -517,7 +569,7 @@ int ltk_attention_f16(ltk_engine* e, const void* d_q, int q_cbt, int q_cb0, cons
                                                        o_cbt, o_cb0, N, heads, d16, s, impl) : 0;
     const hipError_t se = hipStreamSynchronize(s);       // before the V^T scratch goes
     if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("attention kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, "attention launch failed (head dim " + std::to_string(d16) + ")");
+    if (rc) return conv_status(rc, "attention launch failed (head dim " + std::to_string(d16) + ")");
     return LTK_OK;
 }
 

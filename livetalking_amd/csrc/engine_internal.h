@@ -32,6 +32,8 @@ namespace ltk {
 // source sets it
 extern thread_local std::string g_err;
 inline int fail(int code, const std::string& msg) { g_err = msg; return code; }
+// the plan / launch functions' -1 (refused) and -2 (HIP error), with their text, as the ABI's codes
+inline int conv_status(int rc, const std::string& err) { return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, err); }
 
 // Entry of every call that launches: select the engine's GPU, and drop whatever error an EARLIER runtime call left behind on this
 // host thread (ours after a reported failure, or another library's) - hipGetLastError() after a launch must speak about that launch

@@ -124,7 +124,7 @@ int ltk::mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat
     if (feat_ptrs) launch_tokens_gather_to_cb16(*feat_ptrs, nf, 50, 384, e->d_pe, ctx, cbt, s);
     else launch_tokens_to_cb16(d_feat, nf, 50, 384, e->d_pe, ctx, cbt, 0, s);
     const int rc = run_program(e, e->mt, nf);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, std::string("musetalk: ") + mt_graph_error(e->mt));
+    if (rc) return conv_status(rc, std::string("musetalk: ") + mt_graph_error(e->mt));
     if (outs || d_image_f32) {
         OutList64 none;
         for (int i = 0; i < 64; ++i) none.p[i] = nullptr;
@@ -298,7 +298,7 @@ int hubert_forward(ltk_engine* e, long long off, int len, MtGraph** prog) {
     if (!g) return rc;
     launch_hubert_normalise(e->d_hpcm + off, len, e->d_hstats, mt_hubert_pcm_in(g), e->compute);
     rc = run_program(e, g, 1);
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, std::string("hubert: ") + mt_graph_error(g));
+    if (rc) return conv_status(rc, std::string("hubert: ") + mt_graph_error(g));
     e->hubert_last = g;
     *prog = g;
     return LTK_OK;

@@ -86,7 +86,7 @@ struct Builder {
         op.type = UL_CONV; op.name = wname;
         std::string err;
         rc = conv_plan_create(&op.plan, w, in.C, cout, k, k, stride, stride, pad, pad, false, 0, sc.data(), sf.data(), &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, wname + ": " + err);
+        if (rc) return conv_status(rc, wname + ": " + err);
         op.C = op.Creal = cout; op.stride = stride; op.relu = relu;
         op.in_buf = in.buf; op.in_ld = in.ld; op.in_coff = in.coff; op.H = in.H; op.W = in.W;
         op.plan.out_dims(in.H, in.W, &op.Ho, &op.Wo);
@@ -261,7 +261,7 @@ int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, co
             io.relu = op.relu;
             io.partial = e->d_partial; io.partial_cap = e->partial_cap;
             const int rc = conv_launch(op.plan, io, s, &err);
-            if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, op.name + ": " + err);
+            if (rc) return conv_status(rc, op.name + ": " + err);
         }
         }
         CHK(hipGetLastError());

@@ -199,7 +199,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
         rc = conv_plan_create(&L->plan, w, d.cin, d.cout, d.k, d.k, d.sh, d.sw, d.pad, d.pad, d.transposed, d.out_pad,
                               sc.data(), sf.data(), &err);
     }
-    if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
+    if (rc) return conv_status(rc, p + ": " + err);
     // one pixel per frame on both sides: a plain GEMM with as many rows as frames (rowgemm.hip, used for launches of <= 32 frames).
     // Not built (45 MB of duplicated weights) when the process starts with the paths switched off.
     const bool want_rowgemm = knob(K_ROWGEMM) && knob(K_SPLITK), want_rowconv = knob(K_ROWCONV) > 0 && knob(K_SPLITK);
@@ -234,7 +234,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             // conv3 + split-K finish serves the layer
         } else if (J > 0) {
             rc = rowgemm_plan_create(&L->rg, we.data(), J, K, se.data(), fe.data(), &err);
-            if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
+            if (rc) return conv_status(rc, p + ": " + err);
             L->rg_y_ld = (d.transposed ? J : 0);
         } else if (want_rowconv && flat_ld == 0 && !d.transposed && d.k == 3 && d.pad == 1 && (d.cout % 256 == 0 || (map_w < 0 && d.cout == 128)) &&
                    ((map_w > 0 && d.sh == d.sw && (d.sh == 1 || d.sh == 2) && map_w % d.sh == 0 && map_w / d.sh <= 8 && (d.cin == 256 || d.cin == 512)) ||
@@ -246,7 +246,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
             J = d.cout; K = 9 * d.cin;
             rowconv_weff(w, d.cin, d.cout, &we);
             rc = rowgemm_plan_create(&L->rg, we.data(), J, K, sc.data(), sf.data(), &err);
-            if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
+            if (rc) return conv_status(rc, p + ": " + err);
             L->rowconv = true;
             L->rc_stride = d.sh;
             L->rc_stride_w = d.sw;
@@ -257,7 +257,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
                 J = d.cout; K = (1 + (gph >> 1)) * (1 + (gph & 1)) * d.cin;
                 rowconvT_weff(w, d.cin, d.cout, gph, &we);
                 rc = rowgemm_plan_create(&L->rgT[gph], we.data(), J, K, sc.data(), sf.data(), &err);
-                if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
+                if (rc) return conv_status(rc, p + ": " + err);
             }
         }
     }
@@ -277,7 +277,7 @@ int build_layer_impl(ltk_engine* e, const LayerDef& d, const ltk_named_tensor* s
     if (!d.transposed && d.k == 3 && d.sh == 2 && d.sw == 2 && d.pad == 1 && !d.residual && (d.cin == 16 || d.cin == 32) && d.cout % 32 == 0 &&
         knob(K_CONV_S2D) && !L->s2d) {
         rc = convs2d_plan_create(&L->s2d, w, d.cin, d.cout, sc.data(), sf.data(), &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, p + ": " + err);
+        if (rc) return conv_status(rc, p + ": " + err);
     }
     L->name = p;
     L->cin_real = d.cin;
@@ -562,7 +562,7 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
                                 on_aux ? e->aux : s, &err);
         else
             rc = conv_launch(L.plan, io, on_aux ? e->aux : s, &err);
-        if (rc) return fail(rc == -2 ? LTK_E_HIP : LTK_E_INVALID, L.name + ": " + err);
+        if (rc) return conv_status(rc, L.name + ": " + err);
         // debug (knob SAT_CHECK): count what this layer's epilogue clamped to the fp16 limit (a fused head writes bytes: run it unfused)
         if (knob(K_SAT_CHECK) && !(io.head_w && io.head_outs))
             launch_sat_scan(io.y, n, L.out_ld / 16, L.out_coff / 16, (L.plan.Cout + 15) / 16, (long long)L.Ho * L.Wo, 0, e->d_sat, on_aux ? e->aux : s);

@@ -23,6 +23,12 @@ def _as_f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _conv_report_dict(rep: "_lib.ConvReport") -> dict:
+    out = {name: getattr(rep, name) for name, _ in _lib.ConvReport._fields_}
+    out["kernel"] = rep.kernel.decode()
+    return out
+
+
 class Engine:
     """avatars/wav2lip_avatar.py `model` handle + device-resident avatar banks."""
 
@@ -668,9 +674,20 @@ class Engine:
             self._h, C.c_void_p(d_x_ptr), N, H, W, Cin, w.ctypes.data, Cout, kh, kw, sh, sw, ph, pw, 1 if transposed else 0, out_pad,
             sc.ctypes.data if sc is not None else None, sf.ctypes.data if sf is not None else None,
             C.c_void_p(d_res_ptr) if d_res_ptr else None, 0, C.c_void_p(d_y_ptr), C.byref(o), C.byref(rep)))
-        out = {name: getattr(rep, name) for name, _ in _lib.ConvReport._fields_}
-        out["kernel"] = rep.kernel.decode()
-        return out
+        return _conv_report_dict(rep)
+
+    @staticmethod
+    def conv_plan(N, H, W, Cin, Cout, k, stride, pad, transposed=False, out_pad=0, has_res=False, **opts) -> dict:
+        """What conv2d_f16_ex would report for this call, decided on the host alone (ltk_debug_conv_plan; no GPU needed): the same
+        refusals (LtkError) up to the point where a launch would be enqueued, the same report dict."""
+        kh, kw = (k, k) if isinstance(k, int) else k
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        ph, pw = (pad, pad) if isinstance(pad, int) else pad
+        o = _lib.ConvOpts(**{name: int(v) for name, v in opts.items()})
+        rep = _lib.ConvReport()
+        _lib.check(_lib.load().ltk_debug_conv_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, 1 if transposed else 0, out_pad,
+                                                   1 if has_res else 0, 0, C.byref(o), C.byref(rep)))
+        return _conv_report_dict(rep)
 
     @staticmethod
     def conv3_variants() -> list:

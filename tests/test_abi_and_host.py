@@ -445,7 +445,7 @@ def test_plugin_module_contract_against_reference_app():
 
 
 def test_host_e4m3_conversion_matches_torch():
-    """The weight packer's fp32 -> OCP e4m3fn conversion (csrc/conv_mfma.hip f32_to_e4m3) against torch.float8_e4m3fn:
+    """The weight packer's fp32 -> OCP e4m3fn conversion (csrc/conv_plan.hip f32_to_e4m3) against torch.float8_e4m3fn:
     round to nearest even, subnormals, saturation at +-448."""
     import ctypes as C
 
