@@ -193,6 +193,13 @@ int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* 
  * d_pred: device uint8 [160][160][3].  out: uint8 [H][W][3], device or host as ltk_paste_back. */
 int ltk_ultralight_paste_back(ltk_engine* e, int avatar_id, int idx, const void* d_pred, void* out, int out_is_device, void* stream);
 
+/* The twin of ltk_paste_back_batch for avatars/ultralight_avatar.py:173-184: the composites of the `n` frames of one
+ * LightReal.inference_batch result at once (the process thread of avatars/base_avatar.py:383-467 asks for them one by one, in
+ * order).  d_pred = n contiguous device uint8 [160][160][3] predictions, idx[i] = bank frame of prediction i, out = HOST uint8
+ * [n][H][W][3] (pinned memory moves at the PCIe rate).  One launch per 16 frames, ONE device-to-host copy, one synchronisation.
+ * n <= 0, a NULL pointer or an idx[i] outside the bank: LTK_E_INVALID; an unknown avatar id: LTK_E_STATE. */
+int ltk_ultralight_paste_back_batch(ltk_engine* e, int avatar_id, const int32_t* idx, const void* d_pred, int n, void* out, void* stream);
+
 /* ---- frame egress: the steps between paste_back_frame and the encoder ------------
  * Reference: avatars/base_avatar.py:384-453 process_frames (silent path :407-428, transition blend :419-426 and
  * :436-445, watermark :449), server/webrtc.py:190-193 (VideoFrame.from_ndarray(bgr24), converted to yuv420p by the
@@ -213,10 +220,12 @@ int ltk_egress_watermark(ltk_engine* e, ltk_egress* s, const uint8_t* mask, int 
 #define LTK_SRC_WAV2LIP 0   /* composite = ltk_paste_back(avatar, idx, d_pred); d_pred NULL = the cached full frame (silent) */
 #define LTK_SRC_MUSETALK 1  /* composite = ltk_paste_blend(avatar, idx, d_pred); d_pred NULL = the cached full frame */
 #define LTK_SRC_HOST 2      /* frame = h_frame, host uint8 [H][W][3] (custom action video, base_avatar.py:411-414) */
+#define LTK_SRC_ULTRALIGHT 3 /* composite = ltk_ultralight_paste_back(avatar, idx, d_pred), d_pred device uint8 [160][160][3];
+                              * d_pred NULL = the cached full frame */
 typedef struct ltk_egress_req {
     int source;             /* LTK_SRC_* */
     int avatar, idx;        /* bank frame (ignored for LTK_SRC_HOST) */
-    const void* d_pred;     /* device uint8 [256][256][3] or NULL */
+    const void* d_pred;     /* device uint8 [256][256][3] ([160][160][3] for LTK_SRC_ULTRALIGHT) or NULL */
     const uint8_t* h_frame; /* LTK_SRC_HOST only */
     int speaking;           /* which cache this frame refreshes: 1 = _last_speaking_frame, 0 = _last_silent_frame */
     double alpha;           /* transition weight of THIS frame: out = addWeighted(other-state cache, 1-alpha, frame, alpha);
@@ -230,12 +239,13 @@ typedef struct ltk_egress_req {
 int ltk_egress_frame(ltk_engine* e, ltk_egress* s, const ltk_egress_req* req, uint8_t* h_out, void* stream);
 
 /* The speaking frames of ONE inference_batch result at once, for sessions without the transition effect (the reference's
- * default, base_avatar.py:384 enable_transition = False): n composites (ltk_paste_back / ltk_paste_blend of prediction i onto
- * bank frame idx[i]), watermark and format conversion on the device, ONE device-to-host copy into `h_out`
- * ([n][H][W][3] for LTK_FMT_BGR24, [n][H*3/2][W] for LTK_FMT_I420; pinned memory moves at the PCIe rate) and one
+ * default, base_avatar.py:384 enable_transition = False): n composites (ltk_paste_back / ltk_paste_blend /
+ * ltk_ultralight_paste_back of prediction i onto bank frame idx[i]), watermark and format conversion on the device, ONE
+ * device-to-host copy into `h_out` ([n][H][W][3] for LTK_FMT_BGR24, [n][H*3/2][W] for LTK_FMT_I420; pinned memory moves at the PCIe rate) and one
  * synchronisation.  With I420 a 25-fps 720p session costs 35 MB/s of PCIe instead of 69: the link, not the GPU, bounds
- * how many sessions a GPU can serve (bench.py `delivered`).  source: LTK_SRC_WAV2LIP or LTK_SRC_MUSETALK; d_pred: n
- * contiguous device uint8 [256][256][3] predictions.  The session's transition caches are neither read nor written. */
+ * how many sessions a GPU can serve (bench.py `delivered`).  source: LTK_SRC_WAV2LIP, LTK_SRC_MUSETALK or
+ * LTK_SRC_ULTRALIGHT; d_pred: n contiguous device uint8 predictions, [256][256][3] each ([160][160][3] for
+ * LTK_SRC_ULTRALIGHT).  The session's transition caches are neither read nor written. */
 int ltk_egress_batch(ltk_engine* e, ltk_egress* s, int source, int avatar, const int32_t* idx, const void* d_pred, int n, int format,
                      int chroma, uint8_t* h_out, void* stream);
 

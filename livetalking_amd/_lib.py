@@ -85,6 +85,7 @@ SYMBOLS = {
                                                  C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ltk_ultralight_infer": (C.c_int, [C.c_void_p, C.POINTER(UlReq), C.c_int, C.c_void_p]),
     "ltk_ultralight_paste_back": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ltk_ultralight_paste_back_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_ultralight_forward_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_ultralight_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "ltk_dwconv3x3_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

@@ -4,13 +4,15 @@ Module contract the reference's app.py relies on (the plugin is picked by name):
   load_model(opt) -> (audio_processor, model)            (ultralight_avatar.py:58-61)
   load_avatar(avatar_id) -> avatar tuple                 (ultralight_avatar.py:63-81)
   warm_up(batch_size, avatar, modelres)                  (ultralight_avatar.py:84-90)
-  @register("avatar", "ultralight") class LightReal(BaseAvatar) with
+  @register("avatar", "ultralight") class LightReal(DeviceEgressMixin, BaseAvatar) with
   inference_batch(index, audiofeat_batch) and paste_back_frame(pred_frame, idx)   (ultralight_avatar.py:125-184)
 
 What changes underneath: the U-Net is per avatar (`ultralight.pth`), so `load_avatar` returns an `UltralightNet` handle in the
 model's place; it registers state_dict + bank with the engine (libltk_hip.so) on first use.  `inference_batch` returns device
 handles (uint8 160x160x3, already truncated the way paste_back_frame's astype(uint8) does) instead of float numpy frames;
-`paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array.  HuBERT-large runs on
+`paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array; the B items of one
+`inference_batch` result are composited and copied to the host together (LTK_PASTE_BATCH=0: one by one).  With
+`opt.egress` = "bgr24" | "i420" the frames leave through the device-side process_frames of egress.py.  HuBERT-large runs on
 torch by default (audio_features/hubert.py Audio2Feature); with LTK_HUBERT_ENGINE=1 or opt.hubert_engine it runs on the engine
 (EngineAudio2Feature) and its chunks reach inference_batch as device tensors.
 """
@@ -23,10 +25,13 @@ import threading
 
 import numpy as np
 
+from ..egress import SRC_ULTRALIGHT, DeviceEgressMixin, FrameGroup
 from ..engine import Engine
 from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror_index: part of the reference module's namespace)
 from .audio_features.hubert import HubertASR
 from .audio_features import hubert as _hubert
+
+_PASTE_BATCH = os.environ.get("LTK_PASTE_BATCH", "1") != "0"     # 0: one composite + one pageable copy per paste_back_frame call
 
 _engines = {}
 _engines_lock = threading.Lock()
@@ -124,7 +129,9 @@ def warm_up(batch_size, avatar, modelres):
 
 
 @register("avatar", "ultralight")
-class LightReal(BaseAvatar):
+class LightReal(DeviceEgressMixin, BaseAvatar):
+    _egress_source = SRC_ULTRALIGHT   # opt.egress = "bgr24" | "i420": device-side process_frames (egress.py)
+
     def __init__(self, opt, model, avatar):
         super().__init__(opt)
         audio_processor, _ = model
@@ -154,13 +161,28 @@ class LightReal(BaseAvatar):
             raise ValueError(f"expected {B} feature chunks, got {feat.shape[0]}")
         pred = torch.empty((B, 160, 160, 3), dtype=torch.uint8, device=feat.device)
         self.engine.ultralight_infer([(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())])
-        return list(pred.unbind(0))
+        items = list(pred.unbind(0))
+        if _PASTE_BATCH and hasattr(self.engine, "ultralight_paste_back_batch"):
+            # the process thread will ask for these B composites one by one, in order (base_avatar.py:429-433): remember
+            # the batch so that the FIRST request composites all of them and moves them to the host in one copy
+            FrameGroup.attach(items, pred, span=(len(self.face_list_cycle), int(index), B))
+        return items
 
     def paste_back_frame(self, pred_frame, idx: int):
         import torch
         if not isinstance(pred_frame, torch.Tensor):   # a float frame from a foreign inference_batch
             pred_frame = torch.from_numpy(np.ascontiguousarray(pred_frame).astype(np.uint8)).to(self.engine.torch_device)
         h, w = self._frame_hw
+        grp = getattr(pred_frame, "_ltk_group", None)
+        if grp is not None and grp.idx[pred_frame._ltk_i] == int(idx):
+            with grp.lock:
+                if grp.host is None:
+                    # one pinned host block per batch, as LipReal.paste_back_frame: n composites on the GPU, ONE device-to-host
+                    # copy; the returned frames are views of the block, which lives as long as any of them does
+                    host = torch.empty((len(grp.idx), h, w, 3), dtype=torch.uint8, pin_memory=True)
+                    self.engine.ultralight_paste_back_batch(self._aid, grp.idx, grp.pred.data_ptr(), host.data_ptr())
+                    grp.host = host.numpy()
+            return grp.host[pred_frame._ltk_i]
         out = np.empty((h, w, 3), dtype=np.uint8)
         self.engine.ultralight_paste_back(self._aid, int(idx), pred_frame.contiguous().data_ptr(), out)
         return out

@@ -68,6 +68,7 @@ int ltk_egress_frame(ltk_engine* e, ltk_egress* s, const ltk_egress_req* q, uint
     const uint8_t* src = nullptr;
     std::shared_ptr<Avatar> hold_w;           // keep the bank alive until the stream has been synchronised below
     std::shared_ptr<MtAvatar> hold_m;
+    std::shared_ptr<UlAvatar> hold_u;
     if (q->source == LTK_SRC_HOST) {
         if (!q->h_frame) return fail(LTK_E_INVALID, "LTK_SRC_HOST without h_frame");
         CHK(hipMemcpyAsync(s->d_frame, q->h_frame, bytes, hipMemcpyHostToDevice, sl.s));
@@ -101,6 +102,20 @@ int ltk_egress_frame(ltk_engine* e, ltk_egress* s, const ltk_egress_req* q, uint
         } else {
             src = full;
         }
+    } else if (q->source == LTK_SRC_ULTRALIGHT) {
+        if (!(hold_u = find_ul_avatar(e, q->avatar))) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+        const UlAvatar& a = *hold_u;
+        if (q->idx < 0 || q->idx >= a.n) return fail(LTK_E_INVALID, "frame index outside the bank");
+        if (a.H != H || a.W != W) return fail(LTK_E_INVALID, "avatar frame size differs from the egress session");
+        const uint8_t* full = a.d_full + (size_t)q->idx * bytes;
+        if (q->d_pred) {
+            const int32_t* c = a.boxes.data() + 4 * (size_t)q->idx;      // (x1, y1, x2, y2)
+            launch_ul_paste(full, H, W, a.d_face + (size_t)q->idx * kUlFace * kUlFace * 3, (const uint8_t*)q->d_pred, c[0], c[1], c[2], c[3],
+                            s->d_frame, sl.s);
+            src = s->d_frame;
+        } else {
+            src = full;
+        }
     } else {
         return fail(LTK_E_INVALID, "unknown frame source");
     }
@@ -126,17 +141,24 @@ int ltk_egress_batch(ltk_engine* e, ltk_egress* s, int source, int avatar, const
     const size_t bytes = (size_t)H * W * 3;
     if (format != LTK_FMT_BGR24 && format != LTK_FMT_I420) return fail(LTK_E_INVALID, "unknown output format");
     if (format == LTK_FMT_I420 && ((H | W) & 1)) return fail(LTK_E_INVALID, "I420 needs even frame dimensions");
-    if (source != LTK_SRC_WAV2LIP && source != LTK_SRC_MUSETALK) return fail(LTK_E_INVALID, "batch egress: Wav2Lip or MuseTalk frames only");
+    if (source != LTK_SRC_WAV2LIP && source != LTK_SRC_MUSETALK && source != LTK_SRC_ULTRALIGHT)
+        return fail(LTK_E_INVALID, "batch egress: Wav2Lip, MuseTalk or Ultralight frames only");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> gs(s->mu);
     std::shared_ptr<Avatar> hold_w;           // keep the bank alive until the stream has been synchronised below
     std::shared_ptr<MtAvatar> hold_m;
+    std::shared_ptr<UlAvatar> hold_u;
+    int bank_n, bank_h, bank_w;
     if (source == LTK_SRC_WAV2LIP) {
         if (!(hold_w = find_avatar(e, avatar))) return fail(LTK_E_STATE, "unknown avatar id");
-    } else {
+        bank_n = hold_w->n; bank_h = hold_w->H; bank_w = hold_w->W;
+    } else if (source == LTK_SRC_MUSETALK) {
         if (!(hold_m = find_mt_avatar(e, avatar))) return fail(LTK_E_STATE, "unknown MuseTalk avatar id");
+        bank_n = hold_m->n; bank_h = hold_m->H; bank_w = hold_m->W;
+    } else {
+        if (!(hold_u = find_ul_avatar(e, avatar))) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+        bank_n = hold_u->n; bank_h = hold_u->H; bank_w = hold_u->W;
     }
-    const int bank_n = hold_w ? hold_w->n : hold_m->n, bank_h = hold_w ? hold_w->H : hold_m->H, bank_w = hold_w ? hold_w->W : hold_m->W;
     if (bank_h != H || bank_w != W) return fail(LTK_E_INVALID, "avatar frame size differs from the egress session");
     for (int i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= bank_n) return fail(LTK_E_INVALID, "frame index outside the bank");
@@ -157,6 +179,13 @@ int ltk_egress_batch(ltk_engine* e, ltk_egress* s, int source, int avatar, const
                 pb.y1[i] = c[0]; pb.y2[i] = c[1]; pb.x1[i] = c[2]; pb.x2[i] = c[3];
             }
             launch_paste_batch(pb, m, H, W, (const uint8_t*)d_pred + (size_t)i0 * 256 * 256 * 3, comp + bytes * i0, bytes, sl.s);
+        }
+    } else if (hold_u) {
+        for (int i0 = 0; i0 < n; i0 += kPasteBatch) {
+            const int m = std::min(kPasteBatch, n - i0);
+            UlPasteBatch pb;
+            ul_fill_paste_batch(*hold_u, idx + i0, m, &pb);
+            launch_ul_paste_batch(pb, m, H, W, (const uint8_t*)d_pred + (size_t)i0 * kUlRes * kUlRes * 3, comp + bytes * i0, bytes, sl.s);
         }
     } else {
         const MtAvatar& a = *hold_m;

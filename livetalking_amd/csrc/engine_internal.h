@@ -480,6 +480,16 @@ inline std::shared_ptr<UlAvatar> find_ul_avatar(ltk_engine* e, int id) {
     auto it = e->ul_avatars.find(id);
     return it == e->ul_avatars.end() ? nullptr : it->second;
 }
+// the launch_ul_paste_batch argument of bank frames idx[0..m) (m <= kPasteBatch, every index checked by the caller)
+inline void ul_fill_paste_batch(const UlAvatar& a, const int32_t* idx, int m, UlPasteBatch* pb) {
+    const size_t bytes = (size_t)a.H * a.W * 3;
+    for (int i = 0; i < m; ++i) {
+        const int32_t* c = a.boxes.data() + 4 * (size_t)idx[i];
+        pb->full[i] = a.d_full + (size_t)idx[i] * bytes;
+        pb->face[i] = a.d_face + (size_t)idx[i] * kUlFace * kUlFace * 3;
+        pb->x1[i] = c[0]; pb->y1[i] = c[1]; pb->x2[i] = c[2]; pb->y2[i] = c[3];
+    }
+}
 
 // ---------------------------------------------------------------- what crosses the engine's sources
 void build_mel_basis(std::vector<float>* basis, std::vector<int32_t>* lohi, int n_bins = 401, double f_lo = 55.0, double f_hi = 7600.0);   // engine.hip

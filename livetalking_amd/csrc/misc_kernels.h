@@ -92,6 +92,15 @@ struct PasteBatch {
 };
 void launch_paste_batch(const PasteBatch& b, int n, int H, int W, const uint8_t* pred0, uint8_t* out0, size_t out_stride, hipStream_t s);
 
+// launch_ul_paste (dw_kernels.h; ultralight_avatar.py:173-184) for up to kPasteBatch frames in one launch: frame f pastes the 168x168
+// composite of face[f] and prediction pred0 + f * 160*160*3 onto full[f] at box (x1,y1,x2,y2)[f] and writes out0 + f * out_stride
+struct UlPasteBatch {
+    const uint8_t* full[kPasteBatch];
+    const uint8_t* face[kPasteBatch];
+    int x1[kPasteBatch], y1[kPasteBatch], x2[kPasteBatch], y2[kPasteBatch];
+};
+void launch_ul_paste_batch(const UlPasteBatch& b, int n, int H, int W, const uint8_t* pred0, uint8_t* out0, size_t out_stride, hipStream_t s);
+
 // musetalk_avatar.py:154-164 paste_back_frame (resize + paste into the crop + cv2.blendLinear under the mask).
 void launch_paste_blend(const uint8_t* full, int H, int W, const uint8_t* pred256, int x1, int y1, int x2, int y2, int xs, int ys,
                         int xe, int ye, const uint8_t* mask, uint8_t* out, hipStream_t s);

@@ -475,9 +475,9 @@ __device__ __forceinline__ int ul_src(const uint8_t* __restrict__ face, const ui
     return face[(sy * kUlFace + sx) * 3 + c];
 }
 
-__global__ __launch_bounds__(256) void ul_paste_kernel(const uint8_t* __restrict__ full, int H, int W, const uint8_t* __restrict__ face,
-                                                        const uint8_t* __restrict__ pred, int x1, int y1, int x2, int y2,
-                                                        uint8_t* __restrict__ out) {
+__device__ __forceinline__ void ul_paste_body(const uint8_t* __restrict__ full, int H, int W, const uint8_t* __restrict__ face,
+                                              const uint8_t* __restrict__ pred, int x1, int y1, int x2, int y2,
+                                              uint8_t* __restrict__ out) {
     const size_t total = (size_t)H * W * 3;
     const size_t b0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (b0 >= total) return;
@@ -511,11 +511,31 @@ __global__ __launch_bounds__(256) void ul_paste_kernel(const uint8_t* __restrict
         }
         word |= v << (8 * k);
     }
+    // (frame f of a batched launch starts at out0 + f * H*W*3: dword-aligned only when H*W*3 is a multiple of 4)
     if (nb == 4 && (reinterpret_cast<uintptr_t>(out + b0) & 3) == 0) {
         *reinterpret_cast<unsigned*>(out + b0) = word;
     } else {
         for (int k = 0; k < nb; ++k) out[b0 + k] = (uint8_t)(word >> (8 * k));
     }
+}
+
+__global__ __launch_bounds__(256) void ul_paste_kernel(const uint8_t* __restrict__ full, int H, int W, const uint8_t* __restrict__ face,
+                                                        const uint8_t* __restrict__ pred, int x1, int y1, int x2, int y2,
+                                                        uint8_t* __restrict__ out) {
+    ul_paste_body(full, H, W, face, pred, x1, y1, x2, y2, out);
+}
+
+// the composites of up to kPasteBatch frames of ONE inference_batch result in one launch: blockIdx.y = frame
+__global__ __launch_bounds__(256) void ul_paste_batch_kernel(const UlPasteBatch b, int H, int W, const uint8_t* __restrict__ pred0,
+                                                              uint8_t* __restrict__ out0, size_t out_stride) {
+    const int f = blockIdx.y;
+    ul_paste_body(b.full[f], H, W, b.face[f], pred0 + (size_t)f * (kUlRes * kUlRes * 3), b.x1[f], b.y1[f], b.x2[f], b.y2[f],
+                  out0 + (size_t)f * out_stride);
+}
+
+void launch_ul_paste_batch(const UlPasteBatch& b, int n, int H, int W, const uint8_t* pred0, uint8_t* out0, size_t out_stride, hipStream_t s) {
+    const size_t words = ((size_t)H * W * 3 + 3) / 4;
+    hipLaunchKernelGGL(ul_paste_batch_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)n), dim3(256), 0, s, b, H, W, pred0, out0, out_stride);
 }
 
 void launch_ul_paste(const uint8_t* full, int H, int W, const uint8_t* face168, const uint8_t* pred160, int x1, int y1, int x2, int y2,

@@ -473,4 +473,30 @@ int ltk_ultralight_paste_back(ltk_engine* e, int avatar_id, int idx, const void*
     return LTK_OK;
 }
 
+int ltk_ultralight_paste_back_batch(ltk_engine* e, int avatar_id, const int32_t* idx, const void* d_pred, int n, void* out, void* stream) {
+    if (!e || !idx || !d_pred || !out || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);      // held until the stream has been synchronised below
+    if (!ap) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
+    const UlAvatar& a = *ap;
+    for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= a.n) return fail(LTK_E_INVALID, "frame index outside the bank");
+    CHK(enter_device(e->device));
+    const size_t bytes = (size_t)a.H * a.W * 3;
+    StreamLease sl(e, stream);
+    ScratchLease sc(e, bytes * n);
+    if (!sc.s.d) return fail(LTK_E_NOMEM, "scratch allocation failed");
+    for (int i0 = 0; i0 < n; i0 += kPasteBatch) {          // one launch per 16 frames
+        const int m = std::min(kPasteBatch, n - i0);
+        UlPasteBatch pb;
+        ul_fill_paste_batch(a, idx + i0, m, &pb);
+        launch_ul_paste_batch(pb, m, a.H, a.W, (const uint8_t*)d_pred + (size_t)i0 * kUlRes * kUlRes * 3, (uint8_t*)sc.s.d + (size_t)i0 * bytes, bytes, sl.s);
+    }
+    // an error past this point must not hand the scratch back to the pool while earlier launches may still be writing it
+    hipError_t pe = hipGetLastError();
+    if (pe == hipSuccess) pe = hipMemcpyAsync(out, sc.s.d, bytes * n, hipMemcpyDeviceToHost, sl.s);
+    const hipError_t se = hipStreamSynchronize(sl.s);
+    if (pe != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight_paste_back_batch: ") + hipGetErrorString(pe != hipSuccess ? pe : se));
+    return LTK_OK;
+}
+
 }  // extern "C"

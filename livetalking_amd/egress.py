@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 FMT_BGR24, FMT_I420 = 0, 1
-SRC_WAV2LIP, SRC_MUSETALK, SRC_HOST = 0, 1, 2
+SRC_WAV2LIP, SRC_MUSETALK, SRC_HOST, SRC_ULTRALIGHT = 0, 1, 2, 3      # include/ltk.h LTK_SRC_*
 
 WATERMARK_TEXT = "LiveTalking"          # base_avatar.py:449
 WATERMARK_ORG = (10, 20)
@@ -196,7 +196,7 @@ class DeviceEgress:
 
 
 class DeviceEgressMixin:
-    """`process_frames` for LipReal / MuseReal when `opt.egress` is set: the control flow of
+    """`process_frames` for LipReal / MuseReal / LightReal when `opt.egress` is set: the control flow of
     avatars/base_avatar.py:384-460 (queue protocol, speaking flag, custom-action index, audio push, recording), with the
     per-frame pixel work delegated to DeviceEgress.  `_egress_source` is set by the plugin class."""
 

@@ -242,6 +242,13 @@ class Engine:
         _lib.check(self._lib.ltk_ultralight_paste_back(self._h, int(avatar_id), int(idx), C.c_void_p(d_pred_ptr), out.ctypes.data, 0,
                                                        C.c_void_p(stream)))
 
+    def ultralight_paste_back_batch(self, avatar_id: int, idx: Sequence[int], d_pred_ptr: int, out_ptr: int, stream: int = 0):
+        """n = len(idx) composites (n contiguous device uint8 [160][160][3] predictions) into host memory at out_ptr [n][H][W][3]
+        (pinned for the PCIe rate): one device-to-host copy, one synchronisation (include/ltk.h: ltk_ultralight_paste_back_batch)."""
+        arr = np.ascontiguousarray(np.asarray(idx, dtype=np.int32))
+        _lib.check(self._lib.ltk_ultralight_paste_back_batch(self._h, int(avatar_id), arr.ctypes.data, C.c_void_p(d_pred_ptr),
+                                                             int(arr.size), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
     def ultralight_forward_host(self, avatar_id: int, img6: np.ndarray, feat: np.ndarray) -> np.ndarray:
         """Model.forward on explicit inputs: img6 (B,6,160,160) in [0,1], feat (B,16,32,32) or (B,16,1024) -> sigmoid (B,3,160,160)."""
         img6 = np.ascontiguousarray(img6, dtype=np.float32)
