@@ -553,6 +553,25 @@ int ltk_conv2d_fp8(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
                    const float* scale, const float* shift, float act_scale, const void* d_res, int act, void* d_y, int iters,
                    float* ms_avg);
 
+/* The same fp8 conv with the caller saying WHAT runs and the hook reporting what ran (kernel unit tests; one body with
+ * ltk_conv2d_f16_ex).  quant: 0 = the program's rule (MX from 512 input channels on, Cin % 64 == 0), 1 = the e4m3 MFMA, 2 = the MX-scaled
+ * MFMA (Cin % 64 == 0).  `opts` as for ltk_conv2d_f16_ex with family 0 and ups 0; x_ld / x_coff count fp8 channels, in multiples of
+ * 32 (one 32-byte block per pixel), y_* and res_* fp16 channels in multiples of 16.  `rep` (may be NULL): kernel = the instantiation as
+ * ltk_debug_conv3_fp8_variants spells it, conv3_kernel<1,NBT,PXW,NC8,9,1,Q> with Q = 1 (e4m3) or 2 (MX); NC8 counts 16-byte planes
+ * of 16 fp8 channels; the other fields as above. */
+int ltk_conv2d_fp8_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout,
+                      const float* scale, const float* shift, float act_scale, int quant, const void* d_res, void* d_y,
+                      const ltk_conv_opts* opts, ltk_conv_report* rep);
+
+/* What ltk_conv2d_fp8_ex decides before it allocates or enqueues anything, on the host alone (no engine, no GPU), as
+ * ltk_debug_conv_plan does for the fp16 hook.  The layer geometry is an argument here so that what the fp8 route refuses (anything
+ * but 3x3 stride 1 pad 1, Cin % 32, MX with Cin % 64) can be seen refused. */
+int ltk_debug_conv_fp8_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                            int transposed, int out_pad, int quant, int has_res, const ltk_conv_opts* opts, ltk_conv_report* rep);
+
+/* Names of every fp8 conv3 instantiation the launch path can pick (e4m3 and MX), one per line, as ltk_debug_conv3_variants. */
+int ltk_debug_conv3_fp8_variants(char* buf, int cap);
+
 #ifdef __cplusplus
 }
 #endif

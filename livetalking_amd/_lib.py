@@ -157,6 +157,10 @@ SYMBOLS = {
     "ltk_f32_to_e4m3": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "ltk_conv2d_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    "ltk_conv2d_fp8_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
+    "ltk_debug_conv_fp8_plan": (C.c_int, [C.c_int] * 15 + [C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
+    "ltk_debug_conv3_fp8_variants": (C.c_int, [C.c_char_p, C.c_int]),
 }
 
 _lib = None

@@ -1345,18 +1345,41 @@ std::string conv3_variant_names() {
 
 static k3_kernel_t k3_pick(int G, int NBT, int PXW, int NC8, int T) { return k3_pick_f16(G, NBT, PXW, NC8, T, 1); }
 
+// THE tables of fp8 instantiations (3x3 stride 1, conv3_kernel<1, NBT, PXW, NC8, 9, 1, Q>): e4m3 MFMA X(NBT, PXW, NC8), Q = 1, and
+// MX-scaled X(NBT, PXW), Q = 2 with 64-channel chunks (NC8 = 4).  The pickers, the tile rule's candidate filter (k3_choose_tile) and
+// conv3_fp8_variant_names() (ltk_debug_conv3_fp8_variants) are all made of them.
+#define K3_Q8_VARIANTS(X) X(2, 4, 2) X(2, 2, 2) X(1, 4, 2) X(1, 2, 2) X(2, 2, 4) X(1, 2, 4) X(2, 1, 2) X(1, 1, 2)
+#define K3_MX_VARIANTS(X) X(2, 2) X(1, 2) X(2, 1) X(1, 1)
+
 static k3_kernel_t k3_pick_q8(int NBT, int PXW, int NC8) {     // fp8 operands: 3x3 stride 1
-#define K3Q(n, p, c) if (NBT == n && PXW == p && NC8 == c) return (k3_kernel_t)conv3_kernel<1, n, p, c, 9, 1, 1>
-    K3Q(2, 4, 2); K3Q(2, 2, 2); K3Q(1, 4, 2); K3Q(1, 2, 2); K3Q(2, 2, 4); K3Q(1, 2, 4); K3Q(2, 1, 2); K3Q(1, 1, 2);
+#define K3Q(n, p, c) if (NBT == n && PXW == p && NC8 == c) return (k3_kernel_t)conv3_kernel<1, n, p, c, 9, 1, 1>;
+    K3_Q8_VARIANTS(K3Q)
 #undef K3Q
     return nullptr;
 }
 
 static k3_kernel_t k3_pick_mx(int NBT, int PXW) {     // MX-scaled fp8 operands: 3x3 stride 1, 64-channel chunks
-#define K3M(n, p) if (NBT == n && PXW == p) return (k3_kernel_t)conv3_kernel<1, n, p, 4, 9, 1, 2>
-    K3M(2, 2); K3M(1, 2); K3M(2, 1); K3M(1, 1);
+#define K3M(n, p) if (NBT == n && PXW == p) return (k3_kernel_t)conv3_kernel<1, n, p, 4, 9, 1, 2>;
+    K3_MX_VARIANTS(K3M)
 #undef K3M
     return nullptr;
+}
+
+static std::string k3_name_fp8(int NBT, int PXW, int NC8, int Q) {
+    char b[64];
+    snprintf(b, sizeof(b), "conv3_kernel<1,%d,%d,%d,9,1,%d>", NBT, PXW, NC8, Q);
+    return b;
+}
+
+std::string conv3_fp8_variant_names() {
+    std::string out;
+#define K3QNAME(n, p, c) out += k3_name_fp8(n, p, c, 1) + "\n";
+    K3_Q8_VARIANTS(K3QNAME)
+#undef K3QNAME
+#define K3MNAME(n, p) out += k3_name_fp8(n, p, 4, 2) + "\n";
+    K3_MX_VARIANTS(K3MNAME)
+#undef K3MNAME
+    return out;
 }
 
 static k3_kernel_t k3_pick_s2(int NBT, int NC8) {     // 3x3 stride 2 pad 1 (face-encoder / U-Net downsamples): PXW = 2
@@ -1480,6 +1503,8 @@ static K3Tile k3_choose_tile(const ConvPlan& p, int N, int Ho, int Wo, int ext, 
             // the fused output head exists for the 512- and 256-pixel tiles only: a one-frame launch (--batch_size 1, or the
             // one-frame remainder of a micro-batched call) would otherwise settle on 128-pixel tiles and be rejected below
             if (head && pxw == 1) continue;
+            // fp8 plans: only the tiles their picker has (under sweep knob CONV3_NC8 = 4 the e4m3 kernels have no 128-pixel tile)
+            if (p.q8 && !(p.mx ? k3_pick_mx(nbt, pxw) : k3_pick_q8(nbt, pxw, NC8))) continue;
             const K3Tile t = k3_tile(pxw, N, Ho, Wo, S, ext, NC8, T);
             if (!t.fit) continue;
             best = t; *PXW = pxw; *NBT = nbt;
@@ -1689,7 +1714,7 @@ int conv3_plan_launch(const ConvPlan& p, const ConvIO& io_in, K3Launch* k3, std:
     if (io.report) {
         ConvReport& r = *io.report;
         r = ConvReport();
-        const std::string nm = head ? "conv3_head_kernel<" + std::to_string(PXW) + ">" : p.mx ? "conv3_kernel (mx)" : p.q8 ? "conv3_kernel (fp8)" : k3_name(G, NBT, PXW, NC8, T, S);
+        const std::string nm = head ? "conv3_head_kernel<" + std::to_string(PXW) + ">" : p.q8 ? k3_name_fp8(NBT, PXW, NC8, p.mx ? 2 : 1) : k3_name(G, NBT, PXW, NC8, T, S);
         snprintf(r.kernel, sizeof(r.kernel), "%s", nm.c_str());
         r.G = G; r.NBT = NBT; r.PXW = PXW; r.NC8 = NC8; r.T = T; r.S = S; r.ksplit = ksplit; r.items = (int)nblk; r.grid = (int)grid;
     }

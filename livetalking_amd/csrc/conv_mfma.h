@@ -116,6 +116,8 @@ struct ConvReport {
 };
 // every fp16 instantiation conv3_plan_launch's pickers can return, one name per line (conv3_mfma.hip: the table the pickers are made of)
 std::string conv3_variant_names();
+// ... and every fp8 one (e4m3 MFMA, Q = 1, and MX-scaled, Q = 2), spelled conv3_kernel<1,NBT,PXW,NC8,9,1,Q>: the tables k3_pick_q8 / k3_pick_mx are made of
+std::string conv3_fp8_variant_names();
 
 struct ConvIO {
     const f16* x; int N, H, W; int x_ld, x_coff;

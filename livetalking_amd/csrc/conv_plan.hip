@@ -80,7 +80,7 @@ int conv_route(ConvPlan* p, ConvRoute* r, int CinArg, int Cout, int kh, int kw, 
     *p = ConvPlan();
     *r = ConvRoute();
     if (quant) {
-        if (transposed || kh != 3 || kw != 3 || sh != 1 || sw != 1 || ph != 1 || pw != 1 || CinArg % 32 != 0) {
+        if (transposed || kh != 3 || kw != 3 || sh != 1 || sw != 1 || ph != 1 || pw != 1 || out_pad != 0 || CinArg % 32 != 0) {
             if (err) *err = "fp8 operands: 3x3 stride-1 pad-1 convs with Cin % 32 == 0 only";
             return -1;
         }

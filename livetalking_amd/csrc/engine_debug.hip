@@ -253,9 +253,10 @@ struct RowPlansOwner { RowGemmPlan p[4]; ~RowPlansOwner() { for (RowGemmPlan& q 
 }  // namespace
 
 namespace {
-// What ltk_conv2d_f16_ex and ltk_debug_conv_plan derive from their arguments
+// What ltk_conv2d_f16_ex / ltk_conv2d_fp8_ex and their host-only twins derive from their arguments
 struct ConvHookCall {
     int act = 0, x_ld = 0, y_ld = 0, res_ld = 0;
+    int quant = 0;               // the plan's: 0 fp16, 1 e4m3 MFMA, 2 MX
     ConvIO io;                   // family 0: the launch without its pointers and scratch
     int Ho = 0, Wo = 0;          // rowconv / rowconvT: the output map
 };
@@ -266,17 +267,20 @@ void conv_report_copy(const ConvReport& cr, ltk_conv_report* rep) {
     rep->ksplit = cr.ksplit; rep->items = cr.items; rep->grid = cr.grid;
 }
 
-// Everything ltk_conv2d_f16_ex decides before it allocates or enqueues, on the host alone: the options and the channel views; family
-// 0: conv_route and, for a conv3 plan, conv3_plan_launch with the split-K scratch taken as unbounded; the row families: their shape
-// refusals.  *rep (may be NULL) = what a launch of this call reports.
+// Everything ltk_conv2d_f16_ex / ltk_conv2d_fp8_ex decide before they allocate or enqueue, on the host alone: the options and the
+// channel views; family 0: conv_route and, for a conv3 plan, conv3_plan_launch with the split-K scratch taken as unbounded; the row
+// families: their shape refusals.  `quant`: 0 fp16 operands, 1 e4m3, 2 MX - x and its view then count fp8 channels (32 per block) and
+// reach the launch in 16-bit units, as mt_graph.hip halves them.  *rep (may be NULL) = what a launch of this call reports.
 int conv_hook_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad, bool has_res,
-                   int relu, const ltk_conv_opts* opts, ltk_conv_report* rep, ConvHookCall* c) {
-    if (!opts || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return fail(LTK_E_INVALID, "bad arguments");
+                   int relu, int quant, const ltk_conv_opts* opts, ltk_conv_report* rep, ConvHookCall* c) {
+    if (!opts || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || quant < 0 || quant > 2) return fail(LTK_E_INVALID, "bad arguments");
     const ltk_conv_opts& o = *opts;
     if (o.family < 0 || o.family > 3 || o.act < 0 || o.act > 3 || o.ups < 0 || o.ups > 2 || (relu && o.act > 1)) return fail(LTK_E_INVALID, "bad options");
+    if (quant && (o.family != 0 || o.ups != 0)) return fail(LTK_E_INVALID, "fp8 operands: the conv kernels (family 0) without an upsample");
     if (rep) { memset(rep, 0, sizeof(*rep)); rep->family = o.family; }
+    c->quant = quant;
     const int act = c->act = relu ? 1 : o.act;
-    const int CinP = Cin <= 8 ? 8 : (Cin + 15) / 16 * 16;
+    const int CinP = quant ? Cin : Cin <= 8 ? 8 : (Cin + 15) / 16 * 16;
     const int x_ld = c->x_ld = o.x_ld ? o.x_ld : CinP, y_ld = c->y_ld = o.y_ld ? o.y_ld : Cout, res_ld = c->res_ld = o.res_ld ? o.res_ld : Cout;
     if (o.x_coff < 0 || o.y_coff < 0 || o.res_coff < 0 || o.x_coff + CinP > x_ld || o.y_coff + Cout > y_ld || (has_res && o.res_coff + Cout > res_ld))
         return fail(LTK_E_INVALID, "channel view outside its buffer");
@@ -284,15 +288,17 @@ int conv_hook_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int s
     if (o.family == 0) {
         ConvPlan plan;
         ConvRoute route;
-        const int rc = conv_route(&plan, &route, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, 0, o.ups == 2 ? 1 : 0, conv_plan_knobs(), &err);
+        const int rc = conv_route(&plan, &route, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, quant, o.ups == 2 ? 1 : 0, conv_plan_knobs(), &err);
         if (rc) return conv_status(rc, err);
+        if (quant && ((x_ld | o.x_coff) & 31)) return fail(LTK_E_INVALID, "fp8 operands: the view of x is given in multiples of 32 channels");
+        const int xdiv = quant ? 2 : 1;           // fp8: two channels per 16-bit unit
         if (o.ups == 2 && !plan.ups4) return fail(LTK_E_INVALID, "conv3: the four-phase upsample-conv serves 3x3 stride-1 pad-1 layers");
         static const f16 there = (f16)0.f;        // the planner asks whether a residual / a scratch exists, never what it holds
         ConvReport cr;
         memset(&cr, 0, sizeof(cr));
         ConvIO& io = c->io;
         io = ConvIO();
-        io.x = nullptr; io.N = N; io.H = H; io.W = W; io.x_ld = x_ld; io.x_coff = o.x_coff;
+        io.x = nullptr; io.N = N; io.H = H; io.W = W; io.x_ld = x_ld / xdiv; io.x_coff = o.x_coff / xdiv;
         io.y = nullptr; io.y_ld = y_ld; io.y_coff = o.y_coff;
         io.res = has_res ? &there : nullptr; io.res_ld = res_ld; io.res_coff = o.res_coff;
         io.relu = act == 1; io.act = act == 1 ? 0 : act;
@@ -337,15 +343,48 @@ int conv_hook_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int s
 int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad,
                         int has_res, int relu, const ltk_conv_opts* opts, ltk_conv_report* rep) {
     ConvHookCall c;
-    return conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, has_res != 0, relu, opts, rep, &c);
+    return conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, has_res != 0, relu, 0, opts, rep, &c);
 }
+
+int ltk_debug_conv_fp8_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad,
+                            int quant, int has_res, const ltk_conv_opts* opts, ltk_conv_report* rep) {
+    if (quant < 0 || quant > 2) return fail(LTK_E_INVALID, "bad arguments");
+    ConvHookCall c;
+    return conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, has_res != 0, 0, quant ? quant : conv_fp8_quant(Cin), opts, rep, &c);
+}
+
+namespace {
+// family 0 of ltk_conv2d_f16_ex / ltk_conv2d_fp8_ex behind conv_hook_plan: the plan, one launch, the stream drained, the report of what ran
+int conv_hook_launch(ltk_engine* e, const ConvHookCall& c, const void* d_x, const float* weight, int Cin, int Cout, int kh, int kw, int sh, int sw,
+                     int ph, int pw, int transposed, int out_pad, const float* scale, const float* shift, float act_scale, int ups4,
+                     const void* d_res, void* d_y, ltk_conv_report* rep) {
+    std::string err;
+    ConvPlanOwner po;
+    int rc = conv_plan_create(&po.p, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, c.quant, act_scale, ups4);
+    if (rc) return conv_status(rc, err);
+    ConvReport cr;
+    memset(&cr, 0, sizeof(cr));
+    ConvIO io = c.io;
+    io.partial = e->d_partial; io.partial_cap = e->partial_cap;
+    io.x = (const f16*)d_x; io.y = (f16*)d_y; io.res = (const f16*)d_res;
+    io.report = &cr;
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    const int lrc = conv_launch(po.p, io, s, &err);
+    const hipError_t he = hipStreamSynchronize(s);      // the launch's error wins; the stream is drained either way
+    if (lrc) return conv_status(lrc, err);
+    if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
+    if (rep) conv_report_copy(cr, rep);                 // what ran: the split under the engine's own scratch
+    return LTK_OK;
+}
+}  // namespace
 
 int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, int kh, int kw, int sh, int sw,
                       int ph, int pw, int transposed, int out_pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
                       const ltk_conv_opts* opts, ltk_conv_report* rep) {
     if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
     ConvHookCall c;
-    int rc = conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, d_res != nullptr, relu, opts, rep, &c);
+    int rc = conv_hook_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, d_res != nullptr, relu, 0, opts, rep, &c);
     if (rc) return rc;
     const ltk_conv_opts& o = *opts;
     CHK(enter_device(e->device));
@@ -360,21 +399,8 @@ int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int C
         if (he != hipSuccess) return fail(LTK_E_HIP, std::string("conv kernel: ") + hipGetErrorString(he));
         return LTK_OK;
     };
-    if (o.family == 0) {
-        ConvPlanOwner po;
-        rc = conv_plan_create(&po.p, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed != 0, out_pad, scale, shift, &err, 0, 1.f, o.ups == 2 ? 1 : 0);
-        if (rc) return conv_status(rc, err);
-        ConvReport cr;
-        memset(&cr, 0, sizeof(cr));
-        ConvIO io = c.io;
-        io.partial = e->d_partial; io.partial_cap = e->partial_cap;
-        io.x = (const f16*)d_x; io.y = (f16*)d_y; io.res = (const f16*)d_res;
-        io.report = &cr;
-        std::lock_guard<std::mutex> g(e->mu);
-        rc = done(conv_launch(po.p, io, s, &err));
-        if (rep && !rc) conv_report_copy(cr, rep);      // what ran: the split under the engine's own scratch
-        return rc;
-    }
+    if (o.family == 0)
+        return conv_hook_launch(e, c, d_x, weight, Cin, Cout, kh, kw, sh, sw, ph, pw, transposed, out_pad, scale, shift, 1.f, o.ups == 2 ? 1 : 0, d_res, d_y, rep);
     RowPlansOwner ro;
     std::vector<float> we;
     if (o.family == 1) {
@@ -687,6 +713,23 @@ int ltk_conv2d_fp8(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
                    float* ms_avg) {
     return conv2d_hook(e, d_x, N, H, W, Cin, weight, Cout, 3, 3, 1, 1, 1, 1, false, 0, scale, shift, conv_fp8_quant(Cin), act_scale, d_res, 0, act,
                        d_y, iters, ms_avg);
+}
+
+int ltk_conv2d_fp8_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int Cout, const float* scale,
+                      const float* shift, float act_scale, int quant, const void* d_res, void* d_y, const ltk_conv_opts* opts, ltk_conv_report* rep) {
+    if (!e || !d_x || !weight || !d_y || quant < 0 || quant > 2 || !(act_scale > 0.f)) return fail(LTK_E_INVALID, "bad arguments");
+    ConvHookCall c;
+    const int rc = conv_hook_plan(N, H, W, Cin, Cout, 3, 3, 1, 1, 1, 1, 0, 0, d_res != nullptr, 0, quant ? quant : conv_fp8_quant(Cin), opts, rep, &c);
+    if (rc) return rc;
+    CHK(enter_device(e->device));
+    return conv_hook_launch(e, c, d_x, weight, Cin, Cout, 3, 3, 1, 1, 1, 1, 0, 0, scale, shift, act_scale, 0, d_res, d_y, rep);
+}
+
+int ltk_debug_conv3_fp8_variants(char* buf, int cap) {
+    const std::string names = conv3_fp8_variant_names();
+    if (!buf || cap <= (int)names.size()) return fail(LTK_E_INVALID, "buffer too small: " + std::to_string(names.size() + 1) + " bytes needed");
+    memcpy(buf, names.c_str(), names.size() + 1);
+    return LTK_OK;
 }
 
 int ltk_musetalk_forward_host(ltk_engine* e, const float* latents, const float* feat, int B, float* unet_out, float* image,

@@ -702,3 +702,40 @@ class Engine:
         buf = C.create_string_buffer(8192)
         _lib.check(_lib.load().ltk_debug_conv3_variants(buf, len(buf)))
         return buf.value.decode().split()
+
+    def conv2d_fp8_ex(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, Cout, scale: Optional[np.ndarray] = None,
+                      shift: Optional[np.ndarray] = None, act_scale: float = 8.0, quant: int = 0, d_res_ptr: int = 0, d_y_ptr: int = 0,
+                      **opts) -> dict:
+        """One 3x3 s1 p1 conv on e4m3 operands with the caller naming what runs (include/ltk.h: ltk_conv2d_fp8_ex; quant 0 = the
+        program's rule, 1 = e4m3 MFMA, 2 = MX; `opts` = the fields of ltk_conv_opts, x_ld / x_coff in fp8 channels).  Returns the
+        report of what was launched, as conv2d_f16_ex does."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32) if scale is not None else None
+        sf = np.ascontiguousarray(shift, dtype=np.float32) if shift is not None else None
+        o = _lib.ConvOpts(**{name: int(v) for name, v in opts.items()})
+        rep = _lib.ConvReport()
+        _lib.check(self._lib.ltk_conv2d_fp8_ex(
+            self._h, C.c_void_p(d_x_ptr), N, H, W, Cin, w.ctypes.data, Cout, sc.ctypes.data if sc is not None else None,
+            sf.ctypes.data if sf is not None else None, float(act_scale), int(quant), C.c_void_p(d_res_ptr) if d_res_ptr else None,
+            C.c_void_p(d_y_ptr), C.byref(o), C.byref(rep)))
+        return _conv_report_dict(rep)
+
+    @staticmethod
+    def conv_fp8_plan(N, H, W, Cin, Cout, quant: int = 0, has_res=False, k=3, stride=1, pad=1, transposed=False, out_pad=0, **opts) -> dict:
+        """What conv2d_fp8_ex would report for this call, decided on the host alone (ltk_debug_conv_fp8_plan; no GPU needed).  k,
+        stride, pad, transposed and out_pad exist to see the fp8 route refuse everything but 3x3 stride 1 pad 1."""
+        kh, kw = (k, k) if isinstance(k, int) else k
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        ph, pw = (pad, pad) if isinstance(pad, int) else pad
+        o = _lib.ConvOpts(**{name: int(v) for name, v in opts.items()})
+        rep = _lib.ConvReport()
+        _lib.check(_lib.load().ltk_debug_conv_fp8_plan(N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, 1 if transposed else 0, out_pad,
+                                                       int(quant), 1 if has_res else 0, C.byref(o), C.byref(rep)))
+        return _conv_report_dict(rep)
+
+    @staticmethod
+    def conv3_fp8_variants() -> list:
+        """Names of every fp8 conv3 instantiation the launch path can pick, e4m3 and MX (ltk_debug_conv3_fp8_variants); no GPU needed."""
+        buf = C.create_string_buffer(8192)
+        _lib.check(_lib.load().ltk_debug_conv3_fp8_variants(buf, len(buf)))
+        return buf.value.decode().split()

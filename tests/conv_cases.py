@@ -342,6 +342,18 @@ class Reference:
             slope = (1.0, 1.0, R.GELU_SLOPE, SILU_SLOPE)[c.act]
             self.tol = 2.0 ** -10 * self.ref.abs() + slope * c.n_prod * 2.0 ** -23 * A + R.F16_FLOOR
 
+    # what sim_device reads: the operands as the device holds them (tests/conv_fp8_cases.py has the e4m3 ones and their faults)
+    sim_chunk = property(lambda self: 8 * self.c.NC8)           # input channels per chunk
+
+    def sim_x(self, cb0: int, fault: Optional[str]) -> torch.Tensor:
+        return _nchw(self.buf.x[:self.c.N, cb0:cb0 + self.c.Cin // 16])
+
+    def sim_w(self, fault: Optional[str]) -> torch.Tensor:
+        return self.w
+
+    def sim_scale(self, fault: Optional[str]) -> torch.Tensor:
+        return self.scale
+
 
 @functools.lru_cache(maxsize=8)
 def reference(ci: int) -> Reference:
@@ -423,14 +435,14 @@ def _halo(x: torch.Tensor, wrap: bool) -> torch.Tensor:
 
 def sim_device(rf: Reference, fault: Optional[str] = None) -> np.ndarray:
     """The op as the conv3 family computes it, buffer to buffer, in fp32: the input view read from its channel blocks (through the
-    nearest-upsample index where the kernel does that), zero halo, one partial sum per channel chunk, the chunks of a split summed into
+    nearest-upsample index where the kernel does that; rf.sim_x / sim_w / sim_scale: fp16 here, e4m3 codes in conv_fp8_cases), zero halo, one partial sum per channel chunk, the chunks of a split summed into
     its slab and the slabs in order, the affine + residual + activation on the fp32 sum, one rounding to fp16, the images of a tile stored
     one by one into the view's channel blocks of the pre-filled output buffer.  `fault`: one of FAULTS."""
     c, b = rf.c, rf.buf
     N = c.N
     geo = geometry(c)
     cb0 = 0 if fault == "x_cb0" else b.x_cb0
-    x = _nchw(b.x[:N, cb0:cb0 + c.Cin // 16])
+    x, w, scale = rf.sim_x(cb0, fault), rf.sim_w(fault), rf.sim_scale(fault)
     if c.ups == 1:
         if fault == "ups":
             yy, xx = torch.meshgrid(torch.arange(c.H), torch.arange(c.W), indexing="ij")
@@ -451,7 +463,7 @@ def sim_device(rf: Reference, fault: Optional[str] = None) -> np.ndarray:
             xp = xp[:, :, 1:, 1:]
         return F.conv2d(xp, wc, stride=c.stride)
 
-    per = 8 * c.NC8
+    per = rf.sim_chunk
     acc = None
     with torch.no_grad():
         for s in range(c.ksplit):
@@ -460,14 +472,14 @@ def sim_device(rf: Reference, fault: Optional[str] = None) -> np.ndarray:
                 if fault == "chunk" and ch == c.nchunks - 1:
                     continue
                 sl = slice(ch * per, (ch + 1) * per)
-                p = part(x[:, sl], rf.w[sl] if c.transposed else rf.w[:, sl])
+                p = part(x[:, sl], w[sl] if c.transposed else w[:, sl])
                 slab = p if slab is None else slab + p
             if slab is None or (fault == "split" and s == 1):
                 continue
             acc = slab if acc is None else acc + slab
         if acc is None:
             acc = torch.zeros(N, c.Cout, c.Ho, c.Wo)
-        pre = acc * rf.scale.view(1, -1, 1, 1) + rf.shift.view(1, -1, 1, 1)
+        pre = acc * scale.view(1, -1, 1, 1) + rf.shift.view(1, -1, 1, 1)
         r = _nchw(b.res[:N, b.r_cb0:b.r_cb0 + c.Cout // 16]) if c.res else 0.0
         if fault == "finish_act":
             out = _cb(activate(c, pre) + r)

@@ -486,6 +486,17 @@ def test_abi_argument_validation_without_gpu():
     assert lib.ltk_musetalk_set_fp8(null, 1, 0.0) == E_INVALID
     assert lib.ltk_f32_to_e4m3(null, 4, null) == E_INVALID
     assert lib.ltk_conv2d_fp8(null, null, 1, 1, 1, 32, null, 32, null, null, 8.0, null, 0, null, 0, None) == E_INVALID
+    assert lib.ltk_conv2d_fp8_ex(null, null, 1, 1, 1, 32, null, 32, null, null, 8.0, 0, null, null, None, None) == E_INVALID
+    assert b"bad arguments" in lib.ltk_last_error()
+    assert lib.ltk_debug_conv_fp8_plan(1, 1, 1, 32, 32, 3, 3, 1, 1, 1, 1, 0, 0, 1, 0, None, None) == E_INVALID and b"bad arguments" in lib.ltk_last_error()
+    o = _lib.ConvOpts()
+    assert lib.ltk_debug_conv_fp8_plan(1, 1, 1, 32, 32, 3, 3, 1, 1, 1, 1, 0, 0, 3, 0, C.byref(o), None) == E_INVALID      # quant is 0, 1 or 2
+    assert lib.ltk_debug_conv_fp8_plan(1, 1, 1, 32, 32, 3, 3, 1, 1, 1, 1, 0, 0, 1, 0, C.byref(o), None) == 0              # rep may be NULL
+    assert lib.ltk_debug_conv3_fp8_variants(None, 0) == E_INVALID and b"buffer too small" in lib.ltk_last_error()
+    small = C.create_string_buffer(8)
+    assert lib.ltk_debug_conv3_fp8_variants(small, len(small)) == E_INVALID
+    # the fp8 hooks reuse ltk_conv_opts / ltk_conv_report as they are (include/ltk.h): 12 ints; char[64] + 12 ints
+    assert C.sizeof(_lib.ConvOpts) == 48 and C.sizeof(_lib.ConvReport) == 112
     if not torch.cuda.is_available():
         h = C.c_void_p()
         rc = lib.ltk_engine_create(0, C.byref(h))
