@@ -98,6 +98,40 @@ int ltk_mel_step(ltk_engine* e, const float* pcm, int n_samples, const int32_t* 
  * session's NEXT call (knob PREFETCH) that cannot be launched is not an error. */
 int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream);
 
+/* The same call with a deferred wait (knob DEFER, default on; LTK_DEFER=0 makes it ltk_wav2lip_infer): for a lone session issuing
+ * its calls back to back.  The reference's inference thread only queues the handles it gets (avatars/base_avatar.py:366-376);
+ * whoever reads the frames does so through this library or on a stream, so the call need not wait for its OWN pass.
+ *
+ * Contract.  A deferred call returns when its pass is enqueued and every pass issued before it is complete: when a call
+ * returns, at most one pass - its own - is outstanding, frames complete in issue order, and in steady state a call still takes one
+ * period (what the caller measures as its inference rate stays true).  d_mel and d_pred of a call must stay allocated until the
+ * NEXT call on this engine (deferred or not) or ltk_engine_sync has returned.
+ *   stream      as `stream` of ltk_wav2lip_infer: where d_mel was produced; 0 = none, the inputs are ready.
+ *   flags       LTK_DEFER_SYNC: behave as ltk_wav2lip_infer for this call.
+ *   deferred    (may be NULL) set to 1 when the call returned with its pass in flight, to 0 when the frames are ready (knob off,
+ *               LTK_DEFER_SYNC, a call that does not qualify): a caller wraps or orders its frames only in the first case.
+ * No stream is made to wait at the call: such a wait sits in one of the process's few hardware queues for the length of the
+ * pass, and for a caller that issues calls back to back it cost more than the deferral gains (45 us of a 1.2-ms step).  Readers
+ * use ltk_wav2lip_order_stream: the wait is issued when the frames are read.
+ * Who may read a frame when: ltk_paste_back / ltk_paste_back_batch / ltk_egress_frame / ltk_egress_batch order themselves behind
+ * the pass that writes the d_pred they are given (GPU-side); any other reader first calls
+ * ltk_wav2lip_order_stream(e, d_pred, bytes, stream) - `stream` (0 = the default stream) then waits, on the GPU, for the pass in
+ * flight that writes [d_pred, d_pred + bytes), if there is one; no host wait - or ltk_engine_sync, or passes LTK_DEFER_SYNC.
+ * Only a call that qualifies for knob PREFETCH defers - one request, product configuration, no face cache, one arena pass; every
+ * other call (and every ltk_wav2lip_infer call) runs behind the pass in flight and returns when its own frames are ready, which
+ * implies the earlier ones.  ltk_avatar_release, ltk_engine_sync / _destroy, a knob change and the debug / timing entries wait
+ * for the pass in flight (host side); the avatar banks it reads are held by the pass, not by the call.
+ * Errors.  On an error return nothing is in flight - neither of this call nor of the pass before it - and the frames of BOTH
+ * calls are invalid when the error is a device failure (LTK_E_HIP); after a refused request (bad arguments, unknown avatar) the
+ * earlier call's frames are complete and valid.  A device failure of pass N is reported by the call that waits for it - call
+ * N+1, or whichever entry drains the engine first - and its text says so.
+ * ltk_wav2lip_defer_stats: calls that returned with their pass outstanding, the most passes outstanding at such a return (1 with
+ * one caller thread), passes outstanding now. */
+#define LTK_DEFER_SYNC 2
+int ltk_wav2lip_infer_deferred(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream, int flags, int* deferred);
+int ltk_wav2lip_order_stream(ltk_engine* e, const void* d_pred, size_t bytes, void* stream);
+int ltk_wav2lip_defer_stats(ltk_engine* e, unsigned long long* deferred, unsigned long long* max_outstanding, unsigned long long* outstanding);
+
 /* avatars/wav2lip_avatar.py:141-147 LipReal.paste_back_frame: bilinear-resize
  * (cv2.resize INTER_LINEAR semantics) the 256x256 prediction to the frame's box
  * and paste it into a copy of full_bank[idx].  d_pred: device uint8
@@ -428,6 +462,14 @@ int ltk_avatar_face_cache_bytes(ltk_engine* e, int avatar_id, size_t* bytes);
  * index, a multi-request call) runs the whole pass and the unused prefetch is dropped.  Counters since engine creation:
  * single-request calls that found their encoder outputs prefetched / that did not / prefetches issued. */
 int ltk_wav2lip_prefetch_stats(ltk_engine* e, unsigned long long* hits, unsigned long long* misses, unsigned long long* issued);
+
+/* Device-free: the prefetch-slot walk of a lone session's first `calls` back-to-back calls (csrc/defer_window.h, the rule
+ * ltk_wav2lip_infer runs), with `outstanding` = 0 (synchronous calls: two slots) or 1 (deferred calls: the slot of the pass in
+ * flight is skipped, three slots) and the index jumping in front of call `jump_at` (-1: never).  Returns the last call
+ * (0-based) that runs a launch variant for the first or second time - eagerly, then captured (knob GRAPH); every later call
+ * replays - or -1 for bad arguments; *slots_used = slots the walk touched.  Tests derive from it when
+ * ltk_wav2lip_graph_count must have stopped growing. */
+int ltk_debug_solo_walk(int outstanding, int calls, int jump_at, int* slots_used);
 
 /* Number of (program, frame count) pairs of the MuseTalk side - the U-Net + VAE decoder pass behind ltk_musetalk_infer, the
  * Whisper encoder behind ltk_whisper_step - that currently run from a captured hipGraph (knob GRAPH; captured the second time

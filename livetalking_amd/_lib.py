@@ -59,6 +59,8 @@ class NormReport(C.Structure):
     _fields_ = [("kernel", C.c_char * 64)] + [(n, C.c_int) for n in ("impl", "segs", "members", "grid")]
 
 
+DEFER_SYNC = 2      # flag of ltk_wav2lip_infer_deferred
+
 # every symbol include/ltk.h declares: (restype, argtypes)
 SYMBOLS = {
     "ltk_last_error": (C.c_char_p, []),
@@ -72,6 +74,9 @@ SYMBOLS = {
     "ltk_avatar_release": (C.c_int, [C.c_void_p, C.c_int]),
     "ltk_mel_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_wav2lip_infer": (C.c_int, [C.c_void_p, C.POINTER(W2lReq), C.c_int, C.c_void_p]),
+    "ltk_wav2lip_infer_deferred": (C.c_int, [C.c_void_p, C.POINTER(W2lReq), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "ltk_wav2lip_order_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ltk_wav2lip_defer_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "ltk_paste_back": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_paste_back_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_musetalk_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int, C.POINTER(NamedTensor), C.c_int, C.c_int]),
@@ -130,6 +135,7 @@ SYMBOLS = {
     "ltk_wav2lip_graph_count": (C.c_int, [C.c_void_p]),
     "ltk_program_graph_count": (C.c_int, [C.c_void_p]),
     "ltk_wav2lip_prefetch_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "ltk_debug_solo_walk": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ltk_avatar_face_cache_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "ltk_musetalk_op_count": (C.c_int, [C.c_void_p]),
     "ltk_musetalk_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),

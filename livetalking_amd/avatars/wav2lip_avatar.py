@@ -130,6 +130,59 @@ def warm_up(batch_size, model, modelres=256):
         eng.wav2lip_forward_host(mel[:n], img[:n])
 
 
+def _frame_handle_type():
+    """The type of the handles `inference_batch` returns: a torch.Tensor (uint8 [256][256][3], as before) that may name a pass still
+    in flight (knob DEFER).  The first torch operation that touches such a handle makes torch's current stream wait, on the GPU, for
+    that pass (Engine.order_frames) - so `torch.stack(pred).cpu()` right behind the call sees the frames, while a session that only
+    hands its handles to paste_back_frame / the egress never gives torch's stream anything to wait for."""
+    import torch
+
+    class FrameHandle(torch.Tensor):
+        @classmethod
+        def __torch_function__(cls, func, types, args=(), kwargs=None):
+            if getattr(func, "__name__", "") == "data_ptr":          # (the engine's own consumers take the pointer and order themselves)
+                return super().__torch_function__(func, types, args, kwargs or {})
+            pending = None
+            stack = list(args)
+            if kwargs:
+                stack.extend(kwargs.values())                        # tensors=, out=, other=
+            while stack:
+                a = stack.pop()
+                if isinstance(a, (list, tuple)):
+                    stack.extend(a)
+                elif isinstance(a, FrameHandle):
+                    p = a.__dict__.get("_ltk_pass")
+                    if p is not None:
+                        p.order()
+                        pending = p
+            ret = super().__torch_function__(func, types, args, kwargs or {})
+            if pending is not None:
+                # what is derived from a handle (a view, a slice) names the same pass: used later on ANOTHER stream it orders that one too
+                for r in (ret if isinstance(ret, (list, tuple)) else (ret,)):
+                    if isinstance(r, FrameHandle):
+                        r._ltk_pass = pending
+            return ret
+
+    return FrameHandle
+
+
+class _PendingPass:
+    """What the handles of one deferred call share; the engine forgets the pass when it is complete, an order is then free."""
+    __slots__ = ("engine", "ptr", "nbytes", "streams")
+
+    def __init__(self, engine, ptr, nbytes):
+        self.engine, self.ptr, self.nbytes, self.streams = engine, ptr, nbytes, set()
+
+    def order(self):
+        st = self.engine.current_stream()
+        if st not in self.streams:              # the B handles of a call share one wait per stream
+            self.engine.order_frames(self.ptr, self.nbytes, st)
+            self.streams.add(st)
+
+
+_FRAME_HANDLE = None
+
+
 @register("avatar", "wav2lip")
 class LipReal(DeviceEgressMixin, BaseAvatar):
     _egress_source = SRC_WAV2LIP      # opt.egress = "bgr24" | "i420": device-side process_frames (egress.py)
@@ -144,6 +197,11 @@ class LipReal(DeviceEgressMixin, BaseAvatar):
         h, w = self.frame_list_cycle[0].shape[:2]
         self._frame_hw = (int(h), int(w))
         self._sched = get_scheduler(self.engine)
+        self._held = (None, None)
+        # knob DEFER: the handles of a deferred call order their readers themselves (FrameHandle), so this session's engine may defer
+        # (a fake engine of the tests has no such entry and stays as it is)
+        if hasattr(self.engine, "order_frames"):
+            self.engine.defer_handles = True
         self.asr = MelASR(opt, self, engine=self.engine)
         self.asr.warm_up()
 
@@ -163,11 +221,23 @@ class LipReal(DeviceEgressMixin, BaseAvatar):
         if mel.shape[0] != B:
             raise ValueError(f"expected {B} mel windows, got {mel.shape[0]}")
         pred = torch.empty((B, 256, 256, 3), dtype=torch.uint8, device=mel.device)
-        self._sched.infer(self._aid, int(index), B, mel.data_ptr(), pred.data_ptr())
+        deferred = self._sched.infer(self._aid, int(index), B, mel.data_ptr(), pred.data_ptr())
         self._last_mel = mel            # keep inputs alive until the call returned (it has)
         # (everything from here to the next engine call is time the GPU idles when this is the only session: one unbind instead of
         # B slicings, bank indices left to the consumer's thread - 50 -> 20 us of Python per call, scripts/host_overhead.py)
         items = list(pred.unbind(0))
+        if deferred:
+            # the call returned with its pass in flight (knob DEFER: a lone session; the pass before it is complete).  Its mel AND its
+            # frame block stay allocated until that pass is complete, whatever the caller does with the handles - torch's allocator
+            # knows nothing of the engine's stream and would hand a dropped block to the next taker: the last TWO calls' blocks are held
+            self._held = (self._held[1], (mel, pred))
+            global _FRAME_HANDLE
+            if _FRAME_HANDLE is None:
+                _FRAME_HANDLE = _frame_handle_type()
+            pending = _PendingPass(self.engine, pred.data_ptr(), pred.numel())
+            items = [t.as_subclass(_FRAME_HANDLE) for t in items]
+            for t in items:
+                t._ltk_pass = pending
         if _PASTE_BATCH and hasattr(self.engine, "paste_back_batch"):
             # the process thread will ask for these B composites one by one, in order (base_avatar.py:429-433): remember
             # the batch so that the FIRST request composites all of them and moves them to the host in one copy

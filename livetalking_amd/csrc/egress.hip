@@ -81,6 +81,7 @@ int ltk_egress_frame(ltk_engine* e, ltk_egress* s, const ltk_egress_req* q, uint
         const uint8_t* full = a.d_full + (size_t)q->idx * bytes;
         if (q->d_pred) {
             const int32_t* c = a.coords.data() + 4 * (size_t)q->idx;
+            CHK(order_behind_pending(e, sl.s, q->d_pred, (size_t)256 * 256 * 3));     // knob DEFER: the pass that writes the frame may be in flight
             launch_paste(full, H, W, (const uint8_t*)q->d_pred, c[0], c[1], c[2], c[3], s->d_frame, sl.s);
             src = s->d_frame;
         } else {
@@ -170,6 +171,8 @@ int ltk_egress_batch(ltk_engine* e, ltk_egress* s, int source, int avatar, const
     uint8_t* const conv = comp + bytes * n;
     if (hold_w) {                                          // composites: one launch per 16 frames
         const Avatar& a = *hold_w;
+        const hipError_t oe = order_behind_pending(e, sl.s, d_pred, (size_t)n * 256 * 256 * 3);      // knob DEFER: the frames' pass may be in flight
+        if (oe != hipSuccess) return fail(LTK_E_HIP, std::string("egress_batch: ") + hipGetErrorString(oe));
         for (int i0 = 0; i0 < n; i0 += kPasteBatch) {
             const int m = std::min(kPasteBatch, n - i0);
             PasteBatch pb;

@@ -87,10 +87,12 @@ int ltk_engine_create(int device, ltk_engine** out) {
 void ltk_engine_destroy(ltk_engine* e) {
     if (!e) return;
     if (e->tm_calls)
-        fprintf(stderr, "ltk: ltk_wav2lip_infer host time per call over %lu calls: prepare %.1f us, upload + pass launch %.1f us, prefetch join / serial launch %.1f us, wait for the device %.1f us\n",
-                e->tm_calls, e->tm_prep / e->tm_calls, e->tm_launch / e->tm_calls, e->tm_pf / e->tm_calls, e->tm_wait / e->tm_calls);
+        fprintf(stderr, "ltk: ltk_wav2lip_infer host time per call over %lu calls: prepare %.1f us, upload + pass launch %.1f us, prefetch join / serial launch %.1f us, wait for the device %.1f us, wait for the previous pass (deferred calls) %.1f us\n",
+                e->tm_calls, e->tm_prep / e->tm_calls, e->tm_launch / e->tm_calls, e->tm_pf / e->tm_calls, e->tm_wait / e->tm_calls, e->tm_prev / e->tm_calls);
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
+    (void)drain_pending(e);              // knob DEFER: the banks a pass in flight held go with its record
+    e->defer.clear([](hipEvent_t& ev) { if (ev) (void)hipEventDestroy(ev); });
     wav2lip_unload(e);
     if (e->d_basis) (void)hipFree(e->d_basis);
     if (e->d_lohi) (void)hipFree(e->d_lohi);
@@ -126,8 +128,10 @@ void ltk_engine_destroy(ltk_engine* e) {
 int ltk_engine_sync(ltk_engine* e) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
     CHK(enter_device(e->device));
-    CHK(hipDeviceSynchronize());
-    return LTK_OK;
+    const hipError_t se = hipDeviceSynchronize();
+    const int drc = drain_pending(e);     // knob DEFER: the window is empty afterwards; a pass that failed on the device is reported here
+    if (se != hipSuccess) return fail(LTK_E_HIP, std::string("hipDeviceSynchronize(): ") + hipGetErrorString(se));
+    return drc;
 }
 
 int ltk_avatar_register(ltk_engine* e, const uint8_t* face_bank, const uint8_t* full_bank,
@@ -159,6 +163,9 @@ int ltk_avatar_register(ltk_engine* e, const uint8_t* face_bank, const uint8_t* 
 
 int ltk_avatar_release(ltk_engine* e, int avatar_id) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
+    // knob DEFER: a pass in flight keeps the banks it reads through its record; the release waits for it, so that - as without the
+    // knob - the bank's memory is free when the last holder lets go and nothing enqueued still names the id
+    if (e->defer.newest()) { (void)hipSetDevice(e->device); (void)drain_pending(e); }
     {   // prefetch slots keyed by this avatar: their data will never be asked for again, and their hold on the bank goes once the
         // prefetch that reads it has finished (ids are never reused, so a stale key could not match anyway)
         std::lock_guard<std::mutex> ge(e->mu);
@@ -216,6 +223,7 @@ int ltk_paste_back(ltk_engine* e, int avatar_id, int idx, const void* d_pred, vo
     const int32_t* c = a.coords.data() + 4 * (size_t)idx;
     const size_t bytes = (size_t)a.H * a.W * 3;
     StreamLease sl(e, stream);
+    CHK(order_behind_pending(e, sl.s, d_pred, (size_t)256 * 256 * 3));      // knob DEFER: the pass that writes the frame may be in flight
     const uint8_t* full = a.d_full + (size_t)idx * bytes;
     if (out_is_device) {
         launch_paste(full, a.H, a.W, (const uint8_t*)d_pred, c[0], c[1], c[2], c[3], (uint8_t*)out, sl.s);
@@ -244,6 +252,7 @@ int ltk_paste_back_batch(ltk_engine* e, int avatar_id, const int32_t* idx, const
     StreamLease sl(e, stream);
     ScratchLease sc(e, bytes * n);
     if (!sc.s.d) return fail(LTK_E_NOMEM, "scratch allocation failed");
+    CHK(order_behind_pending(e, sl.s, d_pred, (size_t)n * 256 * 256 * 3));  // knob DEFER: the pass that writes the frames may be in flight
     for (int i0 = 0; i0 < n; i0 += kPasteBatch) {          // one launch per 16 frames
         const int m = std::min(kPasteBatch, n - i0);
         PasteBatch pb;

@@ -10,6 +10,7 @@ int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6
     if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
     if (B > e->max_frames) return fail(LTK_E_INVALID, "B exceeds max_frames");
     CHK(enter_device(e->device));
+    { const int drc = drain_pending(e); if (drc) return drc; }      // knob DEFER: behind the pass in flight (as every hook below)
     const int mb = std::min(e->micro_batch, kPackMaxFrames);
     const int cap = std::min(B, mb);
     DevBuf d_mel, d_face, d_pred;
@@ -50,6 +51,8 @@ int ltk_debug_saturation(ltk_engine* e, int reset, unsigned long long* n_at_limi
 
 int ltk_debug_capture(ltk_engine* e, int enable) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
+    (void)hipSetDevice(e->device);
+    { const int drc = drain_pending(e); if (drc) return drc; }
     std::lock_guard<std::mutex> g(e->mu);
     e->capture = enable != 0;
     if (!enable) { e->taps.clear(); e->tap_shape.clear(); }
@@ -63,6 +66,8 @@ int ltk_debug_set_knob(const char* name, int value) {
 
 int ltk_debug_get(ltk_engine* e, const char* layer, float* out, size_t n_floats) {
     if (!e || !layer || !out) return fail(LTK_E_INVALID, "bad arguments");
+    (void)hipSetDevice(e->device);
+    { const int drc = drain_pending(e); if (drc) return drc; }
     std::lock_guard<std::mutex> g(e->mu);
     auto it = e->taps.find(layer);
     if (it == e->taps.end()) return fail(LTK_E_STATE, std::string("no capture for layer ") + layer);
@@ -96,6 +101,7 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
     if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
     if (frames > e->max_frames) return fail(LTK_E_INVALID, "frames exceeds max_frames");
     CHK(enter_device(e->device));
+    { const int drc = drain_pending(e); if (drc) return drc; }
     std::lock_guard<std::mutex> g(e->mu);
     if (e->capture) return fail(LTK_E_STATE, "disable capture before timing");
     // the pass as ltk_wav2lip_infer runs it (pack_mel + conv stack with the bank gather and the output head fused, knob
@@ -145,11 +151,18 @@ int ltk_wav2lip_time_convs(ltk_engine* e, int frames, int iters, float* ms_per_p
 
 int ltk_wav2lip_prefetch_stats(ltk_engine* e, unsigned long long* hits, unsigned long long* misses, unsigned long long* issued) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
+    (void)hipSetDevice(e->device);
+    { const int drc = drain_pending(e); if (drc) return drc; }
     std::lock_guard<std::mutex> g(e->mu);
     if (hits) *hits = e->pf_hits;
     if (misses) *misses = e->pf_misses;
     if (issued) *issued = e->pf_issued;
     return LTK_OK;
+}
+
+int ltk_debug_solo_walk(int outstanding, int calls, int jump_at, int* slots_used) {
+    if (outstanding < 0 || outstanding > 1 || calls <= 0) return -1;
+    return solo_walk_last_capture(outstanding, calls, jump_at, slots_used);
 }
 
 int ltk_program_graph_count(ltk_engine* e) {
@@ -160,6 +173,8 @@ int ltk_program_graph_count(ltk_engine* e) {
 
 int ltk_wav2lip_graph_count(ltk_engine* e) {
     if (!e) return 0;
+    (void)hipSetDevice(e->device);
+    (void)drain_pending(e);
     std::lock_guard<std::mutex> g(e->mu);
     return e->graphs.live();
 }

@@ -18,6 +18,7 @@
 
 #include "../../include/ltk.h"
 #include "conv_mfma.h"
+#include "defer_window.h"
 #include "dw_kernels.h"
 #include "hubert_kernels.h"
 #include "misc_kernels.h"
@@ -221,7 +222,8 @@ struct ltk_engine {
     // `pool_mu` owns the avatar tables + next_avatar, the scratch / stream pools and the tm_* sums.  It is a leaf: never held while
     // `mu` or an egress session's lock is taken (both may be held when it is taken), never held across a HIP call that waits.
     // (Known exception: ltk_avatar_release erases the table's reference under `pool_mu`; when no call holds the bank, its hipFree
-    // runs there.)  An egress session's lock (ltk_egress::mu) owns that session's buffers; it is never nested with `mu`.
+    // runs there.)  An egress session's lock (ltk_egress::mu) owns that session's buffers; `mu` is never held when it is taken (the
+    // egress entries take `mu` briefly under it, order_behind_pending).
     std::mutex mu;
     std::mutex pool_mu;
     // wav2lip
@@ -260,7 +262,10 @@ struct ltk_engine {
     unsigned long pf_hits = 0, pf_misses = 0, pf_issued = 0;
     std::atomic<bool> pf_fail_logged{false};       // a prefetch that could not be launched is reported once (the call itself succeeds)
     // LTK_INFER_TIMING=1 (measurement): host time of ltk_wav2lip_infer by phase, printed when the engine is destroyed
-    double tm_prep = 0, tm_launch = 0, tm_pf = 0, tm_wait = 0;
+    double tm_prep = 0, tm_launch = 0, tm_pf = 0, tm_wait = 0, tm_prev = 0;      // tm_prev: a deferred call's wait for the pass before it
+    // knob DEFER (defer_window.h): the Wav2Lip passes that are enqueued and not yet known to be complete.  Its own (leaf) lock.
+    DeferWindow<hipEvent_t> defer;
+    std::atomic<unsigned> defer_epoch{0};     // knob_epoch() the newest deferred pass was enqueued under
     unsigned long tm_calls = 0;
     size_t buf_halfs[B_COUNT] = {0};  // per frame
     float* d_head = nullptr;          // 96 weights + 3 bias
@@ -432,33 +437,127 @@ int GraphCache<Key>::run(ltk_engine* e, const Key& k, hipStream_t s, const char*
     return 0;
 }
 
+// ---------------------------------------------------------------- knob DEFER: passes in flight behind a returned call
+// Wait (host) for every pass of the window and retire its record.  The compute stream runs them in order, so the newest event covers
+// all of them.  Not under e->mu (it waits).  LTK_E_HIP when a pass failed asynchronously: nothing of it is in flight any more, its
+// frames are invalid.
+inline int drain_pending(ltk_engine* e) {
+    const auto recs = e->defer.snapshot();
+    if (recs.empty()) return 0;
+    const hipError_t se = hipEventSynchronize(recs.back()->ev);
+    if (se != hipSuccess) (void)hipStreamSynchronize(e->compute);
+    for (const auto& r : recs) e->defer.retire(r);
+    if (se != hipSuccess)
+        return fail(LTK_E_HIP, std::string("a deferred ltk_wav2lip_infer pass issued by an EARLIER call failed on the device (reported by the call that waited for it): ") +
+                                   hipGetErrorString(se));
+    return 0;
+}
+// A reader of [p, p + bytes) on stream `s` (paste-back, egress): `s` waits, on the GPU, for the passes of the window that write there
+// (under e->mu, taken only when there is something to wait for: while another thread has a capture open on the compute stream the
+// runtime refuses a wait for an event of that stream - "dependency created on uncaptured work in another stream" - and captures run
+// under e->mu.  Callers hold no lock but an egress session's, which is never held when e->mu is taken elsewhere.)
+inline hipError_t order_behind_pending(ltk_engine* e, hipStream_t s, const void* p, size_t bytes) {
+    const auto writers = e->defer.writers_of(p, bytes);
+    if (writers.empty()) return hipSuccess;
+    std::lock_guard<std::mutex> g(e->mu);
+    for (const auto& r : writers) {
+        const hipError_t we = hipStreamWaitEvent(s, r->ev, 0);
+        if (we != hipSuccess) return we;
+    }
+    return hipSuccess;
+}
+
+// What a call that may be deferred hands to infer_call.  `want`: the caller asked for it; `enq` sets `ok` when the call qualifies (a
+// solo call under knob DEFER, w2l_infer.hip) and `slot`; hold / ranges move into the pass's record.
+struct DeferCall {
+    bool want = false, ok = false;
+    int slot = 0;
+    std::vector<std::shared_ptr<void>> hold;
+    std::vector<PredRange> ranges;
+    double wait_prev_us = 0;             // LTK_INFER_TIMING: host time spent waiting for the passes in front
+    bool deferred = false;               // out: the call returned with its pass in flight
+};
+
 // The call protocol of an inference entry point (include/ltk.h): inputs produced on the caller's stream are waited for on the
 // compute stream; `enq` enqueues under e->mu and returns 0 or its error; `done` is recorded inside the lock and the lock released
 // BEFORE the wait, so the next call's launches queue up behind this one's kernels instead of behind this thread's wake-up
 // (calls of several host threads are serialised for the enqueue only: stream order then keeps them apart on the GPU).  An error
 // behind launches drains the compute stream: nothing of the call may still be writing the caller's buffers when it returns.
+// The call then waits for `done` - or, deferred (`dc`, knob DEFER), for the passes that were in flight when it enqueued, and leaves
+// its own in the window.  A synchronous call's `done` covers those passes too (one stream): it retires them.  On an error return
+// nothing is in flight, neither of this call nor of the window.
 template <class Enq>
-int infer_call(ltk_engine* e, void* stream, Enq enq) {
-    Ev done;
-    CHK(done.create());
+int infer_call(ltk_engine* e, void* stream, Enq enq, DeferCall* dc = nullptr) {
+    auto make_ev = [](hipEvent_t* ev) { return hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess; };
+    auto rec = e->defer.acquire(make_ev);
+    if (!rec) { (void)hipGetLastError(); (void)drain_pending(e); return fail(LTK_E_HIP, "hipEventCreate failed"); }
     int rc = 0;
+    bool launched = false, stream_wait_failed = false;
+    std::vector<decltype(rec)> before;
     {
         std::lock_guard<std::mutex> g(e->mu);
         if (stream) {  // inputs were produced on the caller's stream
             Ev ready;
-            CHK(ready.create());
-            CHK(hipEventRecord(ready.e, (hipStream_t)stream));
-            CHK(hipStreamWaitEvent(e->compute, ready.e, 0));
+            hipError_t he = ready.create();
+            if (he == hipSuccess) he = hipEventRecord(ready.e, (hipStream_t)stream);
+            if (he == hipSuccess) he = hipStreamWaitEvent(e->compute, ready.e, 0);
+            if (he != hipSuccess) rc = fail(LTK_E_HIP, std::string("waiting for the caller's stream: ") + hipGetErrorString(he));
         }
-        rc = enq();
-        if (!rc && hipEventRecord(done.e, e->compute) != hipSuccess) rc = fail(LTK_E_HIP, "hipEventRecord failed");
+        if (!rc) {
+            launched = true;
+            rc = enq();
+            if (!rc && hipEventRecord(rec->ev, e->compute) != hipSuccess) rc = fail(LTK_E_HIP, "hipEventRecord failed");
+        }
+        if (!rc && dc && dc->want && dc->ok) {
+            rec->hold = std::move(dc->hold);
+            rec->ranges = std::move(dc->ranges);
+            rec->slot = dc->slot;
+            before = e->defer.push(rec);
+            dc->deferred = true;
+            // the caller's stream sees the inputs free again behind the pass (under the lock: the runtime refuses a wait for an event of
+            // the compute stream while another thread has a capture open on it, and captures run under the lock)
+            if (stream && hipStreamWaitEvent((hipStream_t)stream, rec->ev, 0) != hipSuccess) stream_wait_failed = true;
+        } else if (!rc) {
+            before = e->defer.snapshot();
+        }
     }
-    if (!rc) {
-        if (stream && hipStreamWaitEvent((hipStream_t)stream, done.e, 0) != hipSuccess) rc = fail(LTK_E_HIP, "hipStreamWaitEvent failed");
-        if (hipEventSynchronize(done.e) != hipSuccess) rc = fail(LTK_E_HIP, "hipEventSynchronize failed");
-    } else {
+    if (rc) {
+        const std::string msg = g_err;                 // (the drain below may set its own text: this call's error is the one reported)
+        if (launched) (void)hipStreamSynchronize(e->compute);
+        (void)drain_pending(e);
+        e->defer.give_back(rec);
+        return fail(rc, msg);
+    }
+    if (dc && dc->deferred) {
+        if (stream_wait_failed) rc = fail(LTK_E_HIP, "hipStreamWaitEvent failed");
+        if (!rc && !before.empty()) {
+            const auto t0 = std::chrono::steady_clock::now();
+            const hipError_t se = hipEventSynchronize(before.back()->ev);
+            dc->wait_prev_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+            if (se != hipSuccess)
+                rc = fail(LTK_E_HIP, std::string("the deferred pass of the PREVIOUS ltk_wav2lip_infer_deferred call failed on the device (reported by this call, which "
+                                                 "waited for it; the frames of both calls are invalid): ") + hipGetErrorString(se));
+        }
+        if (rc) {                                       // both calls' frames are invalid, nothing stays in flight
+            const std::string msg = g_err;
+            (void)hipStreamSynchronize(e->compute);
+            for (const auto& r : before) e->defer.retire(r);
+            e->defer.retire(rec);
+            dc->deferred = false;
+            return fail(rc, msg);
+        }
+        for (const auto& r : before) e->defer.retire(r);
+        e->defer.returned();
+        return 0;
+    }
+    if (stream && hipStreamWaitEvent((hipStream_t)stream, rec->ev, 0) != hipSuccess) rc = fail(LTK_E_HIP, "hipStreamWaitEvent failed");
+    if (hipEventSynchronize(rec->ev) != hipSuccess) {
+        rc = fail(LTK_E_HIP, before.empty() ? "hipEventSynchronize failed"
+                                            : "hipEventSynchronize failed (this call, or the deferred pass of an earlier call it ran behind: the frames of both are invalid)");
         (void)hipStreamSynchronize(e->compute);
     }
+    for (const auto& r : before) e->defer.retire(r);
+    e->defer.give_back(rec);
     return rc;
 }
 

@@ -35,7 +35,8 @@ namespace ltk {
     X(LIN_MP, 1)               /* 1: 1x1 / linear layers with K = 2560 / 5120 on lin_mp_kernel where its grid is one round of blocks; 2 / 3: always, that many slabs; 0: conv3 / rowconv */ \
     X(GN_COOP, 1)              /* 1: GroupNorm of the maps too large for MT_GN1 in ONE tensor pass (gn_coop_kernel); 0: gn_stats + gn_apply */ \
     X(AUDIO0, 3)               /* bit 0: audio_encoder.0 as a VALU kernel reading the float32 mel windows (audio0_kernel); bit 1: audio_encoder.3 on audio3_kernel; 0: pack_mel + conv_mfma_kernel */ \
-    X(CONV_S2D, 1)             /* 1: face_encoder_blocks.1.0 / 2.0 (shallow stride-2 layers) on convs2d_kernel; 0: conv_mfma_kernel (first generation) */
+    X(CONV_S2D, 1)             /* 1: face_encoder_blocks.1.0 / 2.0 (shallow stride-2 layers) on convs2d_kernel; 0: conv_mfma_kernel (first generation) */ \
+    X(DEFER, 1)                /* 1: a solo ltk_wav2lip_infer_deferred call returns with its pass in flight, once the pass before it is complete; 0: every call waits for its own */
 
 // Notes.
 // GRAPH       the per-call pointer tables live in device memory, filled by one small launch in front of the graph.
@@ -62,6 +63,8 @@ namespace ltk {
 //             bit 1: the stride-(3, 1) layer on MFMAs fed straight from global memory.
 // CONV_S2D    16 -> 32 @256^2, 32 -> 64 @128^2 (conv7_mfma.hip): a wave = one output row x 32 output channels, weights in registers,
 //             pixel operands straight from global memory, no LDS.
+// DEFER       engine_internal.h infer_call / defer_window.h: a lone session's host turn-around (completion wake-up, Python, the next
+//             call's launches: 40-55 us of a 1.2-ms step) then runs under the pass in flight instead of between two passes.
 
 enum Knob {
 #define LTK_KNOB_ENUM(name, dflt) K_##name,

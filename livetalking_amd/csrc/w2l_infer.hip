@@ -139,7 +139,30 @@ int ltk_avatar_face_cache_bytes(ltk_engine* e, int avatar_id, size_t* bytes) {
     return LTK_OK;
 }
 
-int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream) {
+}  // extern "C"
+
+// ltk_wav2lip_infer (dc == nullptr) and ltk_wav2lip_infer_deferred.  A call that fails before it enqueues anything still drains the
+// window: after an error return nothing is in flight (include/ltk.h).
+static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream, DeferCall* dc);
+static int w2l_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream, DeferCall* dc) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    // a knob changed since the pass in flight was enqueued (tests, tuners): plans and graphs are rebuilt behind a drained engine
+    if (e->defer_epoch.load(std::memory_order_relaxed) != knob_epoch() && e->defer.newest()) {
+        CHK(enter_device(e->device));
+        const int drc = drain_pending(e);
+        if (drc) return drc;
+    }
+    const int rc = w2l_infer_checked(e, reqs, nreq, stream, dc);
+    if (rc && e->defer.newest()) {
+        const std::string msg = g_err;
+        (void)hipSetDevice(e->device);
+        (void)drain_pending(e);
+        return fail(rc, msg);
+    }
+    return rc;
+}
+
+static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream, DeferCall* dc) {
     if (!e || !reqs || nreq <= 0) return fail(LTK_E_INVALID, "bad arguments");
     if (!e->loaded) return fail(LTK_E_STATE, "ltk_wav2lip_load has not been called");
     static const bool timing = getenv("LTK_INFER_TIMING") != nullptr;
@@ -195,6 +218,8 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
         // (it was a hit, or it starts where a recent solo call of the same avatar and size ended) - prefetches the next call's in turn
         const bool solo = nreq == 1 && !cached && knob(K_PREFETCH) && e->alt_frames > 0 && total <= std::min(e->alt_frames, mbs) &&
                           !e->capture && knob(K_HEAD_FUSED) && e->c7;
+        // knob DEFER: a solo call that was asked to may return with its pass in flight
+        const bool defer = solo && dc && dc->want && knob(K_DEFER) != 0;
         const int first = reqs[0].index;
         int slot = 0;
         if (solo)
@@ -238,21 +263,26 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
             // slots the surplus sessions simply run whole passes instead of evicting each other.
             constexpr double kPfStale = 1.5;
             const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-            int victim = 0, busy = 0;
+            PfSlotView view[ltk_engine::kPfSlots + 1];
+            const unsigned long long in_flight = e->defer.slots_in_use();
             for (int k = 1; k <= ltk_engine::kPfSlots; ++k) {
-                if (k == slot) continue;
                 const ltk_engine::PfSlot& sl = e->pfs[k];
-                if (sl.valid && now - sl.filled_at < kPfStale) continue;
+                view[k].valid = sl.valid;
+                view[k].age = now - sl.filled_at;
+                view[k].stamp = sl.stamp;
                 // ... and among the free ones the MOST recently used: a lone session then alternates between two slots (five graphs: captured
                 // within its first six calls) instead of walking all sixteen (33 graphs, each launch variant run eagerly once and captured
                 // once: the first ~35 calls of a session - all of a 20-step benchmark run - paid for captures, 4.5 % on its timed line)
                 // (... whose last reader is done: with calls of several sessions in flight the most recently consumed slot may still be read by
                 // another session's pass, and a prefetch into it would wait for that pass instead of running beside it)
-                if (sl.read && hipEventQuery(sl.ev_read) != hipSuccess) { if (!busy || sl.stamp > e->pfs[busy].stamp) busy = k; continue; }
-                if (!victim || sl.stamp > e->pfs[victim].stamp) victim = k;
+                // (knob DEFER: the pass the previous call left in flight works in its slot whether or not the query already says so - the
+                // lone session's walk over three slots, and with it the set of captured graphs, does not depend on host timing;
+                // defer_window.h choose_prefetch_slot is the rule, checked on the CPU)
+                view[k].reader_running = k != slot && !(sl.valid && view[k].age < kPfStale) &&
+                                         (((in_flight >> k) & 1) || (sl.read && hipEventQuery(sl.ev_read) != hipSuccess));
             }
             (void)hipGetLastError();          // hipEventQuery's hipErrorNotReady is not an error
-            if (!victim) victim = busy;
+            const int victim = choose_prefetch_slot(view, ltk_engine::kPfSlots, slot, kPfStale);
             if (victim) {
             ltk_engine::PfSlot& sl = e->pfs[victim];
             sl.valid = false;
@@ -260,6 +290,9 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
             const Avatar& a = *hold[0];
             for (int i = 0; i < total; ++i) nx.p[i] = a.d_face + (size_t)mirror_index(a.n, first + total + i) * 256 * 256 * 3;
             sl.hold = hold[0];                  // (a previous prefetch into this slot is behind us on aux2: its bank may go now)
+            // (knob DEFER: the host runs one pass ahead of the device, so this encoder starts as soon as its slot's last reader - two passes
+            // back - is done, beside the pass in flight; gating it on that pass's end instead measured 7-17 us per step slower,
+            // profiles/defer_ab.txt)
             launch_upload_tables(&nx, nullptr, nullptr, total, e->d_tab_next, e->aux2);
             // a prefetch that cannot be launched does not fail the call: this call's pass is already enqueued and complete without it (returning
             // an error here would hand the caller an error while the pass still writes its frames); the session's next call misses and runs whole
@@ -283,15 +316,54 @@ int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* st
             seq_rec->avatar = reqs[0].avatar; seq_rec->next = first + total; seq_rec->nf = total; seq_rec->stamp = ++e->pf_clock;
         }
         if (timing) tp3 = std::chrono::steady_clock::now();
+        if (!rc && defer) {
+            dc->ok = true;
+            dc->slot = slot;
+            for (auto& ap : hold) dc->hold.push_back(ap);
+            dc->ranges.push_back({(const unsigned char*)reqs[0].d_pred, (size_t)total * 65536 * 3});
+            e->defer_epoch.store(knob_epoch(), std::memory_order_relaxed);
+        }
         return rc;
-    });
+    }, dc);
     if (timing) {
         const auto tp4 = std::chrono::steady_clock::now();
         auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         std::lock_guard<std::mutex> g(e->pool_mu);
-        e->tm_prep += us(tp0, tp1); e->tm_launch += us(tp1, tp2); e->tm_pf += us(tp2, tp3); e->tm_wait += us(tp3, tp4); ++e->tm_calls;
+        const double prev = dc ? dc->wait_prev_us : 0.0;
+        e->tm_prep += us(tp0, tp1); e->tm_launch += us(tp1, tp2); e->tm_pf += us(tp2, tp3); e->tm_wait += us(tp3, tp4) - prev; e->tm_prev += prev; ++e->tm_calls;
     }
     return rc;
+}
+
+extern "C" {
+
+int ltk_wav2lip_infer(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream) { return w2l_infer(e, reqs, nreq, stream, nullptr); }
+
+int ltk_wav2lip_infer_deferred(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, void* stream, int flags, int* deferred) {
+    if (deferred) *deferred = 0;
+    if (flags & ~LTK_DEFER_SYNC) return fail(LTK_E_INVALID, "unknown flags");
+    DeferCall dc;
+    dc.want = !(flags & LTK_DEFER_SYNC);
+    const int rc = w2l_infer(e, reqs, nreq, stream, &dc);
+    if (!rc && deferred) *deferred = dc.deferred ? 1 : 0;
+    return rc;
+}
+
+int ltk_wav2lip_order_stream(ltk_engine* e, const void* d_pred, size_t bytes, void* stream) {
+    if (!e || !d_pred || !bytes) return fail(LTK_E_INVALID, "bad arguments");
+    if (e->defer.writers_of(d_pred, bytes).empty()) return LTK_OK;      // the frames are complete: nothing to wait for
+    CHK(enter_device(e->device));
+    CHK(order_behind_pending(e, (hipStream_t)stream, d_pred, bytes));
+    return LTK_OK;
+}
+
+int ltk_wav2lip_defer_stats(ltk_engine* e, unsigned long long* deferred, unsigned long long* max_outstanding, unsigned long long* outstanding) {
+    if (!e) return fail(LTK_E_INVALID, "engine is null");
+    const DeferStats st = e->defer.stats();
+    if (deferred) *deferred = st.deferred;
+    if (max_outstanding) *max_outstanding = st.max_outstanding;
+    if (outstanding) *outstanding = st.outstanding;
+    return LTK_OK;
 }
 
 }  // extern "C"

@@ -307,7 +307,8 @@ namespace ltk {
 // Everything ltk_wav2lip_load creates (layer plans, head weights, first-layer plan, activation arena): a failed load leaves
 // the engine as it found it, and can be retried.
 void wav2lip_unload(ltk_engine* e) {
-    if (e->aux2) (void)hipStreamSynchronize(e->aux2);        // an outstanding prefetch writes buffers that go away below
+    (void)drain_pending(e);                                  // knob DEFER: a pass still in flight works in the buffers that go away below
+    if (e->aux2) (void)hipStreamSynchronize(e->aux2);        // an outstanding prefetch writes them too
     e->graphs.drop();
     if (e->d_tab) { (void)hipFree(e->d_tab); e->d_tab = nullptr; }
     for (Layer& L : e->layers) {

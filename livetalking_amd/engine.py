@@ -8,6 +8,7 @@ host - there is no cross-GPU traffic.
 from __future__ import annotations
 
 import ctypes as C
+import sys
 import threading
 from typing import Dict, Optional, Sequence
 
@@ -42,6 +43,9 @@ class Engine:
         self._closed = False
         self._lock = threading.Lock()
         self._egress_open = set()       # egress sessions still open: closed with the engine
+        # True: single-request wav2lip_infer calls may return with their pass in flight (knob DEFER).  Set by a caller whose frame
+        # readers all go through this engine (paste_back*, egress_*) or through order_frames - the wav2lip plugin's handles do
+        self.defer_handles = False
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -158,7 +162,36 @@ class Engine:
             arr[i].batch = int(batch)
             arr[i].d_mel = C.c_void_p(mel_ptr)
             arr[i].d_pred = C.c_void_p(pred_ptr)
+        if len(reqs) == 1 and self.defer_handles:
+            # a lone request may return with its pass in flight (knob DEFER, include/ltk.h: ltk_wav2lip_infer_deferred; the engine
+            # decides).  The engine's own consumers (paste_back*, egress_*) order themselves behind that pass; every other reader of
+            # the frames goes through order_frames first - which is what `defer_handles` promises
+            deferred = C.c_int(0)
+            _lib.check(self._lib.ltk_wav2lip_infer_deferred(self._h, arr, 1, C.c_void_p(stream), 0, C.byref(deferred)))
+            return bool(deferred.value)          # True: the frames' pass is in flight, the caller wraps / orders its readers
         _lib.check(self._lib.ltk_wav2lip_infer(self._h, arr, len(reqs), C.c_void_p(stream)))
+        return False
+
+    def current_stream(self) -> int:
+        """torch's current stream on this engine's GPU as a handle (0 = the default stream, also without torch)."""
+        torch = sys.modules.get("torch")
+        return int(torch.cuda.current_stream(self.device).cuda_stream) if torch is not None else 0
+
+    def order_frames(self, d_pred_ptr: int, nbytes: int, stream: Optional[int] = None):
+        """Makes `stream` (default: torch's current stream on this engine's GPU; 0 = the default stream) wait, on the GPU, for the
+        deferred pass that writes [d_pred_ptr, d_pred_ptr + nbytes), if one is in flight.  No host wait.  The wait is issued when
+        the frames are READ instead of with every call: a wait given to torch's stream at every call sat in a hardware queue for the
+        length of every pass and cost more than the deferral gains (profiles/defer_ab.txt)."""
+        if stream is None:
+            stream = self.current_stream()
+        _lib.check(self._lib.ltk_wav2lip_order_stream(self._h, C.c_void_p(d_pred_ptr), int(nbytes), C.c_void_p(stream)))
+
+    def defer_stats(self) -> dict:
+        """Knob DEFER (include/ltk.h): calls that returned with their pass outstanding / the most passes outstanding at such a return /
+        passes outstanding now."""
+        d, m, o = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+        _lib.check(self._lib.ltk_wav2lip_defer_stats(self._h, C.byref(d), C.byref(m), C.byref(o)))
+        return {"deferred": int(d.value), "max_outstanding": int(m.value), "outstanding": int(o.value)}
 
     def paste_back(self, avatar_id: int, idx: int, d_pred_ptr: int, out: np.ndarray, stream: int = 0):
         """out: C-contiguous uint8 (H,W,3) host array, filled in place."""

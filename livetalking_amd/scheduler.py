@@ -32,12 +32,13 @@ import time
 
 
 class _Req:
-    __slots__ = ("args", "batch", "done", "err")
+    __slots__ = ("args", "batch", "done", "err", "deferred")
 
     def __init__(self, args, batch):
         self.args, self.batch = args, batch
         self.done = threading.Event()
         self.err = None
+        self.deferred = False            # the engine call that carried it (alone) returned with its pass in flight
 
 
 class BatchingScheduler:
@@ -82,7 +83,8 @@ class BatchingScheduler:
         return int(lim) if lim else 1 << 30
 
     def infer(self, aid, index, batch, in_ptr, out_ptr):
-        """Blocks until this request's frames are ready.  Raises what the engine raised for the call that carried it."""
+        """Blocks until this request's frames are ready - or, returning True, until its pass is enqueued behind a completed one (a lone
+        wav2lip session under knob DEFER: Engine.wav2lip_infer).  Raises what the engine raised for the call that carried it."""
         batch = int(batch)
         with self._cv:
             # A lone session (nothing in flight, nothing queued, no window to hold, no multi-request batch lately): the call goes straight
@@ -117,14 +119,16 @@ class BatchingScheduler:
         r.done.wait()
         if r.err is not None:
             raise r.err
+        return r.deferred
 
     def _run_solo(self, args, frames):
         """One request, one call, in the caller's thread; holds the in-flight slot infer() took.  Sessions that arrive meanwhile queue
         up as usual (they see a call in flight) and the workers issue their batch - behind this call, or when it ends."""
         t0 = time.perf_counter()
         err = None
+        deferred = False
         try:
-            self._call([args])
+            deferred = self._call([args])
         except Exception as ex:  # noqa: BLE001
             err = ex
         t1 = time.perf_counter()
@@ -147,6 +151,7 @@ class BatchingScheduler:
                 self._cv.notify_all()
         if err is not None:
             raise err
+        return bool(deferred)
 
     def _ensure_workers(self):
         """Under the lock."""
@@ -186,7 +191,9 @@ class BatchingScheduler:
         errs = [None] * len(group)
         if group:
             try:
-                self._call([q.args for q in group])
+                res = self._call([q.args for q in group])
+                if len(group) == 1:
+                    group[0].deferred = bool(res)
             except Exception as ex:  # noqa: BLE001
                 if len(group) == 1:
                     errs[0] = ex
@@ -196,7 +203,7 @@ class BatchingScheduler:
                     # call before it launches anything, so the requests are re-issued one by one and only the offender raises.
                     for i, q in enumerate(group):
                         try:
-                            self._call([q.args])
+                            q.deferred = bool(self._call([q.args]))
                         except Exception as ex_i:  # noqa: BLE001
                             errs[i] = ex_i
         t1 = time.perf_counter()
