@@ -507,7 +507,12 @@ int ltk_conv2d_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
  *                  weight as the Wav2Lip program builds them
  * `rep` (may be NULL): family as asked; conv3: kernel = the instantiation's name as ltk_debug_conv3_variants spells it, its template
  * arguments G, NBT, PXW, NC8, T, S, the effective split factor, the work items and the grid; rowgemm / rowconv / rowconvT: kernel and
- * the instantiation's FT / UB; kernel = "" where another kernel served the layer. */
+ * the instantiation's FT / UB.  The first-generation kernel (csrc/conv_mfma.hip, every family-0 layer conv3 does not take): kernel =
+ * "conv_mfma_kernel<NC8,NBT,TT9,MAXA>" as ltk_debug_conv1_variants spells it (TT9 true / false), NC8, NBT (the effective one, after the
+ * rule that keeps a launch at 512 blocks), T = the taps per chunk (padded to even at NC8 = 1), S = the column stride, items = grid = the
+ * blocks, and the tile: l2w / l2h = log2 of its width / height in output pixels, NB = its images, s2half = the column-parity pitch of the
+ * patch rows (0: plain rows), phases = sub-pixel phases of the launch (4 for the transposed conv), lds = its dynamic LDS bytes, args_hash =
+ * 31 bits of an FNV-1a hash over the kernel's scalar arguments (everything but the pointers); 0 for every other kernel. */
 typedef struct ltk_conv_opts {
     int x_ld, x_coff, y_ld, y_coff, res_ld, res_coff;
     int act, ups;
@@ -517,6 +522,7 @@ typedef struct ltk_conv_opts {
 typedef struct ltk_conv_report {
     char kernel[64];
     int family, G, NBT, PXW, NC8, T, S, ksplit, items, grid, FT, UB;
+    int l2w, l2h, NB, s2half, phases, lds, args_hash;
 } ltk_conv_report;
 int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin,
                       const float* weight, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
@@ -524,8 +530,8 @@ int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int C
                       const void* d_res, int relu, void* d_y, const ltk_conv_opts* opts, ltk_conv_report* rep);
 
 /* What ltk_conv2d_f16_ex decides about the same call before it allocates or enqueues anything, on the host alone (no engine, no GPU):
- * the option and view checks, the plan's route (conv_route), conv3's launch plan (conv3_plan_launch) with the split-K scratch taken as
- * unbounded, the row families' shape checks.  `has_res`: a residual would be passed.  `rep` as above.  Refusals that only a launcher
+ * the option and view checks, the plan's route (conv_route), the launch plan (conv3_plan_launch with the split-K scratch taken as
+ * unbounded, or the first-generation kernel's conv1_plan_launch), the row families' shape checks.  `has_res`: a residual would be passed.  `rep` as above.  Refusals that only a launcher
  * makes (more rows or frames than a row kernel is built for) are not seen here. */
 int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                         int transposed, int out_pad, int has_res, int relu, const ltk_conv_opts* opts, ltk_conv_report* rep);
@@ -533,6 +539,27 @@ int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, 
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */
 int ltk_debug_conv3_variants(char* buf, int cap);
+
+/* ... and of every instantiation of the first-generation kernel its picker can return (csrc/conv_mfma.hip: the table pick_kernel is
+ * made of), the same way. */
+int ltk_debug_conv1_variants(char* buf, int cap);
+
+/* The special-case kernels at the head of the Wav2Lip program (csrc/conv7_mfma.hip) on their own, for kernel unit tests: the op's plan
+ * from torch-layout fp32 weights and the folded scale / shift (host fp32, one per output channel), its existing launch on the compute
+ * stream, synchronised.  All ops end in ReLU.
+ *   CONV7_BANK    Conv2d(6, 16, 7, 1, 3) with the input pack fused: frame i is frame_ptrs[i], device uint8 [256][256][3]; the operand is
+ *                 fp16(fp32(byte) * fp32(1 / 255)) = {b, g, r with rows >= 128 zero, b, g, r, 0, 0}; y = 16 channels at 256 x 256
+ *   CONV7_PACKED  the same layer from d_x = fp16 [N][256][256][8], the packed operand itself
+ *   AUDIO0        Conv2d(1, 32, 3, 1, 1): frame i is frame_ptrs[i], device fp32 [80][16], rounded to fp16; y = 32 channels at 80 x 16
+ *   AUDIO3        Conv2d(32, 64, 3, (3, 1), 1): d_x = CB16 of 32 channels at 80 x 16; y = 64 channels at 27 x 16
+ *   CONVS2D       Conv2d(Cin, Cout, 3, 2, 1), Cin 16 or 32, Cout % 32 == 0: d_x = CB16 of Cin channels at H x W (H even, W % 64 == 0);
+ *                 y = Cout channels at H/2 x W/2
+ * frame_ptrs: HOST array of N device pointers (BANK, AUDIO0; any order, repeats allowed - the hook uploads it as the launch's FacePtrs /
+ * MelPtrs table, as the bank gather does); d_x: the other ops' input.  H, W, Cin, Cout: CONVS2D only.  `opts`: y (and x of AUDIO3 /
+ * CONVS2D) are channels [coff, coff + C) of a channel-blocked buffer of `ld` channels; ld = 0: contiguous.  What the launchers and plans
+ * refuse - more than 256 frames, a view that is no multiple of 16 channels, odd H, W % 64 != 0, another Cin - comes back as
+ * LTK_E_INVALID with their message. */
+enum { LTK_W2L_CONV7_BANK = 0, LTK_W2L_CONV7_PACKED = 1, LTK_W2L_AUDIO0 = 2, LTK_W2L_AUDIO3 = 3, LTK_W2L_CONVS2D = 4 };
 
 /* Standalone GroupNorm (+ SiLU) over a channel-blocked fp16 tensor, for kernel unit tests and timing (diffusers GroupNorm as the MuseTalk U-Net / VAE
  * use it; `avatars/musetalk/models/unet.py:36-46`, `vae.py:96-108` call sites).  x, y: device fp16 [N][C/16][P][16]; gamma / beta host fp32 [C];
@@ -558,6 +585,10 @@ typedef struct ltk_norm_report {
 } ltk_norm_report;
 int ltk_groupnorm_f16_ex(ltk_engine* e, const void* d_x, int N, int C, int P, int groups, float eps, const float* gamma, const float* beta,
                          int silu, int impl, int out_fp8, float out_scale, void* d_y, const ltk_norm_opts* opts, ltk_norm_report* rep);
+
+/* (the LTK_W2L_* ops above) */
+int ltk_w2l_head_f16(ltk_engine* e, int op, const void* const* frame_ptrs, const void* d_x, int N, int H, int W, int Cin, int Cout,
+                     const float* weight, const float* scale, const float* shift, void* d_y, const ltk_norm_opts* opts);
 
 /* The pointwise and layout kernels of csrc/nn_kernels.hip on their own (kernel unit tests): the existing launch, on the compute stream,
  * synchronised.  N images of P pixels / tokens and C channels; `opts` as above (views of 16-channel blocks; x_* unused where x is fp32).

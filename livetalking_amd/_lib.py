@@ -48,7 +48,7 @@ class ConvOpts(C.Structure):
 
 class ConvReport(C.Structure):
     _fields_ = [("kernel", C.c_char * 64)] + [(n, C.c_int) for n in ("family", "G", "NBT", "PXW", "NC8", "T", "S", "ksplit", "items", "grid",
-                                                                     "FT", "UB")]
+                                                                     "FT", "UB", "l2w", "l2h", "NB", "s2half", "phases", "lds", "args_hash")]
 
 
 class NormOpts(C.Structure):
@@ -153,6 +153,9 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
     "ltk_debug_conv_plan": (C.c_int, [C.c_int] * 15 + [C.POINTER(ConvOpts), C.POINTER(ConvReport)]),
     "ltk_debug_conv3_variants": (C.c_int, [C.c_char_p, C.c_int]),
+    "ltk_debug_conv1_variants": (C.c_int, [C.c_char_p, C.c_int]),
+    "ltk_w2l_head_f16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(NormOpts)]),
     "ltk_groupnorm_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_float, C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "ltk_groupnorm_f16_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

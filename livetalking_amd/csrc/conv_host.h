@@ -41,6 +41,10 @@ struct PhaseMeta {
 constexpr int kMaxBItems = 9;   // 16-byte weight items a thread stages per chunk
 // whether the first-generation kernel has an instantiation for this plan configuration at all (conv_route)
 bool conv1_has_kernel(int NC8, int NBT, bool tt9);
+// conv1_launch = conv1_plan_launch (pure: checks, tile and its shrink loop, effective NBT, kernel, grid, LDS bytes, s2half, KArgs geometry,
+// report; no HIP call, no device pointer dereferenced) + the enqueue.  `k1` may be null when only the verdict and the report are wanted.
+struct K1Launch;
+int conv1_plan_launch(const ConvPlan& p, const ConvIO& io, K1Launch* k1, std::string* err);
 int conv1_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err);
 
 }  // namespace ltk

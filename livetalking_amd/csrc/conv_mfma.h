@@ -2,7 +2,8 @@
 // (CB16: [N][C/16][H][W][16]; network inputs of <= 8 channels are [N][H][W][8]).  Host-side plan + launch interface: conv_plan.hip
 // builds a plan in steps (conv_route decides, the rest packs and uploads) and dispatches a launch to conv_mfma.hip (register-staged
 // first-generation kernel, conv1_launch) or conv3_mfma.hip (LDS-DMA kernel: conv3_plan_launch decides, conv3_launch enqueues);
-// DESIGN.md §2-3.  conv_route and conv3_plan_launch are pure: the CPU suite holds them to tests/conv_cases.py through ltk_debug_conv_plan.
+// DESIGN.md §2-3.  conv_route, conv3_plan_launch and conv1_plan_launch are pure: the CPU suite holds them to tests/conv_cases.py and
+// tests/conv1_cases.py through ltk_debug_conv_plan.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -113,10 +114,16 @@ void conv_plan_destroy(ConvPlan* p);
 struct ConvReport {
     char kernel[64];
     int G, NBT, PXW, NC8, T, S, ksplit, items, grid;
+    // the first-generation kernel (conv1_plan_launch: kernel = conv_mfma_kernel<NC8,NBT,TT9,MAXA> as conv1_variant_names() spells it, NBT the
+    // effective one, T = Tp, S = sw, items = grid = blocks): the tile's log2 width / height, its images, KArgs::s2half, the phases, the LDS bytes,
+    // and 31 bits of an FNV-1a hash over the kernel's scalar arguments
+    int l2w, l2h, NB, s2half, phases, lds, args_hash;
 };
 // every fp16 instantiation conv3_plan_launch's pickers can return, one name per line (conv3_mfma.hip: the table the pickers are made of)
 std::string conv3_variant_names();
-// ... and every fp8 one (e4m3 MFMA, Q = 1, and MX-scaled, Q = 2), spelled conv3_kernel<1,NBT,PXW,NC8,9,1,Q>: the tables k3_pick_q8 / k3_pick_mx are made of
+// every instantiation the first-generation picker can return (conv_mfma.hip: the table pick_kernel is made of)
+std::string conv1_variant_names();
+// ... and every fp8 conv3 one (e4m3 MFMA, Q = 1, and MX-scaled, Q = 2), spelled conv3_kernel<1,NBT,PXW,NC8,9,1,Q>: the tables k3_pick_q8 / k3_pick_mx are made of
 std::string conv3_fp8_variant_names();
 
 struct ConvIO {
@@ -145,8 +152,8 @@ struct ConvIO {
 
 // Enqueue the layer on `stream`.  Returns 0 or a negative error (message in *err).
 int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err);
-// conv_launch up to the point where it would touch the device: conv3's planner (its report through io.report), or what the
-// first-generation path refuses before it looks at the tile.  Pure.
+// conv_launch up to the point where it would touch the device: conv3's planner or the first-generation one (conv1_plan_launch), their
+// report through io.report.  Pure.
 int conv_launch_dry(const ConvPlan& p, const ConvIO& io, std::string* err);
 
 // conv3_mfma.hip: conv3_launch = conv3_plan_launch (pure: checks, tile, split, kernel, grid, LDS bytes, K3Args geometry, report; no

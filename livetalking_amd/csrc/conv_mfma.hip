@@ -1,7 +1,8 @@
 // Implicit-GEMM fp16 convolution for gfx950 (CDNA4) on MFMA, first generation (register-staged); activations are
 // channel-blocked CB16 ([N][C/16][H][W][16]), inputs of <= 8 channels [N][H][W][8].  Today it runs the 7x7, the
 // shallow strided 3x3 and the valid-padding layers; conv3_mfma.hip runs the rest.  This file holds the kernel, its picker and its
-// launcher (conv1_launch, what conv_launch calls for a plan that is not conv3's); plans are built in conv_plan.hip.
+// launcher (conv1_launch = conv1_plan_launch, pure, + the enqueue; what conv_launch calls for a plan that is not conv3's); plans are
+// built in conv_plan.hip.
 //
 // Replaces the torch.nn.Conv2d / ConvTranspose2d + BatchNorm2d(eval) + residual
 // + ReLU blocks of the reference generator (avatars/wav2lip/models/conv.py:5-44,
@@ -31,6 +32,8 @@
 #include "tune.h"
 
 #include <hip/hip_fp16.h>
+#include <stddef.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -361,37 +364,66 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const KArgs a) {
 
 typedef void (*conv_kernel_t)(const KArgs);
 
-// `need` = 16-byte A items per thread this launch stages; returns the smallest instantiation that holds them.
-// A launch runs blocks of at most 64 output channels (NBT <= 2, conv1_launch).
-static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int need) {
-#define KERNEL(nc8, nbt, maxa) (tt9 ? (conv_kernel_t)conv_mfma_kernel<nc8, nbt, true, maxa> : (conv_kernel_t)conv_mfma_kernel<nc8, nbt, false, maxa>)
-    if (NC8 == 1) return (NBT == 1 && need <= 5) ? (conv_kernel_t)conv_mfma_kernel<1, 1, false, 5> : nullptr;
-    if (NC8 == 4 && need <= 6) {
-        if (NBT == 1) return KERNEL(4, 1, 6);
-        if (NBT == 2) return KERNEL(4, 2, 6);
-    }
-    if (NC8 == 2 && need <= 3) {
-        if (NBT == 1) return KERNEL(2, 1, 3);
-        if (NBT == 2) return KERNEL(2, 2, 3);
-    }
-    if (NC8 == 2 && need <= 10) {
-        if (NBT == 1) return KERNEL(2, 1, 10);
-        if (NBT == 2) return KERNEL(2, 2, 10);
-    }
-#undef KERNEL
+// THE table of instantiations, X(NC8, NBT, TT9, MAXA), per (NC8, NBT, TT9) in ascending MAXA: pick_kernel and conv1_variant_names()
+// (what a test has to see launched, ltk_debug_conv1_variants) are both made of it.  A launch runs blocks of at most 64 output channels
+// (NBT <= 2, conv1_plan_launch).
+#define K1_VARIANTS(X) \
+    X(1, 1, false, 5) \
+    X(4, 1, true, 6) X(4, 1, false, 6) X(4, 2, true, 6) X(4, 2, false, 6) \
+    X(2, 1, true, 3) X(2, 1, false, 3) X(2, 2, true, 3) X(2, 2, false, 3) \
+    X(2, 1, true, 10) X(2, 1, false, 10) X(2, 2, true, 10) X(2, 2, false, 10)
+
+// `need` = 16-byte A items per thread this launch stages; returns the smallest instantiation that holds them (*maxa = its MAXA).
+static conv_kernel_t pick_kernel(int NC8, int NBT, bool tt9, int need, int* maxa = nullptr) {
+#define K1CASE(nc8, nbt, t9, ma) \
+    if (NC8 == nc8 && NBT == nbt && tt9 == t9 && need <= ma) { if (maxa) *maxa = ma; return (conv_kernel_t)conv_mfma_kernel<nc8, nbt, t9, ma>; }
+    K1_VARIANTS(K1CASE)
+#undef K1CASE
     return nullptr;
+}
+
+static std::string k1_name(int NC8, int NBT, bool tt9, int maxa) {
+    char b[64];
+    snprintf(b, sizeof(b), "conv_mfma_kernel<%d,%d,%s,%d>", NC8, NBT, tt9 ? "true" : "false", maxa);
+    return b;
+}
+
+std::string conv1_variant_names() {
+    std::string out;
+#define K1NAME(nc8, nbt, t9, ma) out += k1_name(nc8, nbt, t9, ma) + "\n";
+    K1_VARIANTS(K1NAME)
+#undef K1NAME
+    return out;
 }
 
 bool conv1_has_kernel(int NC8, int NBT, bool tt9) { return pick_kernel(NC8, NBT, tt9, 1) != nullptr; }
 
-int conv1_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
+// What conv1_plan_launch decides: the instantiation, the grid, the dynamic LDS and KArgs with everything but the pointers
+// (conv1_launch fills those from the plan and the ConvIO)
+struct K1Launch {
+    conv_kernel_t kernel;
+    unsigned grid;
+    size_t lds;
     KArgs a;
+};
+
+// FNV-1a over every KArgs field behind the pointers (which the planner leaves null): one number a test can hold a launch's arguments to
+static unsigned kargs_hash(const KArgs& a) {
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(&a);
+    unsigned h = 2166136261u;
+    for (size_t i = offsetof(KArgs, N); i < sizeof(KArgs); ++i) h = (h ^ b[i]) * 16777619u;
+    return h;
+}
+
+int conv1_plan_launch(const ConvPlan& p, const ConvIO& io, K1Launch* k1, std::string* err) {
+    K1Launch local;
+    K1Launch& L = k1 ? *k1 : local;
+    if (io.ups) { if (err) *err = "input upsampling is a conv3 feature (3x3 s1 p1 / 1x1 layers)"; return -1; }
+    KArgs& a = L.a;
     memset(&a, 0, sizeof(a));
     const int NC8 = p.NC8;
     int HoA, WoA;
     p.out_dims(io.H, io.W, &HoA, &WoA);
-    a.x = io.x; a.w = p.d_w; a.scale = p.d_scale; a.shift = p.d_shift; a.res = io.res; a.y = io.y;
-    a.phases = reinterpret_cast<const PhaseMeta*>((const char*)p.d_w + (p.w_bytes + 15) / 16 * 16);
     a.N = io.N; a.H = io.H; a.W = io.W; a.x_cbt = io.x_ld >> 4; a.x_cb0 = io.x_coff >> 4;
     a.res_cbt = io.res_ld >> 4; a.res_cb0 = io.res_coff >> 4;
     a.Cin8 = p.Cin / 8;
@@ -466,12 +498,31 @@ int conv1_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::s
     if ((double)io.N * io.H * io.W * io.x_ld >= 2147483647.0) { if (err) *err = "input tensor too large for 32-bit offsets"; return -1; }
 
     const int need = (npix * NC8 + 255) / 256;
-    conv_kernel_t k = pick_kernel(NC8, NBT, p.tt9, need);
+    int maxa = 0;
+    conv_kernel_t k = pick_kernel(NC8, NBT, p.tt9, need, &maxa);
     if (!k) { if (err) *err = "no kernel instantiation for this launch"; return -1; }
     const long long nblk = (long long)p.nphase * a.tiles_n * a.tiles_y * a.tiles_x * a.n_ntiles;
     if (nblk <= 0 || nblk > 0x7fffffffll) { if (err) *err = "bad grid"; return -1; }
-    HIPCHK((hipError_t)ensure_dyn_lds((const void*)k, kLdsLimit));
-    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(256), lds, stream, a);
+    L.kernel = k; L.grid = (unsigned)nblk; L.lds = lds;
+    if (io.report) {
+        ConvReport& r = *io.report;
+        r = ConvReport();
+        snprintf(r.kernel, sizeof(r.kernel), "%s", k1_name(NC8, NBT, p.tt9, maxa).c_str());
+        r.NC8 = NC8; r.NBT = NBT; r.T = p.Tp; r.S = a.sw; r.items = (int)nblk; r.grid = (int)nblk;
+        r.l2w = l2w; r.l2h = l2h; r.NB = NB; r.s2half = a.s2half; r.phases = p.nphase; r.lds = (int)lds;
+        r.args_hash = (int)(kargs_hash(a) & 0x7fffffffu);
+    }
+    return 0;
+}
+
+int conv1_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
+    K1Launch L;
+    if (const int rc = conv1_plan_launch(p, io, &L, err)) return rc;
+    KArgs& a = L.a;
+    a.x = io.x; a.w = p.d_w; a.scale = p.d_scale; a.shift = p.d_shift; a.res = io.res; a.y = io.y;
+    a.phases = reinterpret_cast<const PhaseMeta*>((const char*)p.d_w + (p.w_bytes + 15) / 16 * 16);
+    HIPCHK((hipError_t)ensure_dyn_lds((const void*)L.kernel, kLdsLimit));
+    hipLaunchKernelGGL(L.kernel, dim3(L.grid), dim3(256), L.lds, stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }

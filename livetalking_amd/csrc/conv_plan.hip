@@ -400,20 +400,12 @@ void conv_plan_destroy(ConvPlan* p) {
 
 // launch dispatch
 
-// what the first-generation path refuses before it looks at the tile
-static int conv1_refuses(const ConvIO& io, std::string* err) {
-    if (io.ups) { if (err) *err = "input upsampling is a conv3 feature (3x3 s1 p1 / 1x1 layers)"; return -1; }
-    return 0;
-}
-
 int conv_launch(const ConvPlan& p, const ConvIO& io, hipStream_t stream, std::string* err) {
-    if (p.v3) return conv3_launch(p, io, stream, err);
-    if (const int rc = conv1_refuses(io, err)) return rc;
-    return conv1_launch(p, io, stream, err);
+    return p.v3 ? conv3_launch(p, io, stream, err) : conv1_launch(p, io, stream, err);
 }
 
 int conv_launch_dry(const ConvPlan& p, const ConvIO& io, std::string* err) {
-    return p.v3 ? conv3_plan_launch(p, io, nullptr, err) : conv1_refuses(io, err);
+    return p.v3 ? conv3_plan_launch(p, io, nullptr, err) : conv1_plan_launch(p, io, nullptr, err);
 }
 
 }  // namespace ltk

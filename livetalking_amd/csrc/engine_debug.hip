@@ -280,10 +280,11 @@ void conv_report_copy(const ConvReport& cr, ltk_conv_report* rep) {
     memcpy(rep->kernel, cr.kernel, sizeof(rep->kernel));
     rep->G = cr.G; rep->NBT = cr.NBT; rep->PXW = cr.PXW; rep->NC8 = cr.NC8; rep->T = cr.T; rep->S = cr.S;
     rep->ksplit = cr.ksplit; rep->items = cr.items; rep->grid = cr.grid;
+    rep->l2w = cr.l2w; rep->l2h = cr.l2h; rep->NB = cr.NB; rep->s2half = cr.s2half; rep->phases = cr.phases; rep->lds = cr.lds; rep->args_hash = cr.args_hash;
 }
 
 // Everything ltk_conv2d_f16_ex / ltk_conv2d_fp8_ex decide before they allocate or enqueue, on the host alone: the options and the
-// channel views; family 0: conv_route and, for a conv3 plan, conv3_plan_launch with the split-K scratch taken as unbounded; the row
+// channel views; family 0: conv_route and the launch planner (conv3_plan_launch with the split-K scratch taken as unbounded, or conv1_plan_launch); the row
 // families: their shape refusals.  `quant`: 0 fp16 operands, 1 e4m3, 2 MX - x and its view then count fp8 channels (32 per block) and
 // reach the launch in 16-bit units, as mt_graph.hip halves them.  *rep (may be NULL) = what a launch of this call reports.
 int conv_hook_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int transposed, int out_pad, bool has_res,
@@ -450,6 +451,75 @@ int ltk_debug_conv3_variants(char* buf, int cap) {
     const std::string names = conv3_variant_names();
     if (!buf || cap <= (int)names.size()) return fail(LTK_E_INVALID, "buffer too small: " + std::to_string(names.size() + 1) + " bytes needed");
     memcpy(buf, names.c_str(), names.size() + 1);
+    return LTK_OK;
+}
+
+int ltk_debug_conv1_variants(char* buf, int cap) {
+    const std::string names = conv1_variant_names();
+    if (!buf || cap <= (int)names.size()) return fail(LTK_E_INVALID, "buffer too small: " + std::to_string(names.size() + 1) + " bytes needed");
+    memcpy(buf, names.c_str(), names.size() + 1);
+    return LTK_OK;
+}
+
+namespace {
+// plans of ltk_w2l_head_f16, freed on every return path
+struct HeadPlansOwner {
+    Conv7Plan* c7 = nullptr; Audio0Plan* a0 = nullptr; Audio3Plan* a3 = nullptr; ConvS2dPlan* s2 = nullptr;
+    ~HeadPlansOwner() { conv7_plan_destroy(c7); audio0_plan_destroy(a0); audio3_plan_destroy(a3); convs2d_plan_destroy(s2); }
+};
+}  // namespace
+
+int ltk_w2l_head_f16(ltk_engine* e, int op, const void* const* frame_ptrs, const void* d_x, int N, int H, int W, int Cin, int Cout,
+                     const float* weight, const float* scale, const float* shift, void* d_y, const ltk_norm_opts* opts) {
+    if (!e || !weight || !scale || !shift || !d_y || !opts || N <= 0 || op < LTK_W2L_CONV7_BANK || op > LTK_W2L_CONVS2D)
+        return fail(LTK_E_INVALID, "bad arguments");
+    const bool table = op == LTK_W2L_CONV7_BANK || op == LTK_W2L_AUDIO0;       // the per-frame inputs come through a pointer table
+    if (table ? !frame_ptrs : !d_x) return fail(LTK_E_INVALID, "bad arguments");
+    // the layers' own channel counts; CONVS2D's are the caller's (its plan refuses what it has no kernel for)
+    const int Ci = op == LTK_W2L_CONVS2D ? Cin : op == LTK_W2L_AUDIO3 ? 32 : 0;
+    const int Co = op == LTK_W2L_CONVS2D ? Cout : op == LTK_W2L_AUDIO3 ? 64 : op == LTK_W2L_AUDIO0 ? 32 : 16;
+    if (Ci < 0 || Co <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const bool x_view = op == LTK_W2L_AUDIO3 || op == LTK_W2L_CONVS2D;
+    const int x_ld = opts->x_ld ? opts->x_ld : Ci, y_ld = opts->y_ld ? opts->y_ld : Co;
+    if (!x_view && (opts->x_ld || opts->x_coff)) return fail(LTK_E_INVALID, "this op's input is no channel-blocked tensor: no view of x");
+    if (opts->x_coff < 0 || opts->y_coff < 0 || (x_view && opts->x_coff + Ci > x_ld) || opts->y_coff + Co > y_ld)
+        return fail(LTK_E_INVALID, "channel view outside its buffer");
+    CHK(enter_device(e->device));
+    { const int drc = drain_pending(e); if (drc) return drc; }
+    std::string err;
+    HeadPlansOwner po;
+    int rc = 0;
+    switch (op) {
+        case LTK_W2L_CONV7_BANK: case LTK_W2L_CONV7_PACKED: rc = conv7_plan_create(&po.c7, weight, scale, shift, &err); break;
+        case LTK_W2L_AUDIO0: rc = audio0_plan_create(&po.a0, weight, scale, shift, &err); break;
+        case LTK_W2L_AUDIO3: rc = audio3_plan_create(&po.a3, weight, scale, shift, &err); break;
+        default: rc = convs2d_plan_create(&po.s2, weight, Cin, Cout, scale, shift, &err); break;
+    }
+    if (rc) return conv_status(rc, err);
+    // the table as the bank gather builds it: entry i = frame i's input, any order, repeats allowed (entries past N, and past the
+    // table's capacity when the launcher is about to refuse N, stay null)
+    DevBuf d_tab;
+    if (table) {
+        FacePtrs fp;
+        memset(&fp, 0, sizeof(fp));
+        for (int i = 0; i < std::min(N, kPackMaxFrames); ++i) fp.p[i] = (const uint8_t*)frame_ptrs[i];
+        static_assert(sizeof(FacePtrs) == sizeof(MelPtrs), "one upload serves both tables");
+        const int urc = upload(&fp, sizeof(fp), &d_tab);
+        if (urc) return urc;
+    }
+    hipStream_t s = e->compute;
+    std::lock_guard<std::mutex> g(e->mu);
+    int lrc = 0;
+    switch (op) {
+        case LTK_W2L_CONV7_BANK: lrc = conv7_launch(po.c7, (const FacePtrs*)d_tab.p, nullptr, N, (f16*)d_y, y_ld, opts->y_coff, s, &err); break;
+        case LTK_W2L_CONV7_PACKED: lrc = conv7_launch(po.c7, nullptr, (const f16*)d_x, N, (f16*)d_y, y_ld, opts->y_coff, s, &err); break;
+        case LTK_W2L_AUDIO0: lrc = audio0_launch(po.a0, (const MelPtrs*)d_tab.p, N, (f16*)d_y, y_ld, opts->y_coff, s, &err); break;
+        case LTK_W2L_AUDIO3: lrc = audio3_launch(po.a3, (const f16*)d_x, x_ld, opts->x_coff, N, (f16*)d_y, y_ld, opts->y_coff, s, &err); break;
+        default: lrc = convs2d_launch(po.s2, (const f16*)d_x, x_ld, opts->x_coff, N, H, W, (f16*)d_y, y_ld, opts->y_coff, s, &err); break;
+    }
+    const hipError_t he = hipStreamSynchronize(s);      // the launch's error wins; the stream is drained either way
+    if (lrc) return conv_status(lrc, err);
+    if (he != hipSuccess) return fail(LTK_E_HIP, std::string("w2l head kernel: ") + hipGetErrorString(he));
     return LTK_OK;
 }
 

@@ -736,6 +736,28 @@ class Engine:
         _lib.check(_lib.load().ltk_debug_conv3_variants(buf, len(buf)))
         return buf.value.decode().split()
 
+    @staticmethod
+    def conv1_variants() -> list:
+        """Names of every instantiation of the first-generation kernel its picker can return (ltk_debug_conv1_variants); no GPU needed."""
+        buf = C.create_string_buffer(8192)
+        _lib.check(_lib.load().ltk_debug_conv1_variants(buf, len(buf)))
+        return buf.value.decode().split()
+
+    W2L_HEAD_OPS = ("conv7_bank", "conv7_packed", "audio0", "audio3", "convs2d")
+
+    def w2l_head_f16(self, op: str, weight: np.ndarray, scale: np.ndarray, shift: np.ndarray, d_y_ptr: int, N: int, frame_ptrs=None,
+                     d_x_ptr: int = 0, H: int = 0, W: int = 0, Cin: int = 0, Cout: int = 0, **opts) -> None:
+        """One special-case kernel of csrc/conv7_mfma.hip on its own (include/ltk.h: ltk_w2l_head_f16); op: a name of W2L_HEAD_OPS;
+        frame_ptrs: N device pointers of the per-frame inputs (conv7_bank, audio0), d_x_ptr: the other ops' input; `opts` = the fields of
+        ltk_norm_opts."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        sc = np.ascontiguousarray(scale, dtype=np.float32)
+        sf = np.ascontiguousarray(shift, dtype=np.float32)
+        o = _lib.NormOpts(**{name: int(v) for name, v in opts.items()})
+        tab = (C.c_void_p * len(frame_ptrs))(*[int(p) for p in frame_ptrs]) if frame_ptrs is not None else None
+        _lib.check(self._lib.ltk_w2l_head_f16(self._h, self.W2L_HEAD_OPS.index(op), tab, C.c_void_p(d_x_ptr) if d_x_ptr else None, N, H, W, Cin, Cout,
+                                              w.ctypes.data, sc.ctypes.data, sf.ctypes.data, C.c_void_p(d_y_ptr), C.byref(o)))
+
     def conv2d_fp8_ex(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, Cout, scale: Optional[np.ndarray] = None,
                       shift: Optional[np.ndarray] = None, act_scale: float = 8.0, quant: int = 0, d_res_ptr: int = 0, d_y_ptr: int = 0,
                       **opts) -> dict:

@@ -495,8 +495,12 @@ def test_abi_argument_validation_without_gpu():
     assert lib.ltk_debug_conv3_fp8_variants(None, 0) == E_INVALID and b"buffer too small" in lib.ltk_last_error()
     small = C.create_string_buffer(8)
     assert lib.ltk_debug_conv3_fp8_variants(small, len(small)) == E_INVALID
-    # the fp8 hooks reuse ltk_conv_opts / ltk_conv_report as they are (include/ltk.h): 12 ints; char[64] + 12 ints
-    assert C.sizeof(_lib.ConvOpts) == 48 and C.sizeof(_lib.ConvReport) == 112
+    # the fp8 hooks reuse ltk_conv_opts / ltk_conv_report as they are (include/ltk.h): 12 ints; char[64] + 12 ints + the seven fields of the
+    # first-generation launch (l2w, l2h, NB, s2half, phases, lds, args_hash), behind everything that was there
+    assert C.sizeof(_lib.ConvOpts) == 48 and C.sizeof(_lib.ConvReport) == 140
+    assert _lib.ConvReport.UB.offset == 108 and _lib.ConvReport.l2w.offset == 112 and _lib.ConvReport.args_hash.offset == 136
+    assert lib.ltk_debug_conv1_variants(None, 0) == E_INVALID and b"buffer too small" in lib.ltk_last_error()
+    assert lib.ltk_w2l_head_f16(null, 0, null, null, 1, 0, 0, 0, 0, null, null, null, null, None) == E_INVALID and b"bad arguments" in lib.ltk_last_error()
     if not torch.cuda.is_available():
         h = C.c_void_p()
         rc = lib.ltk_engine_create(0, C.byref(h))
