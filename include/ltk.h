@@ -322,6 +322,20 @@ int ltk_hubert_features(ltk_engine* e, const float* pcm, long long n_samples, fl
  * first_row 2*(l/2) - 8, row_step 2).  Returns when d_out is complete. */
 int ltk_hubert_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out);
 
+/* The live steps of nreq concurrent sessions in one call (scheduler.py kind "hubert").  Every request is what ltk_hubert_step takes.
+ * Requests of one length are forwarded together, up to 16 clips per program run, so that the weights stream once for all of them;
+ * no clip's statistics, padding, attention or chunk clamp sees another clip.  Batched programs (16 clips of one length) live in a
+ * cache of their own, at most 2, least recently used dropped, and are built only while their activations at 16 clips stay under
+ * 2 GiB; a request alone at its length, or of a longer length, runs as ltk_hubert_step does, and nreq == 1 IS ltk_hubert_step.
+ * All requests are validated before the first launch (LTK_E_INVALID names the request); returns when every d_out is complete; an
+ * error return leaves nothing in flight. */
+typedef struct ltk_hubert_req {
+    const float* pcm; int n_samples;              /* host, 400 <= n_samples < 320000 */
+    int batch, first_row, row_step, rows;         /* feature2chunks of this request */
+    void* d_out;                                  /* device float32 [batch][rows][1024] */
+} ltk_hubert_req;
+int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq);
+
 /* Avatar preparation: avatars/musetalk/models/vae.py:84-94,110-122 get_latents_for_unet, as
  * avatars/musetalk/genavatar.py:116-128 calls it.  vae_sd: the AutoencoderKL state_dict keys "encoder.*" and
  * "quant_conv.*" (fp32 host).  faces_bgr: host uint8 [nfaces][256][256][3] (the LANCZOS-resized crops);
@@ -340,6 +354,17 @@ int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_
 /* named tensor of the HuBERT program that ran last as [C][T] float32: an op name (ltk_hubert_op_name; an attention's output is
  * "<op>.attn"), or "input_values": the normalised waveform fp32 [n_samples] of that clip */
 int ltk_hubert_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats);
+/* ... of clip `clip` of the batched run (ltk_hubert_step_batch) that ran last: [C][T] float32, or "input_values" */
+int ltk_hubert_debug_get_clip(ltk_engine* e, const char* name, int clip, float* out, size_t n_floats);
+/* clips per batched program run, batched programs currently kept, activation bytes of the one that ran last at full capacity (any may
+ * be NULL) */
+int ltk_hubert_batch_info(ltk_engine* e, int* capacity, int* programs, size_t* activation_bytes);
+/* How ltk_hubert_step_batch cuts a call of nreq requests of n_samples[r] for a model of `layers` encoder layers, on the host alone (no
+ * engine, no GPU): run_of[r] / slot_of[r] = the run that carries request r and its place in it, run_batched[i] = 1 if run i is one
+ * batched program run (0: the single-clip path), runs in execution order, *n_runs of them (all arrays hold nreq entries);
+ * clip_bytes[r] (may be NULL) = activation bytes of one clip of that length. */
+int ltk_debug_hubert_batch_plan(const int* n_samples, int nreq, int layers, int* run_of, int* slot_of, int* run_batched, int* n_runs,
+                                size_t* clip_bytes);
 /* ops of a HuBERT program in execution order; type as ltk_musetalk_op_name, and 7 conv layer 0 + LayerNorm + GELU, 8 LayerNorm +
  * GELU, 9 positional conv */
 int ltk_hubert_op_count(ltk_engine* e);

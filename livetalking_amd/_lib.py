@@ -36,6 +36,11 @@ class UlReq(C.Structure):
     _fields_ = [("avatar", C.c_int), ("index", C.c_int), ("batch", C.c_int), ("d_feat", C.c_void_p), ("d_pred", C.c_void_p)]
 
 
+class HubertReq(C.Structure):
+    _fields_ = [("pcm", C.c_void_p), ("n_samples", C.c_int), ("batch", C.c_int), ("first_row", C.c_int), ("row_step", C.c_int),
+                ("rows", C.c_int), ("d_out", C.c_void_p)]
+
+
 class EgressReq(C.Structure):
     _fields_ = [("source", C.c_int), ("avatar", C.c_int), ("idx", C.c_int), ("d_pred", C.c_void_p), ("h_frame", C.c_void_p),
                 ("speaking", C.c_int), ("alpha", C.c_double), ("keep", C.c_int), ("format", C.c_int), ("chroma", C.c_int)]
@@ -112,7 +117,12 @@ SYMBOLS = {
     "ltk_hubert_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int]),
     "ltk_hubert_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ltk_hubert_step_batch": (C.c_int, [C.c_void_p, C.POINTER(HubertReq), C.c_int]),
     "ltk_hubert_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ltk_hubert_debug_get_clip": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ltk_hubert_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "ltk_debug_hubert_batch_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "ltk_ultralight_op_count": (C.c_int, [C.c_void_p, C.c_int]),
     "ltk_ultralight_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_op_count": (C.c_int, [C.c_void_p]),

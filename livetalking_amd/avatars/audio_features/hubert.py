@@ -25,6 +25,10 @@ import numpy as np
 from ...hostshim import BaseASR
 
 HUBERT_DIR = "./models/hubert-large-ls960-ft"      # avatars/ultralight/audio2feature.py:9-10
+# 1: the live steps of concurrent sessions go through the engine's "hubert" scheduler and share one forward per tick
+# (Engine.hubert_step_batch); 0: every step is its own hubert_step call.  Read once.
+_HUBERT_BATCH_DEFAULT = "1"
+_HUBERT_BATCH = os.environ.get("LTK_HUBERT_BATCH", _HUBERT_BATCH_DEFAULT) != "0"
 
 
 class Audio2Feature:
@@ -83,10 +87,15 @@ class EngineAudio2Feature:
 
     def step(self, pcm, batch, first_row, row_step=2, rows=16):
         """One forward of the step's pcm -> device float32 (batch, rows, 1024): frame i = rows [first_row + i * row_step, + rows),
-        index-clamped."""
+        index-clamped.  Steps of concurrent sessions on this engine share a forward (scheduler kind "hubert"); a lone session's
+        call goes straight down in its own thread."""
         import torch
         out = torch.empty((batch, rows, 1024), dtype=torch.float32, device=self.engine.torch_device)
-        self.engine.hubert_step(pcm, batch, first_row, out.data_ptr(), row_step=row_step, rows=rows)
+        if _HUBERT_BATCH:
+            from ...scheduler import get_scheduler
+            get_scheduler(self.engine, "hubert").submit((pcm, batch, first_row, row_step, rows, out.data_ptr()), 1)
+        else:
+            self.engine.hubert_step(pcm, batch, first_row, out.data_ptr(), row_step=row_step, rows=rows)
         return out
 
     def zeros(self, batch, rows):

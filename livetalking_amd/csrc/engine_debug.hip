@@ -951,6 +951,57 @@ int ltk_hubert_info(ltk_engine* e, int* layers, int* programs, size_t* activatio
     return LTK_OK;
 }
 
+int ltk_hubert_debug_get_clip(ltk_engine* e, const char* name, int clip, float* out, size_t n_floats) {
+    if (!e || !name || !out || clip < 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    if (!e->hubert_blast) return fail(LTK_E_STATE, "no batched HuBERT run yet");
+    if (clip >= e->hubert_blast_nf) return fail(LTK_E_INVALID, "the last batched run carried " + std::to_string(e->hubert_blast_nf) + " clips");
+    CHK(hipStreamSynchronize(e->compute));
+    if (std::string(name) == "input_values") {
+        size_t n = 0;
+        for (auto& p : e->hubert_bprogs) if (p.g == e->hubert_blast) n = (size_t)p.n_samples;
+        if (n != n_floats) return fail(LTK_E_INVALID, "size mismatch: the clip has " + std::to_string(n) + " samples");
+        CHK(hipMemcpy(out, mt_hubert_pcm_in(e->hubert_blast) + (size_t)clip * n, n * sizeof(float), hipMemcpyDeviceToHost));
+        return LTK_OK;
+    }
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->hubert_blast, name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no HuBERT tensor named ") + name);
+    const size_t cnt = (size_t)C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats per clip");
+    return read_cb16(e, t + (size_t)clip * ld * H * W, 1, C, ld, coff, H, W, out);
+}
+
+int ltk_hubert_batch_info(ltk_engine* e, int* capacity, int* programs, size_t* activation_bytes) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+    if (capacity) *capacity = kHubertBatchClips;
+    if (programs) *programs = (int)e->hubert_bprogs.size();
+    if (activation_bytes) {
+        *activation_bytes = 0;
+        for (auto& p : e->hubert_bprogs)
+            if (p.g == e->hubert_blast) *activation_bytes = hubert_clip_activation_bytes(p.n_samples, mt_hubert_layers(e->hubert_w)) * kHubertBatchClips;
+    }
+    return LTK_OK;
+}
+
+int ltk_debug_hubert_batch_plan(const int* n_samples, int nreq, int layers, int* run_of, int* slot_of, int* run_batched, int* n_runs,
+                                size_t* clip_bytes) {
+    if (!n_samples || nreq <= 0 || layers <= 0 || !run_of || !slot_of || !run_batched || !n_runs) return fail(LTK_E_INVALID, "bad arguments");
+    const std::vector<HubertRun> runs = hubert_batch_plan(n_samples, nreq, layers);
+    for (size_t i = 0; i < runs.size(); ++i) {
+        run_batched[i] = runs[i].batched ? 1 : 0;
+        for (size_t j = 0; j < runs[i].req.size(); ++j) { run_of[runs[i].req[j]] = (int)i; slot_of[runs[i].req[j]] = (int)j; }
+    }
+    *n_runs = (int)runs.size();
+    if (clip_bytes)
+        for (int r = 0; r < nreq; ++r) clip_bytes[r] = hubert_clip_activation_bytes(n_samples[r], layers);
+    return LTK_OK;
+}
+
 int ltk_hubert_stats(ltk_engine* e, const float* pcm, long long n, float* mean_var) {
     if (!e || !pcm || !mean_var || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
     CHK(enter_device(e->device));

@@ -317,9 +317,17 @@ struct ltk_engine {
     unsigned long hubert_clock = 0;
     float* d_hpcm = nullptr;              // staging: the whole utterance, fp32
     size_t hpcm_cap = 0;                  // samples
-    float* d_hstats = nullptr;            // [2] mean, variance
+    float* d_hstats = nullptr;            // [2] mean, variance, then [1] the residual of the stored mean (hubert_kernels.h)
     float* d_hrows = nullptr;             // staging: fp32 rows of one clip on their way to the host
     size_t hrows_cap = 0;                 // rows
+    // ltk_hubert_step_batch: programs for up to kHubertBatchClips clips of one length, a cache of their own (at most
+    // kHubertBatchPrograms, least recently used dropped; ltk_hubert_info does not count them), with their own staging
+    std::vector<HubertProg> hubert_bprogs;
+    MtGraph* hubert_blast = nullptr;      // the batched program that ran last, and how many clips it carried (debug read-back)
+    int hubert_blast_nf = 0;
+    float* d_hbpcm = nullptr;             // staging: fp32 [nf][n_samples] of one run
+    size_t hbpcm_cap = 0;                 // samples
+    float* d_hbstats = nullptr;           // [kHubertBatchClips][2] mean, variance per clip, then [kHubertBatchClips] residuals of the means
     // ultralight: per-avatar programs over ONE activation arena of ul_frames frames (grown by a register call that asks for more)
     std::map<int, std::shared_ptr<UlAvatar>> ul_avatars;
     f16* ul_buf[kUlBufs] = {nullptr};
@@ -608,6 +616,7 @@ double ul_macs_per_frame(const UlAvatar& a);
 void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
 void ul_unload(ltk_engine* e);                         // engine teardown
 constexpr size_t kHubertPrograms = 3;
+constexpr size_t kHubertBatchPrograms = 2;
 MtGraph* hubert_program(ltk_engine* e, int n_samples, int* rc);                                             // mt_engine.hip, under e->mu
 void hubert_unload(ltk_engine* e);
 int mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat_ptrs, int nf, const OutList64* outs, float* d_image_f32);

@@ -18,8 +18,11 @@
 // feature-extractor maps and 25 MB per encoder layer, 0.79 GB at 24 layers.
 #include <math.h>
 
+#include <algorithm>
+
 #include "mt_graph.h"
 #include "hubert_kernels.h"
+#include "nn_kernels.h"
 
 namespace ltk {
 
@@ -169,10 +172,60 @@ int mt_build_hubert(MtGraph& g, const ltk_named_tensor* t, int n, int n_samples)
 int mt_build_hubert_weights(MtGraph* g, const ltk_named_tensor* sd, int n) {
     return mt_build_hubert(*g, sd, n, kHbProtoSamples);           // packs every layer; no activations: this graph is never run
 }
-int mt_build_hubert_program(MtGraph* g, const MtGraph* weights, int n_samples) {
+int mt_build_hubert_program(MtGraph* g, const MtGraph* weights, int n_samples, int frames) {
     g->share = weights;
     if (mt_build_hubert(*g, nullptr, 0, n_samples)) return -1;
-    return mt_graph_alloc(*g, 1);
+    return mt_graph_alloc(*g, frames);
+}
+
+// mt_build_hubert's buffer list: the waveform, layer 0's map, conv + LayerNorm map of layers 1-6, the projection's two, the positional
+// conv's, nine maps per encoder layer (eight of 1024 channels, the FFN's 4096), the final LayerNorm, the attention's transposed values
+size_t hubert_clip_activation_bytes(int n_samples, int layers) {
+    size_t len[7];
+    long long tt = n_samples;
+    for (int i = 0; i < 7; ++i) {
+        if (tt < kHbConvK[i]) return 0;
+        tt = (tt - kHbConvK[i]) / kHbConvS[i] + 1;
+        len[i] = (size_t)tt;
+    }
+    const size_t T = len[6];
+    size_t halfs = (size_t)n_samples * 2 + (size_t)kHbC * len[0];
+    for (int i = 1; i < 7; ++i) halfs += 2 * (size_t)kHbC * len[i];
+    halfs += (size_t)kHbC * T + 2 * (size_t)kHbD * T;
+    halfs += (size_t)layers * (8 * (size_t)kHbD + kHbFF) * T;
+    halfs += (size_t)kHbD * T;
+    halfs += (size_t)kHbHeads * attn_dv32(kHbD / kHbHeads) * attn_tkp((int)T);
+    return halfs * sizeof(f16);
+}
+
+std::vector<HubertRun> hubert_batch_plan(const int* n_samples, int nreq, int layers) {
+    std::vector<HubertRun> runs;
+    std::vector<char> taken((size_t)std::max(nreq, 0), 0);
+    for (int r = 0; r < nreq; ++r) {
+        if (taken[r]) continue;
+        std::vector<int> group;
+        for (int q = r; q < nreq; ++q)
+            if (!taken[q] && n_samples[q] == n_samples[r]) { group.push_back(q); taken[q] = 1; }
+        const size_t clip = hubert_clip_activation_bytes(n_samples[r], layers);
+        const bool fits = clip > 0 && clip * kHubertBatchClips < kHubertBatchBudget;
+        for (size_t i0 = 0; i0 < group.size(); i0 += kHubertBatchClips) {
+            const size_t m = std::min(group.size() - i0, (size_t)kHubertBatchClips);
+            if (fits && m > 1) {
+                HubertRun run;
+                run.n_samples = n_samples[r]; run.batched = true;
+                run.req.assign(group.begin() + i0, group.begin() + i0 + m);
+                runs.push_back(run);
+            } else {
+                for (size_t i = i0; i < i0 + m; ++i) {
+                    HubertRun run;
+                    run.n_samples = n_samples[r];
+                    run.req.push_back(group[i]);
+                    runs.push_back(run);
+                }
+            }
+        }
+    }
+    return runs;
 }
 int mt_hubert_layers(const MtGraph* g) { return g->hb_layers; }
 int mt_hubert_rows(const MtGraph* g) { return g->hb_rows; }

@@ -229,15 +229,17 @@ int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, 
 // ================================================================================ HuBERT-large audio features (Ultralight)
 // The program for clips of n_samples, built on first use over the engine's packed weights; at most kHubertPrograms are kept.  A dropped
 // program takes its captured graph with it (the graph holds its buffers' addresses, and the next program may land on the same one).
-MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
+namespace {
+// `cache` = e->hubert_progs (single clips, `frames` 1) or e->hubert_bprogs (batched runs, kHubertBatchClips)
+MtGraph* hubert_cached_program(ltk_engine* e, std::vector<ltk_engine::HubertProg>& cache, size_t cap, int n_samples, int frames, int* rc) {
     *rc = LTK_OK;
-    for (auto& p : e->hubert_progs)
+    for (auto& p : cache)
         if (p.n_samples == n_samples) { p.stamp = ++e->hubert_clock; return p.g; }
-    if (e->hubert_progs.size() >= kHubertPrograms) {
+    if (cache.size() >= cap) {
         size_t v = 0;
-        for (size_t i = 1; i < e->hubert_progs.size(); ++i)
-            if (e->hubert_progs[i].stamp < e->hubert_progs[v].stamp) v = i;
-        MtGraph* old = e->hubert_progs[v].g;
+        for (size_t i = 1; i < cache.size(); ++i)
+            if (cache[i].stamp < cache[v].stamp) v = i;
+        MtGraph* old = cache[v].g;
         (void)hipStreamSynchronize(e->compute);
         for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
             if (it->first.first != (const void*)old) { ++it; continue; }
@@ -245,12 +247,13 @@ MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
             it = e->prog_graphs.graphs.erase(it);
         }
         if (e->hubert_last == old) e->hubert_last = nullptr;
+        if (e->hubert_blast == old) { e->hubert_blast = nullptr; e->hubert_blast_nf = 0; }
         mt_graph_delete(old);
-        e->hubert_progs.erase(e->hubert_progs.begin() + v);
+        cache.erase(cache.begin() + v);
     }
     MtGraph* g = mt_graph_new();
     mt_set_sat_counter(g, e->d_sat);
-    const int brc = mt_build_hubert_program(g, e->hubert_w, n_samples);
+    const int brc = mt_build_hubert_program(g, e->hubert_w, n_samples, frames);
     if (brc) {
         *rc = fail(brc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, std::string("hubert: ") + mt_graph_error(g));
         mt_graph_delete(g);
@@ -258,14 +261,24 @@ MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
     }
     ltk_engine::HubertProg p;
     p.g = g; p.n_samples = n_samples; p.stamp = ++e->hubert_clock;
-    e->hubert_progs.push_back(p);
+    cache.push_back(p);
     return g;
+}
+}  // namespace
+
+MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
+    return hubert_cached_program(e, e->hubert_progs, kHubertPrograms, n_samples, 1, rc);
 }
 
 void ltk::hubert_unload(ltk_engine* e) {
     for (auto& p : e->hubert_progs) mt_graph_delete(p.g);
     e->hubert_progs.clear();
     e->hubert_last = nullptr;
+    for (auto& p : e->hubert_bprogs) mt_graph_delete(p.g);
+    e->hubert_bprogs.clear();
+    e->hubert_blast = nullptr; e->hubert_blast_nf = 0;
+    if (e->d_hbpcm) { (void)hipFree(e->d_hbpcm); e->d_hbpcm = nullptr; e->hbpcm_cap = 0; }
+    if (e->d_hbstats) { (void)hipFree(e->d_hbstats); e->d_hbstats = nullptr; }
     if (e->hubert_w) { mt_graph_delete(e->hubert_w); e->hubert_w = nullptr; }
     if (e->d_hpcm) { (void)hipFree(e->d_hpcm); e->d_hpcm = nullptr; e->hpcm_cap = 0; }
     if (e->d_hstats) { (void)hipFree(e->d_hstats); e->d_hstats = nullptr; }
@@ -287,7 +300,7 @@ int hubert_upload(ltk_engine* e, const float* pcm, long long n, hipStream_t s) {
         e->hpcm_cap = cap;
     }
     CHK(hipMemcpyAsync(e->d_hpcm, pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-    launch_hubert_stats(e->d_hpcm, n, e->d_hstats, s);
+    launch_hubert_stats_n(e->d_hpcm, n, 1, e->d_hstats, e->d_hstats + 2, s);
     return LTK_OK;
 }
 
@@ -296,7 +309,7 @@ int hubert_forward(ltk_engine* e, long long off, int len, MtGraph** prog) {
     int rc;
     MtGraph* g = hubert_program(e, len, &rc);
     if (!g) return rc;
-    launch_hubert_normalise(e->d_hpcm + off, len, e->d_hstats, mt_hubert_pcm_in(g), e->compute);
+    launch_hubert_normalise_n(e->d_hpcm + off, len, 1, e->d_hstats, e->d_hstats + 2, mt_hubert_pcm_in(g), e->compute);
     rc = run_program(e, g, 1);
     if (rc) return conv_status(rc, std::string("hubert: ") + mt_graph_error(g));
     e->hubert_last = g;
@@ -319,7 +332,7 @@ int ltk_hubert_load(ltk_engine* e, const ltk_named_tensor* sd, int n) {
         mt_graph_delete(wg);
         return fail(LTK_E_INVALID, "hubert: " + msg);
     }
-    if (!e->d_hstats && hipMalloc((void**)&e->d_hstats, 2 * sizeof(float)) != hipSuccess) {
+    if (!e->d_hstats && hipMalloc((void**)&e->d_hstats, 3 * sizeof(float)) != hipSuccess) {
         mt_graph_delete(wg);
         return fail(LTK_E_NOMEM, "hubert: hipMalloc failed");
     }
@@ -396,6 +409,70 @@ int ltk_hubert_step(ltk_engine* e, const float* pcm, int n_samples, int batch, i
         int cbt, cb0;
         const f16* h = mt_hubert_out(prog, &cbt, &cb0);
         launch_hubert_chunks(h, cb0, mt_hubert_rows(prog), batch, first_row, row_step, rows, (float*)d_out, s);
+        if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "hubert kernels failed to launch");
+        return LTK_OK;
+    });
+}
+
+// N concurrent live steps in one call.  hubert_batch_plan cuts the call; a batched run uploads its clips into [nf][n] staging, takes
+// each clip's statistics in a block of its own, and forwards them as the nf images of ONE program run (captured per (program, nf)
+// as every program, run_program), so that the 0.63 GB of weights stream once for all of them; every request then gathers its own
+// chunks from its own image.  Runs of one request, and lengths past the budget, take ltk_hubert_step's path one by one.
+int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq) {
+    if (!reqs || nreq <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    for (int r = 0; r < nreq; ++r)          // every request before the first launch: a refused call has touched nothing
+        if (!reqs[r].pcm || !reqs[r].d_out || reqs[r].n_samples < kHubertKernel || reqs[r].n_samples >= kHubertClip || reqs[r].batch <= 0 ||
+            reqs[r].rows <= 0)
+            return fail(LTK_E_INVALID, "bad request " + std::to_string(r) + " (400 <= n_samples < 320000, batch and rows positive)");
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    if (nreq == 1)
+        return ltk_hubert_step(e, reqs[0].pcm, reqs[0].n_samples, reqs[0].batch, reqs[0].first_row, reqs[0].row_step, reqs[0].rows, reqs[0].d_out);
+    CHK(enter_device(e->device));
+    return infer_call(e, nullptr, [&]() -> int {
+        if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
+        hipStream_t s = e->compute;
+        std::vector<int> ns(nreq);
+        for (int r = 0; r < nreq; ++r) ns[r] = reqs[r].n_samples;
+        int cbt, cb0;
+        for (const HubertRun& run : hubert_batch_plan(ns.data(), nreq, mt_hubert_layers(e->hubert_w))) {
+            const int n = run.n_samples;
+            if (!run.batched) {
+                const ltk_hubert_req& q = reqs[run.req[0]];
+                int rc = hubert_upload(e, q.pcm, n, s);
+                if (rc) return rc;
+                MtGraph* prog = nullptr;
+                rc = hubert_forward(e, 0, n, &prog);
+                if (rc) return rc;
+                const f16* h = mt_hubert_out(prog, &cbt, &cb0);
+                launch_hubert_chunks(h, cb0, mt_hubert_rows(prog), q.batch, q.first_row, q.row_step, q.rows, (float*)q.d_out, s);
+                continue;
+            }
+            const int nf = (int)run.req.size();
+            if ((size_t)nf * n > e->hbpcm_cap) {
+                CHK(hipStreamSynchronize(s));
+                if (e->d_hbpcm) (void)hipFree(e->d_hbpcm);
+                e->d_hbpcm = nullptr; e->hbpcm_cap = 0;
+                const size_t cap = (size_t)kHubertBatchClips * n;
+                CHK(hipMalloc((void**)&e->d_hbpcm, cap * sizeof(float)));
+                e->hbpcm_cap = cap;
+            }
+            if (!e->d_hbstats) CHK(hipMalloc((void**)&e->d_hbstats, (size_t)kHubertBatchClips * 3 * sizeof(float)));
+            for (int i = 0; i < nf; ++i)
+                CHK(hipMemcpyAsync(e->d_hbpcm + (size_t)i * n, reqs[run.req[i]].pcm, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+            launch_hubert_stats_n(e->d_hbpcm, n, nf, e->d_hbstats, e->d_hbstats + 2 * kHubertBatchClips, s);
+            int rc;
+            MtGraph* g = hubert_cached_program(e, e->hubert_bprogs, kHubertBatchPrograms, n, kHubertBatchClips, &rc);
+            if (!g) return rc;
+            launch_hubert_normalise_n(e->d_hbpcm, n, nf, e->d_hbstats, e->d_hbstats + 2 * kHubertBatchClips, mt_hubert_pcm_in(g), s);
+            rc = run_program(e, g, nf);
+            if (rc) return conv_status(rc, std::string("hubert: ") + mt_graph_error(g));
+            e->hubert_blast = g; e->hubert_blast_nf = nf;
+            const f16* h = mt_hubert_out(g, &cbt, &cb0);
+            for (int i = 0; i < nf; ++i) {
+                const ltk_hubert_req& q = reqs[run.req[i]];
+                launch_hubert_chunks_img(h, i, cbt, cb0, mt_hubert_rows(g), q.batch, q.first_row, q.row_step, q.rows, (float*)q.d_out, s);
+            }
+        }
         if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "hubert kernels failed to launch");
         return LTK_OK;
     });

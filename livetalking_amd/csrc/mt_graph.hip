@@ -344,16 +344,16 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
             launch_add_pos(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.P(), g.vecs[op.gamma], s);
             break;
         case OP_HB_L0:
-            launch_hubert_layer0(reinterpret_cast<const float*>(g.bufs[g.hb_pcm_buf]), g.hb_samples, g.vecs[op.wvec], g.vecs[op.bvec],
-                                 g.vecs[op.gamma], g.vecs[op.beta], op.eps, g.bufs[op.y.buf], s);
+            launch_hubert_layer0_n(reinterpret_cast<const float*>(g.bufs[g.hb_pcm_buf]), g.hb_samples, nf, g.vecs[op.wvec], g.vecs[op.bvec],
+                                   g.vecs[op.gamma], g.vecs[op.beta], op.eps, g.bufs[op.y.buf], op.y.ld / 16, s);
             break;
         case OP_LNGELU:
-            launch_ln_gelu512(g.bufs[op.x.buf], op.x.coff / 16, op.x.P(), op.eps, g.vecs[op.gamma], g.vecs[op.beta], g.bufs[op.y.buf],
-                              op.y.coff / 16, s);
+            launch_ln_gelu512_n(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.P(), op.eps, g.vecs[op.gamma], g.vecs[op.beta],
+                                g.bufs[op.y.buf], op.y.ld / 16, op.y.coff / 16, s);
             break;
         case OP_POSCONV:
-            launch_hubert_posconv(g.bufs[op.x.buf], op.x.coff / 16, op.x.P(), reinterpret_cast<const f16*>(g.vecs[op.wvec]), g.vecs[op.bvec],
-                                  g.bufs[op.y.buf], op.y.coff / 16, s);
+            launch_hubert_posconv_n(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.P(), reinterpret_cast<const f16*>(g.vecs[op.wvec]),
+                                    g.vecs[op.bvec], g.bufs[op.y.buf], op.y.ld / 16, op.y.coff / 16, s);
             break;
         case OP_GEGLU:
             launch_geglu(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.y.C, op.x.P(), g.bufs[op.y.buf], op.y.ld / 16,

@@ -52,7 +52,19 @@ f16* mt_whisper_state(MtGraph* g, int i, int* cbt, int* cb0);
 // CB16 [64][rows][16].
 int hubert_rows(int n_samples);                 // rows HubertModel returns for a clip of n_samples (0: shorter than the receptive field)
 int mt_build_hubert_weights(MtGraph* g, const ltk_named_tensor* sd, int n);
-int mt_build_hubert_program(MtGraph* g, const MtGraph* weights, int n_samples);
+// a program for up to `frames` clips of n_samples each (images of one run; the waveform of clip i at i * n_samples floats of
+// mt_hubert_pcm_in(), its rows in image i of every tensor)
+int mt_build_hubert_program(MtGraph* g, const MtGraph* weights, int n_samples, int frames = 1);
+// Batched live steps (ltk_hubert_step_batch).  Activation bytes of ONE clip of a program, from the clip length and the depth alone -
+// the builder's buffer list restated, so that a call can be planned before anything is built or allocated.
+size_t hubert_clip_activation_bytes(int n_samples, int layers);
+constexpr int kHubertBatchClips = 16;                    // 16 x 51 = 816 rows: every linear layer of a live-length batch stays on the weight-streaming row kernel
+constexpr size_t kHubertBatchBudget = (size_t)2 << 30;   // a batched program is built only if its activations at full capacity stay under this
+// How a call of nreq requests is cut (pure host): requests grouped by n_samples in arrival order, every group cut into runs of at most
+// kHubertBatchClips; a run of one, or a length whose program at full capacity would pass the budget, goes to the single-clip path
+// (batched = false, one request per run).
+struct HubertRun { int n_samples = 0; bool batched = false; std::vector<int> req; };
+std::vector<HubertRun> hubert_batch_plan(const int* n_samples, int nreq, int layers);
 int mt_hubert_layers(const MtGraph* g);
 int mt_hubert_rows(const MtGraph* g);
 float* mt_hubert_pcm_in(MtGraph* g);

@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import LtkError, MtReq, NamedTensor, UlReq, W2lReq  # noqa: F401
+from ._lib import HubertReq, LtkError, MtReq, NamedTensor, UlReq, W2lReq  # noqa: F401
 
 
 def _as_f32(a) -> np.ndarray:
@@ -484,6 +484,31 @@ class Engine:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
         _lib.check(self._lib.ltk_hubert_step(self._h, pcm.ctypes.data, pcm.shape[0], int(batch), int(first_row), int(row_step), int(rows),
                                              C.c_void_p(d_out_ptr)))
+
+    def hubert_step_batch(self, reqs: Sequence[tuple]):
+        """The live steps of several sessions in one call: reqs = [(pcm, batch, first_row, row_step, rows, d_out_ptr)].  Clips of one
+        length share a program run of up to 16 (ltk_hubert_step_batch); one request is hubert_step."""
+        arr = (HubertReq * len(reqs))()
+        keep = []                                      # the pcm arrays stay alive across the call
+        for i, (pcm, batch, first_row, row_step, rows, d_out_ptr) in enumerate(reqs):
+            pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+            keep.append(pcm)
+            arr[i].pcm, arr[i].n_samples = pcm.ctypes.data, pcm.shape[0]
+            arr[i].batch, arr[i].first_row, arr[i].row_step, arr[i].rows = int(batch), int(first_row), int(row_step), int(rows)
+            arr[i].d_out = d_out_ptr
+        _lib.check(self._lib.ltk_hubert_step_batch(self._h, arr, len(reqs)))
+        del keep
+
+    def hubert_debug_get_clip(self, name: str, clip: int, shape) -> np.ndarray:
+        """A named tensor (or "input_values") of clip `clip` of the batched run that ran last."""
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.ltk_hubert_debug_get_clip(self._h, name.encode(), int(clip), out.ctypes.data, out.size))
+        return out
+
+    def hubert_batch_info(self) -> dict:
+        cap, progs, act = C.c_int(), C.c_int(), C.c_size_t()
+        _lib.check(self._lib.ltk_hubert_batch_info(self._h, C.byref(cap), C.byref(progs), C.byref(act)))
+        return {"capacity": cap.value, "programs": progs.value, "activation_bytes": act.value}
 
     def hubert_debug_get(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, dtype=np.float32)

@@ -21,7 +21,10 @@ scheduler batches them instead (continuous batching):
 
 A session's frames keep their order: a request is one contiguous (index .. index+batch) span, a session has at most
 one request in flight (its inference thread blocks in `infer()`), and every request's frames land in its own output
-tensor.  One scheduler per (engine, kind); kinds: "wav2lip" -> Engine.wav2lip_infer, "musetalk" -> Engine.musetalk_infer.
+tensor.  One scheduler per (engine, kind); kinds: "wav2lip" -> Engine.wav2lip_infer, "musetalk" -> Engine.musetalk_infer,
+"hubert" -> Engine.hubert_step_batch (the live HuBERT steps of concurrent Ultralight sessions: a request is
+(pcm, batch, first_row, row_step, rows, out_ptr), its size unit one clip, at most HUBERT_BATCH_CLIPS per engine call; it enters
+through `submit`).
 """
 from __future__ import annotations
 
@@ -29,6 +32,12 @@ import collections
 import os
 import threading
 import time
+
+
+# kind -> the engine method that takes a list of requests; resolved on first use (an engine need not have the methods of the kinds
+# it never serves)
+_ENGINE_CALL = {"wav2lip": "wav2lip_infer", "musetalk": "musetalk_infer", "hubert": "hubert_step_batch"}
+HUBERT_BATCH_CLIPS = 16          # csrc/musetalk.h kHubertBatchClips: clips per batched program run
 
 
 class _Req:
@@ -55,7 +64,9 @@ class BatchingScheduler:
     def __init__(self, engine, kind: str = "wav2lip", window_ms: float = 0.0, max_frames: int = 0):
         self.engine = engine
         self.kind = kind
-        self._call = engine.wav2lip_infer if kind == "wav2lip" else engine.musetalk_infer
+        if kind not in _ENGINE_CALL:
+            raise ValueError(f"unknown scheduler kind {kind!r}")
+        self._call_fn = None
         self.window = max(0.0, float(window_ms)) * 1e-3
         self._max_frames = int(max_frames)
         self._cv = threading.Condition()
@@ -76,16 +87,29 @@ class BatchingScheduler:
         self._last_multi = -1e9            # perf_counter() of the last batch that carried more than one request
         self.stats = {"calls": 0, "requests": 0, "frames": 0, "max_requests_per_call": 0, "overlapped_calls": 0}
 
+    def _call(self, reqs):
+        fn = self._call_fn
+        if fn is None:
+            fn = self._call_fn = getattr(self.engine, _ENGINE_CALL[self.kind])
+        return fn(reqs)
+
     def _limit(self) -> int:
         if self._max_frames > 0:
             return self._max_frames
+        if self.kind == "hubert":
+            return HUBERT_BATCH_CLIPS
         lim = getattr(self.engine, "max_frames" if self.kind == "wav2lip" else "mt_max_frames", 0)
         return int(lim) if lim else 1 << 30
 
     def infer(self, aid, index, batch, in_ptr, out_ptr):
         """Blocks until this request's frames are ready - or, returning True, until its pass is enqueued behind a completed one (a lone
         wav2lip session under knob DEFER: Engine.wav2lip_infer).  Raises what the engine raised for the call that carried it."""
-        batch = int(batch)
+        return self.submit((aid, index, int(batch), in_ptr, out_ptr), int(batch))
+
+    def submit(self, args, units):
+        """The generic entry: `args` is one request as the kind's engine method takes it, `units` its size in the kind's unit (frames;
+        clips for "hubert").  Same rules and return as infer()."""
+        batch = int(units)
         with self._cv:
             # A lone session (nothing in flight, nothing queued, no window to hold, no multi-request batch lately): the call goes straight
             # down in this thread with no request object, queue or event - the Python between two calls of a single session is time
@@ -98,8 +122,8 @@ class BatchingScheduler:
                 if self._spf is not None:
                     self._busy_until = time.perf_counter() + batch * self._spf
         if solo:
-            return self._run_solo((aid, index, batch, in_ptr, out_ptr), batch)
-        r = _Req((aid, index, batch, in_ptr, out_ptr), batch)
+            return self._run_solo(args, batch)
+        r = _Req(args, batch)
         with self._cv:
             self._pending.append(r)
             leader = self._inflight == 0 and len(self._pending) == 1
