@@ -222,6 +222,42 @@ typedef struct ltk_ul_req {
  * the second time and replayed afterwards (knob GRAPH, counted by ltk_program_graph_count). */
 int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* stream);
 
+/* What an ltk_ultralight_infer_merged call launched.  The arrays hold the first LTK_UL_MERGE_MAX_PASSES passes; n_passes, grouped
+ * and frames count all of them. */
+#define LTK_UL_MERGE_MAX_PASSES 64
+#define LTK_UL_PATH_PER_AVATAR 0 /* one avatar's program (the kernels and captured graph of ltk_ultralight_infer) */
+#define LTK_UL_PATH_GROUPED 1    /* the grouped program: every frame takes its own avatar's weights through a per-frame table */
+typedef struct ltk_ul_merge_report {
+    int n_passes;                          /* launch sequences the call ran */
+    int n_avatars;                         /* distinct avatars among its requests */
+    int grouped;                           /* passes on the grouped path */
+    int frames;                            /* frames over all passes */
+    int path[LTK_UL_MERGE_MAX_PASSES];     /* per pass: LTK_UL_PATH_* */
+    int nf[LTK_UL_MERGE_MAX_PASSES];       /* per pass: frames (<= the arena's) */
+    int avatar[LTK_UL_MERGE_MAX_PASSES];   /* per pass: its avatar, -1 on the grouped path */
+} ltk_ul_merge_report;
+
+/* ltk_ultralight_infer for the sessions of one scheduler tick, with the requests' passes MERGED: where ltk_ultralight_infer runs one
+ * launch sequence (86 launches) per request, this call runs one per pass of the plan below, each over up to the arena's frames.
+ * Same requests, same results per request (every request's frames land in its own d_pred, in its own order) and the same return
+ * contract: it returns when the frames are ready, an error return leaves nothing in flight.  EVERY request is validated before the
+ * first launch (LTK_E_INVALID names the request; an unknown avatar is LTK_E_STATE), so a caller that batched several sessions can
+ * re-issue them one by one and only the offender fails again.  The avatars are held until the call has synchronised.
+ * mode 0, the rule: requests of ONE avatar -> per-avatar passes over the union of their frames; of several avatars -> grouped passes
+ * over all frames in request order under knob UL_GROUPED (default off, profiles/ultralight_merge.txt), else each avatar's requests
+ * merged, avatars in order of first appearance.  mode 1 forces the per-avatar form, mode 2 the grouped form.  Frames keep request
+ * order inside a pass; a request is a contiguous span and is split only where a pass is full.  A call of one request runs exactly
+ * what ltk_ultralight_infer runs for it (same launches, same captured graph).  In a per-avatar pass every conv keeps, per frame, the
+ * split-K factor of the ltk_ultralight_infer pass that would have carried the frame, so a request's frames are byte-identical to its
+ * own call's whatever shares the pass (a few convs then take more than one launch where the requests' sizes differ; such a pass is
+ * captured per avatar and run lengths of those sizes).  A grouped pass is captured per frame count under a
+ * key of its own, holds no avatar's address and survives ltk_avatar_release.  rep (or NULL): what was launched. */
+int ltk_ultralight_infer_merged(ltk_engine* e, const ltk_ul_req* reqs, int nreq, int mode, void* stream, ltk_ul_merge_report* rep);
+
+/* The Ultralight arena: frames per pass (0: no avatar registered yet), its bytes, the bytes one frame takes, and whether the grouped
+ * path is part of this build.  Any pointer may be NULL. */
+int ltk_ultralight_info(ltk_engine* e, int* arena_frames, size_t* arena_bytes, size_t* bytes_per_frame, int* grouped);
+
 /* avatars/ultralight_avatar.py:173-184 LightReal.paste_back_frame: the 168x168 bank face with the prediction written at
  * [4:164, 4:164], bilinear-resized (cv2.resize INTER_LINEAR semantics) to the frame's box and pasted into a copy of full_bank[idx].
  * d_pred: device uint8 [160][160][3].  out: uint8 [H][W][3], device or host as ltk_paste_back. */
@@ -430,6 +466,14 @@ int ltk_dwconv3x3_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C
 int ltk_upsample2x_cat_f16(ltk_engine* e, const void* d_x, int N, int h, int w, int C_up, const void* d_skip, int Hs, int Ws, int C_skip,
                            void* d_y);
 
+/* The call plan of ltk_ultralight_infer_merged on the host alone (no engine, no GPU): requests (avatar[r], batch[r]), the arena's
+ * frames `cap`, the mode, whether the grouped path is available, and knob UL_GROUPED (0 / 1; -1: the process's knob).  Out: per pass
+ * its path, avatar (-1 grouped) and frames; per span (in pass order) its pass, request, first frame of the request, frame count and
+ * first frame in the pass.  LTK_E_INVALID: bad arguments, mode 2 without the grouped path, or arrays too small. */
+int ltk_debug_ul_merge_plan(const int* avatar, const int* batch, int nreq, int cap, int mode, int grouped_available, int grouped_knob,
+                            int* pass_path, int* pass_avatar, int* pass_nf, int max_passes, int* n_passes,
+                            int* span_pass, int* span_req, int* span_first, int* span_count, int* span_at, int max_spans, int* n_spans);
+
 /* After a forward with capture enabled, copy one layer's activation
  * (state_dict prefix, e.g. "face_encoder_blocks.1.0") as NCHW float32. */
 /* Saturation counters (debug; knob SAT_CHECK = 1, environment LTK_SAT_CHECK or ltk_debug_set_knob).  The conv epilogues clamp to
@@ -560,6 +604,17 @@ int ltk_conv2d_f16_ex(ltk_engine* e, const void* d_x, int N, int H, int W, int C
  * makes (more rows or frames than a row kernel is built for) are not seen here. */
 int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                         int transposed, int out_pad, int has_res, int relu, const ltk_conv_opts* opts, ltk_conv_report* rep);
+
+/* The grouped dense conv of the Ultralight program on its own (ul_gconv_kernel; the twin of ltk_conv2d_f16_ex for kernel unit tests):
+ * y = clamp(relu?(conv(x, weight[set[n]]) * scale[set[n]] + shift[set[n]] + res)) for image n.  weight host fp32 [n_sets][Cout][Cin]
+ * [k][k] (rounded to fp16), scale / shift host fp32 [n_sets][Cout] (NULL = 1 / 0), set host int32 [N] in [0, n_sets).  k = 1 (stride 1,
+ * pad 0) or k = 3 with stride 2 and pad 1 or 3; Cin and Cout multiples of 16; N <= 256.  opts (or NULL): the channel views of x, y
+ * and res as ltk_conv2d_f16_ex takes them (act, ups and the force_* fields must be 0).  rep (or NULL): kernel = "ul_gconv_kernel",
+ * PXW = pixels and NBT = output channels of a block's tile, T = k-steps, grid = blocks, items = grid x * 65536 + grid y, NB = grid z.
+ * Everything else: LTK_E_INVALID. */
+int ltk_ul_gconv_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int n_sets, const int32_t* set,
+                     int Cout, int k, int stride, int pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
+                     const ltk_conv_opts* opts, ltk_conv_report* rep);
 
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */

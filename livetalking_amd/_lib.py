@@ -36,6 +36,15 @@ class UlReq(C.Structure):
     _fields_ = [("avatar", C.c_int), ("index", C.c_int), ("batch", C.c_int), ("d_feat", C.c_void_p), ("d_pred", C.c_void_p)]
 
 
+UL_MERGE_MAX_PASSES = 64     # include/ltk.h LTK_UL_MERGE_MAX_PASSES
+UL_PATH_PER_AVATAR, UL_PATH_GROUPED = 0, 1
+
+
+class UlMergeReport(C.Structure):
+    _fields_ = [("n_passes", C.c_int), ("n_avatars", C.c_int), ("grouped", C.c_int), ("frames", C.c_int),
+                ("path", C.c_int * UL_MERGE_MAX_PASSES), ("nf", C.c_int * UL_MERGE_MAX_PASSES), ("avatar", C.c_int * UL_MERGE_MAX_PASSES)]
+
+
 class HubertReq(C.Structure):
     _fields_ = [("pcm", C.c_void_p), ("n_samples", C.c_int), ("batch", C.c_int), ("first_row", C.c_int), ("row_step", C.c_int),
                 ("rows", C.c_int), ("d_out", C.c_void_p)]
@@ -94,6 +103,15 @@ SYMBOLS = {
     "ltk_ultralight_avatar_register": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                  C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "ltk_ultralight_infer": (C.c_int, [C.c_void_p, C.POINTER(UlReq), C.c_int, C.c_void_p]),
+    "ltk_ultralight_infer_merged": (C.c_int, [C.c_void_p, C.POINTER(UlReq), C.c_int, C.c_int, C.c_void_p, C.POINTER(UlMergeReport)]),
+    "ltk_ultralight_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "ltk_debug_ul_merge_plan": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.c_int, C.POINTER(C.c_int)]),
+    "ltk_ul_gconv_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ConvOpts),
+                                   C.POINTER(ConvReport)]),
     "ltk_ultralight_paste_back": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_ultralight_paste_back_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_ultralight_forward_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -11,7 +11,9 @@ What changes underneath: the U-Net is per avatar (`ultralight.pth`), so `load_av
 model's place; it registers state_dict + bank with the engine (libltk_hip.so) on first use.  `inference_batch` returns device
 handles (uint8 160x160x3, already truncated the way paste_back_frame's astype(uint8) does) instead of float numpy frames;
 `paste_back_frame` composites on the GPU and returns a writable C-contiguous uint8 (H,W,3) BGR array; the B items of one
-`inference_batch` result are composited and copied to the host together (LTK_PASTE_BATCH=0: one by one).  With
+`inference_batch` result are composited and copied to the host together (LTK_PASTE_BATCH=0: one by one).  `inference_batch` goes
+through the engine's "ultralight" scheduler, so that concurrent sessions' passes merge into one launch sequence
+(Engine.ultralight_infer_merged; LTK_UL_SCHED=0: one ultralight_infer call per session).  With
 `opt.egress` = "bgr24" | "i420" the frames leave through the device-side process_frames of egress.py.  HuBERT-large runs on
 torch by default (audio_features/hubert.py Audio2Feature); with LTK_HUBERT_ENGINE=1 or opt.hubert_engine it runs on the engine
 (EngineAudio2Feature) and its chunks reach inference_batch as device tensors.
@@ -28,10 +30,13 @@ import numpy as np
 from ..egress import SRC_ULTRALIGHT, DeviceEgressMixin, FrameGroup
 from ..engine import Engine
 from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror_index: part of the reference module's namespace)
+from ..scheduler import get_scheduler
 from .audio_features.hubert import HubertASR
 from .audio_features import hubert as _hubert
 
 _PASTE_BATCH = os.environ.get("LTK_PASTE_BATCH", "1") != "0"     # 0: one composite + one pageable copy per paste_back_frame call
+_UL_SCHED_DEFAULT = "1"
+_UL_SCHED = os.environ.get("LTK_UL_SCHED", _UL_SCHED_DEFAULT) != "0"    # 0: inference_batch calls ultralight_infer itself, no scheduler
 
 _engines = {}
 _engines_lock = threading.Lock()
@@ -160,7 +165,12 @@ class LightReal(DeviceEgressMixin, BaseAvatar):
         if feat.shape[0] != B:
             raise ValueError(f"expected {B} feature chunks, got {feat.shape[0]}")
         pred = torch.empty((B, 160, 160, 3), dtype=torch.uint8, device=feat.device)
-        self.engine.ultralight_infer([(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())])
+        if _UL_SCHED and hasattr(self.engine, "ultralight_infer_merged"):
+            # concurrent sessions' passes merge into one launch sequence (scheduler kind "ultralight"); a lone session takes the
+            # scheduler's solo path: one request, the launches and bytes of the direct call
+            get_scheduler(self.engine, "ultralight").infer(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())
+        else:
+            self.engine.ultralight_infer([(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())])
         items = list(pred.unbind(0))
         if _PASTE_BATCH and hasattr(self.engine, "ultralight_paste_back_batch"):
             # the process thread will ask for these B composites one by one, in order (base_avatar.py:429-433): remember

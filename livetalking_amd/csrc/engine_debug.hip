@@ -1,5 +1,6 @@
 // ------------------------------------------------------------------ test / measurement hooks of both models
 #include "debug_util.h"
+#include "ul_gconv.h"
 
 extern "C" {
 
@@ -763,6 +764,72 @@ int ltk_dwconv3x3_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C
     const hipError_t le = hipGetLastError();
     const hipError_t se = hipStreamSynchronize(e->compute);
     if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("depthwise conv kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
+int ltk_ul_gconv_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int n_sets, const int32_t* set,
+                     int Cout, int k, int stride, int pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
+                     const ltk_conv_opts* opts, ltk_conv_report* rep) {
+    // what the host alone can refuse comes first (also with no engine): the shape, the views, the set indices
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || n_sets <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (opts && (opts->act || opts->ups || opts->force_pxw || opts->force_nbt || opts->force_ksplit || opts->family))
+        return fail(LTK_E_INVALID, "ul_gconv: only the channel views of the options apply");
+    UlGconvIO io;
+    io.N = N; io.H = H; io.W = W; io.Cin = Cin; io.Cout = Cout; io.k = k; io.stride = stride; io.pad = pad; io.relu = relu ? 1 : 0;
+    io.x_ld = opts && opts->x_ld ? opts->x_ld : Cin; io.x_coff = opts ? opts->x_coff : 0;
+    io.y_ld = opts && opts->y_ld ? opts->y_ld : Cout; io.y_coff = opts ? opts->y_coff : 0;
+    io.res_ld = opts && opts->res_ld ? opts->res_ld : Cout; io.res_coff = opts ? opts->res_coff : 0;
+    io.x = (const f16*)d_x; io.y = (f16*)d_y; io.res = (const f16*)d_res;
+    UlGconvGeom geo;
+    std::string err;
+    if (ul_gconv_geom(io, &geo, &err)) return fail(LTK_E_INVALID, err);
+    if (!set) return fail(LTK_E_INVALID, "bad arguments");
+    for (int n = 0; n < N; ++n)
+        if (set[n] < 0 || set[n] >= n_sets) return fail(LTK_E_INVALID, "ul_gconv: image " + std::to_string(n) + " names a weight set outside [0, n_sets)");
+    if (rep) {
+        memset(rep, 0, sizeof(*rep));
+        snprintf(rep->kernel, sizeof(rep->kernel), "%s", ul_gconv_kernel_name());
+        rep->PXW = geo.tile_px; rep->NBT = geo.tile_co; rep->T = geo.ksteps; rep->S = stride; rep->grid = geo.blocks;
+        rep->items = geo.grid_x * 65536 + geo.grid_y; rep->NB = geo.grid_z;
+    }
+    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    // one record per weight set, as an avatar's (op 0), and the per-image table
+    const size_t wh = ul_gconv_pack(nullptr, Cin, Cout, k, nullptr), wsz = (size_t)Cout * Cin * k * k;
+    std::vector<f16> packed(wh * n_sets);
+    std::vector<float> ss((size_t)2 * Cout * n_sets);
+    for (int i = 0; i < n_sets; ++i) {
+        ul_gconv_pack(weight + i * wsz, Cin, Cout, k, packed.data() + i * wh);
+        for (int c = 0; c < Cout; ++c) {
+            ss[((size_t)2 * i) * Cout + c] = scale ? scale[(size_t)i * Cout + c] : 1.f;
+            ss[((size_t)2 * i + 1) * Cout + c] = shift ? shift[(size_t)i * Cout + c] : 0.f;
+        }
+    }
+    DevBuf d_w, d_ss, d_rec, d_tab;
+    int rc = upload(packed.data(), packed.size() * sizeof(f16), &d_w);
+    if (!rc) rc = upload(ss.data(), ss.size() * sizeof(float), &d_ss);
+    if (rc) return rc;
+    std::vector<UlGroupW> recs(n_sets);
+    memset(recs.data(), 0, recs.size() * sizeof(UlGroupW));
+    for (int i = 0; i < n_sets; ++i) {
+        recs[i].op[0].w = (const f16*)d_w.p + i * wh;
+        recs[i].op[0].scale = (const float*)d_ss.p + ((size_t)2 * i) * Cout;
+        recs[i].op[0].shift = (const float*)d_ss.p + ((size_t)2 * i + 1) * Cout;
+    }
+    rc = upload(recs.data(), recs.size() * sizeof(UlGroupW), &d_rec);
+    if (rc) return rc;
+    CHK(hipMalloc(&d_tab.p, sizeof(UlGroupTab)));
+    UlGroupTab tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int n = 0; n < N; ++n) tab.w[n] = (const UlGroupW*)d_rec.p + set[n];
+    std::lock_guard<std::mutex> g(e->mu);
+    hipStream_t s = e->compute;
+    launch_upload_group_table(&tab, N, (UlGroupTab*)d_tab.p, s);
+    hipError_t le = hipGetLastError();
+    const int lrc = le == hipSuccess ? launch_ul_gconv((const UlGroupTab*)d_tab.p, 0, io, s, &err) : 0;
+    const hipError_t se = hipStreamSynchronize(s);          // before the operands go
+    if (lrc) return conv_status(lrc, err);
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("ul_gconv kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
     return LTK_OK;
 }
 

@@ -134,6 +134,7 @@ struct MtAvatar {
 // Ultralight avatar (avatars/ultralight_avatar.py:63-81): the model is per avatar, so the launch program (ultralight.hip) lives with
 // the bank.  boxes = coords.pkl as (x1, y1, x2, y2).
 struct UlProgram;
+struct UlGroupTab;                                    // ul_gconv.h
 void ul_program_delete(UlProgram* p);                 // ultralight.hip
 struct UlAvatar {
     UlProgram* prog = nullptr;
@@ -333,6 +334,12 @@ struct ltk_engine {
     f16* ul_buf[kUlBufs] = {nullptr};
     int ul_frames = 0;
     DevTables* ul_tab = nullptr;          // per-frame bank crop / HuBERT chunk / output pointers of the pass being enqueued
+    UlGroupTab* ul_gtab = nullptr;        // per-frame weight records of a grouped pass (ul_gconv.h), uploaded like ul_tab
+    UlProgram* ul_geo = nullptr;          // the grouped path's geometry-only program, built at the first grouped pass
+    size_t ul_frame_bytes = 0;            // arena bytes per frame
+    // merged per-avatar passes (ul_pass with `own`): the run lengths of the frames' own-call frame counts -> the number such a pass's
+    // captured graph is keyed by (kUlMaxComps of them; a pass of a composition past that runs uncaptured)
+    std::map<std::vector<int>, int> ul_comps;
     // pools
     std::vector<Scratch> scratch_free;
     std::vector<hipStream_t> stream_free;
@@ -611,9 +618,27 @@ int run_program(ltk_engine* e, MtGraph* prog, int nf);                          
 // ultralight.hip.  ul_pass: one pass over frames [0, nf) of the arena, the per-frame tables already in e->ul_tab, under e->mu.
 // bank: the faces table holds uint8 bank crops (else d_img6: float32 NCHW test input); u8_out: the outs table holds the frame
 // destinations; d_pred_f32 (test hook): float32 NCHW sigmoid output.  The product configuration replays from e->prog_graphs.
-int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32);
+// own (ltk_ultralight_infer_merged): own[i] = the frame count of the ltk_ultralight_infer pass that would carry frame i on its own
+// request's behalf.  Every conv then sums a frame's channels in the order that pass would (conv3's split-K factor follows a launch's
+// frame count), so a frame's bytes do not depend on which requests share its pass; nullptr or all == nf: the plain pass.
+int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32, const std::vector<int>* own = nullptr);
 double ul_macs_per_frame(const UlAvatar& a);
 void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
+// ltk_ultralight_infer_merged's call plan (ultralight.hip ul_merge_plan; seen through ltk_debug_ul_merge_plan): which frames of which
+// request share a pass.  A span = frames [first, first + count) of request `req` at frames [at, at + count) of the pass.
+enum { UL_PATH_PER_AVATAR = 0, UL_PATH_GROUPED = 1 };
+struct UlMergeSpan { int req, first, count, at; };
+struct UlMergePass {
+    int path;                          // UL_PATH_*
+    int avatar;                        // the pass's avatar id; -1 on the grouped path
+    int nf;                            // <= cap
+    std::vector<UlMergeSpan> spans;
+};
+// mode 0: the rule (one avatar: per-avatar passes over the union of its requests; several: grouped passes over all frames when
+// `grouped_knob` and `grouped_ok`, else per avatar in order of first appearance); 1 / 2 force the per-avatar / grouped form.
+// 0, or -1 with *err set.
+int ul_merge_plan(const int* avatar, const int* batch, int nreq, int cap, int mode, bool grouped_ok, bool grouped_knob,
+                  std::vector<UlMergePass>* out, std::string* err);
 void ul_unload(ltk_engine* e);                         // engine teardown
 constexpr size_t kHubertPrograms = 3;
 constexpr size_t kHubertBatchPrograms = 2;

@@ -36,7 +36,8 @@ namespace ltk {
     X(GN_COOP, 1)              /* 1: GroupNorm of the maps too large for MT_GN1 in ONE tensor pass (gn_coop_kernel); 0: gn_stats + gn_apply */ \
     X(AUDIO0, 3)               /* bit 0: audio_encoder.0 as a VALU kernel reading the float32 mel windows (audio0_kernel); bit 1: audio_encoder.3 on audio3_kernel; 0: pack_mel + conv_mfma_kernel */ \
     X(CONV_S2D, 1)             /* 1: face_encoder_blocks.1.0 / 2.0 (shallow stride-2 layers) on convs2d_kernel; 0: conv_mfma_kernel (first generation) */ \
-    X(DEFER, 1)                /* 1: a solo ltk_wav2lip_infer_deferred call returns with its pass in flight, once the pass before it is complete; 0: every call waits for its own */
+    X(DEFER, 1)                /* 1: a solo ltk_wav2lip_infer_deferred call returns with its pass in flight, once the pass before it is complete; 0: every call waits for its own */ \
+    X(UL_GROUPED, 0)           /* 1: an ltk_ultralight_infer_merged call that carries several avatars runs ONE launch sequence over all its frames on the grouped kernels (per-image weights, ul_gconv.hip); 0: one merged sequence per avatar */
 
 // Notes.
 // GRAPH       the per-call pointer tables live in device memory, filled by one small launch in front of the graph.
@@ -63,6 +64,7 @@ namespace ltk {
 //             bit 1: the stride-(3, 1) layer on MFMAs fed straight from global memory.
 // CONV_S2D    16 -> 32 @256^2, 32 -> 64 @128^2 (conv7_mfma.hip): a wave = one output row x 32 output channels, weights in registers,
 //             pixel operands straight from global memory, no LDS.
+// UL_GROUPED  mode 0 of ltk_ultralight_infer_merged only (modes 1 / 2 force a form); the default follows profiles/ultralight_merge.txt.
 // DEFER       engine_internal.h infer_call / defer_window.h: a lone session's host turn-around (completion wake-up, Python, the next
 //             call's launches: 40-55 us of a 1.2-ms step) then runs under the pass in flight instead of between two passes.
 

@@ -6,6 +6,7 @@
 // ltk_ultralight_avatar_register and owned by the avatar; the activation arena and the pointer tables belong to the engine.
 // Its VALU kernels are dw_kernels.hip; what the other engine sources call is declared in engine_internal.h.
 #include "engine_internal.h"
+#include "ul_gconv.h"
 
 namespace ltk {
 
@@ -19,6 +20,9 @@ struct UlOp {
     std::string name;               // state_dict prefix of the conv (tap name); "<block>.up" for an upsample
     ConvPlan plan;                  // UL_CONV
     float* d_dw = nullptr;          // UL_DW: [C/16][9][16] weights, then scale [C], shift [C]
+    f16* d_gw = nullptr;            // UL_CONV, grouped path: the weights as ul_gconv_pack lays them out, then (d_gss) scale [C], shift [C]
+    float* d_gss = nullptr;
+    int cin = 0, k = 1, pad = 0;    // UL_CONV geometry (the geometry-only program of the grouped path has no plan)
     int C = 0, Creal = 0;           // channels the op writes (layout) / of the reference's tensor
     int stride = 1, relu = 0;
     int in_buf = 0, in_ld = 0, in_coff = 0, H = 0, W = 0;
@@ -33,6 +37,7 @@ struct UlProgram {
     UlHeadW headw;
     size_t buf_halfs[U_COUNT] = {0};      // per frame
     double macs_per_frame = 0;
+    UlGroupW* d_group = nullptr;          // the avatar's record of the grouped path (ul_gconv.h): every op's operands by op index
 };
 
 void ul_program_delete(UlProgram* p) {
@@ -40,7 +45,10 @@ void ul_program_delete(UlProgram* p) {
     for (UlOp& op : p->ops) {
         conv_plan_destroy(&op.plan);
         if (op.d_dw) (void)hipFree(op.d_dw);
+        if (op.d_gw) (void)hipFree(op.d_gw);
+        if (op.d_gss) (void)hipFree(op.d_gss);
     }
+    if (p->d_group) (void)hipFree(p->d_group);
     delete p;
 }
 
@@ -88,6 +96,16 @@ struct Builder {
         rc = conv_plan_create(&op.plan, w, in.C, cout, k, k, stride, stride, pad, pad, false, 0, sc.data(), sf.data(), &err);
         if (rc) return conv_status(rc, wname + ": " + err);
         op.C = op.Creal = cout; op.stride = stride; op.relu = relu;
+        op.cin = (in.C + 15) / 16 * 16; op.k = k; op.pad = pad;      // layout channels (inc's project conv reads 12 of 16)
+        {   // the grouped path's copy: fp16 weights in ul_gconv_kernel's operand layout (zeros behind channel in.C), fp32 scale / shift
+            std::vector<f16> gw(ul_gconv_pack(w, in.C, cout, k, nullptr));
+            ul_gconv_pack(w, in.C, cout, k, gw.data());
+            CHK(hipMalloc((void**)&op.d_gw, gw.size() * sizeof(f16)));
+            CHK(hipMemcpy(op.d_gw, gw.data(), gw.size() * sizeof(f16), hipMemcpyHostToDevice));
+            CHK(hipMalloc((void**)&op.d_gss, (size_t)2 * cout * sizeof(float)));
+            CHK(hipMemcpy(op.d_gss, sc.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
+            CHK(hipMemcpy(op.d_gss + cout, sf.data(), (size_t)cout * sizeof(float), hipMemcpyHostToDevice));
+        }
         op.in_buf = in.buf; op.in_ld = in.ld; op.in_coff = in.coff; op.H = in.H; op.W = in.W;
         op.plan.out_dims(in.H, in.W, &op.Ho, &op.Wo);
         op.out_buf = out_buf; op.out_ld = out_ld; op.out_coff = out_coff;
@@ -227,40 +245,141 @@ int build_ul_program(UlProgram* p, const ltk_named_tensor* sd, int n) {
     op.out_buf = f.buf;       // (writes the caller's frames, no arena buffer)
     op.macs = 96.0 * R * R;
     p->macs_per_frame += op.macs;
+    // ---- the record the grouped kernels read this avatar's operands from
+    if (p->ops.size() > (size_t)kUlMaxOps) return fail(LTK_E_INVALID, "ultralight program: more ops than a grouped record holds");
+    std::vector<UlGroupW> rec(1);
+    memset(&rec[0], 0, sizeof(UlGroupW));
+    for (size_t i = 0; i < p->ops.size(); ++i) {
+        const UlOp& o = p->ops[i];
+        rec[0].op[i] = UlGroupOp{o.d_gw, o.d_gss, o.d_gss ? o.d_gss + o.C : nullptr, o.d_dw};
+    }
+    rec[0].inw = p->inw;
+    rec[0].headw = p->headw;
+    CHK(hipMalloc((void**)&p->d_group, sizeof(UlGroupW)));
+    CHK(hipMemcpy(p->d_group, rec.data(), sizeof(UlGroupW), hipMemcpyHostToDevice));
     return 0;
 }
 
-// the launches of one pass over frames [0, nf); tables in e->ul_tab
-int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32) {
+// the grouped path's program: the ops' types, views and shapes of the one architecture, no weights (plans, d_dw, d_gw stay empty)
+UlProgram* ul_geometry_of(const UlProgram& src) {
+    UlProgram* p = new UlProgram();
+    for (const UlOp& o : src.ops) {
+        p->ops.emplace_back();
+        UlOp& g = p->ops.back();
+        g.type = o.type; g.name = o.name;
+        g.C = o.C; g.Creal = o.Creal; g.stride = o.stride; g.relu = o.relu; g.cin = o.cin; g.k = o.k; g.pad = o.pad;
+        g.in_buf = o.in_buf; g.in_ld = o.in_ld; g.in_coff = o.in_coff; g.H = o.H; g.W = o.W;
+        g.out_buf = o.out_buf; g.out_ld = o.out_ld; g.out_coff = o.out_coff; g.Ho = o.Ho; g.Wo = o.Wo;
+        g.res_buf = o.res_buf; g.res_ld = o.res_ld; g.res_coff = o.res_coff;
+        g.macs = o.macs;
+    }
+    memcpy(p->buf_halfs, src.buf_halfs, sizeof(p->buf_halfs));
+    p->macs_per_frame = src.macs_per_frame;
+    return p;
+}
+
+// the split factor conv3's planner takes for `io` over n frames (force > 0: asked for that factor); 1 where the route has no split
+// (the first-generation kernels, lin_fk_kernel).  Pure.
+int ul_conv_split(const ConvPlan& plan, ConvIO io, int n, int force, int* ks, std::string* err) {
+    ConvReport r;
+    memset(&r, 0, sizeof(r));
+    io.N = n; io.force_ksplit = force; io.report = &r;
+    const int rc = conv_launch_dry(plan, io, err);
+    *ks = std::max(1, r.ksplit);
+    return rc;
+}
+
+// One dense conv of a merged per-avatar pass, `io` over all its frames.  conv3 splits the channel loop of an under-filled launch by a
+// factor that follows the launch's frame count, and another factor is another fp32 summation order.  Here every frame takes the factor
+// of its OWN call (own[i] frames): neighbouring frames of one factor share a launch that forces it (unsplit: always one launch; split:
+// one launch where the planner grants the factor at that size, else launches of at most the own call's size, where it must).
+int ul_conv_as_own_calls(const UlOp& op, const ConvIO& io, const std::vector<int>& own, hipStream_t s, std::string* err) {
+    const int nf = io.N;
+    const size_t xs = (size_t)op.H * op.W * op.in_ld, ys = (size_t)op.Ho * op.Wo * op.out_ld, rs = (size_t)op.Ho * op.Wo * op.res_ld;
+    auto launch = [&](int at, int n, int ks) -> int {
+        ConvIO sub = io;
+        sub.N = n; sub.force_ksplit = ks;
+        sub.x = io.x + (size_t)at * xs; sub.y = io.y + (size_t)at * ys;
+        if (io.res) sub.res = io.res + (size_t)at * rs;
+        return conv_launch(op.plan, sub, s, err);
+    };
+    std::map<int, int> split_of;              // own-call frame count -> its split factor
+    for (int i = 0; i < nf; ++i)
+        if (!split_of.count(own[i])) {
+            int ks = 1;
+            if (const int rc = ul_conv_split(op.plan, io, own[i], 0, &ks, err)) return rc;
+            split_of[own[i]] = ks;
+        }
+    for (int at = 0; at < nf;) {
+        const int n_own = own[at], ks = split_of[n_own];
+        int end = at + 1;
+        while (end < nf && split_of[own[end]] == ks && (ks == 1 || own[end] == n_own)) ++end;
+        int step = end - at;
+        if (ks > 1) {
+            int got = 1;
+            if (ul_conv_split(op.plan, io, step, ks, &got, err) || got != ks) step = std::min(step, n_own);
+        }
+        for (int f = at; f < end; f += step) {
+            const int n = std::min(step, end - f);
+            if (ks > 1 && n != end - at) {      // (a launch of at most the own call's size: the same scratch fits, the same route)
+                int got = 1;
+                if (const int rc = ul_conv_split(op.plan, io, n, ks, &got, err)) return rc;
+                if (got != ks) { *err = "split factor " + std::to_string(ks) + " of a " + std::to_string(n_own) + "-frame call refused for " + std::to_string(n) + " frames"; return -1; }
+            }
+            if (const int rc = launch(f, n, ks)) return rc;
+        }
+        at = end;
+    }
+    return 0;
+}
+
+// the launches of one pass over frames [0, nf); tables in e->ul_tab.  gtab (grouped path): `p` is the geometry-only program and every
+// op that has weights takes them per frame through the table (e->ul_gtab), by its index in the program.  own: see ul_pass
+int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32,
+               const UlGroupTab* gtab = nullptr, const std::vector<int>* own = nullptr) {
     std::string err;
+    int opi = -1;
     for (UlOp& op : p.ops) {
+        ++opi;
         const f16* x = op.in_buf >= 0 ? e->ul_buf[op.in_buf] : nullptr;
         f16* y = e->ul_buf[op.out_buf];
         switch (op.type) {
         case UL_IN:
-            launch_ul_in(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, p.inw, y, s);
+            if (gtab) launch_ul_in_grouped(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, gtab, y, s);
+            else launch_ul_in(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, p.inw, y, s);
             break;
         case UL_FEAT:
             launch_ul_pack_feat(&e->ul_tab->mels, nf, y, s);
             break;
         case UL_DW:
-            launch_dwconv3x3(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, op.stride, op.d_dw, op.d_dw + (size_t)op.C * 9,
+            if (gtab) launch_dwconv3x3_grouped(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, op.stride, gtab, opi, op.relu, y,
+                                               op.out_ld / 16, op.out_coff / 16, s);
+            else launch_dwconv3x3(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, op.stride, op.d_dw, op.d_dw + (size_t)op.C * 9,
                              op.d_dw + (size_t)op.C * 10, op.relu, y, op.out_ld / 16, op.out_coff / 16, s);
             break;
         case UL_UP:
             launch_upsample2x(x, nf, op.in_ld / 16, op.in_coff / 16, op.C, op.H, op.W, y, op.out_ld / 16, op.out_coff / 16, s);
             break;
         case UL_HEAD:
-            launch_ul_head(x, nf, p.headw, u8_out ? &e->ul_tab->outs : nullptr, d_pred_f32, s);
+            if (gtab) launch_ul_head_grouped(x, nf, gtab, u8_out ? &e->ul_tab->outs : nullptr, d_pred_f32, s);
+            else launch_ul_head(x, nf, p.headw, u8_out ? &e->ul_tab->outs : nullptr, d_pred_f32, s);
             break;
-        default: {
+        default: if (gtab) {
+            UlGconvIO io;
+            io.x = x; io.N = nf; io.H = op.H; io.W = op.W; io.x_ld = op.in_ld; io.x_coff = op.in_coff; io.Cin = op.cin; io.Cout = op.C;
+            io.y = y; io.y_ld = op.out_ld; io.y_coff = op.out_coff;
+            io.res = op.res_buf >= 0 ? e->ul_buf[op.res_buf] : nullptr; io.res_ld = op.res_ld; io.res_coff = op.res_coff;
+            io.k = op.k; io.stride = op.stride; io.pad = op.pad; io.relu = op.relu;
+            const int rc = launch_ul_gconv(gtab, opi, io, s, &err);
+            if (rc) return conv_status(rc, op.name + ": " + err);
+        } else {
             ConvIO io;
             io.x = x; io.N = nf; io.H = op.H; io.W = op.W; io.x_ld = op.in_ld; io.x_coff = op.in_coff;
             io.y = y; io.y_ld = op.out_ld; io.y_coff = op.out_coff;
             io.res = op.res_buf >= 0 ? e->ul_buf[op.res_buf] : nullptr; io.res_ld = op.res_ld; io.res_coff = op.res_coff;
             io.relu = op.relu;
             io.partial = e->d_partial; io.partial_cap = e->partial_cap;
-            const int rc = conv_launch(op.plan, io, s, &err);
+            const int rc = own ? ul_conv_as_own_calls(op, io, *own, s, &err) : conv_launch(op.plan, io, s, &err);
             if (rc) return conv_status(rc, op.name + ": " + err);
         }
         }
@@ -287,12 +406,26 @@ int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, co
 
 // key of a captured Ultralight pass in e->prog_graphs: avatar ids are never reused (a program's address could be)
 const void* ul_graph_token(int avatar_id) { return reinterpret_cast<const void*>((uintptr_t)avatar_id); }
+// ... of a merged pass whose frames come from own calls of other sizes (e->ul_comps numbers the compositions from 1): the avatar id
+// stays in the low half
+constexpr int kUlMaxComps = 1024;
+const void* ul_comp_token(int avatar_id, int comp) { return reinterpret_cast<const void*>((uintptr_t)(uint32_t)avatar_id | ((uintptr_t)comp << 32)); }
+bool ul_token_is_avatar(const void* tok, int avatar_id) {
+    const uintptr_t t = reinterpret_cast<uintptr_t>(tok);
+    return (uint32_t)t == (uint32_t)avatar_id && (t >> 32) <= (uintptr_t)kUlMaxComps;
+}
+// ... and of a grouped pass: it holds no avatar's address (the table is filled in front of it), so it outlives every avatar
+const void* ul_group_token() { return reinterpret_cast<const void*>(~(uintptr_t)0); }
 
 // the engine's arena serves every Ultralight avatar (one architecture): grown, never shrunk.  Under e->mu.
 int ul_arena_reserve(ltk_engine* e, const UlProgram& p, int frames) {
     if (!e->ul_tab) {
         if (hipMalloc((void**)&e->ul_tab, sizeof(DevTables)) != hipSuccess) return fail(LTK_E_NOMEM, "pointer table allocation failed");
         CHK(hipMemset(e->ul_tab, 0, sizeof(DevTables)));
+    }
+    if (!e->ul_gtab) {
+        if (hipMalloc((void**)&e->ul_gtab, sizeof(UlGroupTab)) != hipSuccess) return fail(LTK_E_NOMEM, "pointer table allocation failed");
+        CHK(hipMemset(e->ul_gtab, 0, sizeof(UlGroupTab)));
     }
     if (frames <= e->ul_frames) return 0;
     CHK(hipStreamSynchronize(e->compute));
@@ -303,8 +436,8 @@ int ul_arena_reserve(ltk_engine* e, const UlProgram& p, int frames) {
         for (auto& kv : e->ul_avatars) ids.push_back(kv.first);
     }
     for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
-        bool ul = false;
-        for (int id : ids) ul = ul || it->first.first == ul_graph_token(id);
+        bool ul = it->first.first == ul_group_token();
+        for (int id : ids) ul = ul || ul_token_is_avatar(it->first.first, id);
         if (ul) { if (it->second.exec) (void)hipGraphExecDestroy(it->second.exec); it = e->prog_graphs.graphs.erase(it); }
         else ++it;
     }
@@ -319,25 +452,54 @@ int ul_arena_reserve(ltk_engine* e, const UlProgram& p, int frames) {
         CHK(hipMemset(e->ul_buf[i], 0, bytes));
     }
     e->ul_frames = frames;
+    e->ul_frame_bytes = 0;
+    for (int i = 0; i < U_COUNT; ++i) e->ul_frame_bytes += p.buf_halfs[i] * sizeof(f16);
     return 0;
 }
 
 }  // namespace
 
-int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32) {
+int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32, const std::vector<int>* own) {
     if (nf <= 0 || nf > e->ul_frames || nf > kPackMaxFrames) return fail(LTK_E_INVALID, "ultralight pass: frame count outside the arena");
+    if (own && (int)own->size() != nf) return fail(LTK_E_INVALID, "ultralight pass: one own-call frame count per frame");
+    if (own && std::all_of(own->begin(), own->end(), [nf](int n) { return n == nf; })) own = nullptr;      // the plain pass, its graph
     hipStream_t s = e->compute;
-    auto enq = [&]() -> int { return ul_enqueue(e, *a.prog, nf, s, bank, d_img6, u8_out, d_pred_f32); };
+    auto enq = [&]() -> int { return ul_enqueue(e, *a.prog, nf, s, bank, d_img6, u8_out, d_pred_f32, nullptr, own); };
     // the product configuration (bank crops in, uint8 frames out) has no per-call arguments: captured and replayed (knob GRAPH)
-    if (knob(K_GRAPH) && bank && u8_out && !d_pred_f32 && !e->capture)
-        return e->prog_graphs.run(e, std::make_pair(ul_graph_token(a.id), nf), s, "ultralight pass", nf, enq);
+    if (knob(K_GRAPH) && bank && u8_out && !d_pred_f32 && !e->capture) {
+        if (!own) return e->prog_graphs.run(e, std::make_pair(ul_graph_token(a.id), nf), s, "ultralight pass", nf, enq);
+        // the launches follow the run lengths of `own` alone: one graph per (avatar, composition)
+        std::vector<int> comp;
+        for (int i = 0; i < nf; ++i) {
+            if ((*own)[i] <= 0) return fail(LTK_E_INVALID, "ultralight pass: own-call frame count");
+            if (comp.empty() || comp.back() != (*own)[i]) { comp.push_back(1); comp.push_back((*own)[i]); }
+            else ++comp[comp.size() - 2];
+        }
+        auto it = e->ul_comps.find(comp);
+        if (it == e->ul_comps.end() && (int)e->ul_comps.size() < kUlMaxComps) it = e->ul_comps.emplace(comp, (int)e->ul_comps.size() + 1).first;
+        if (it != e->ul_comps.end())
+            return e->prog_graphs.run(e, std::make_pair(ul_comp_token(a.id, it->second), nf), s, "ultralight merged pass", nf, enq);
+    }
+    return enq();
+}
+
+// one pass over frames [0, nf) of SEVERAL avatars: the tables, e->ul_gtab among them, are uploaded; `like`: any avatar's program (the
+// geometry is the architecture's).  Captured per frame count under a token of its own.  Under e->mu.
+int ul_pass_grouped(ltk_engine* e, const UlAvatar& like, int nf) {
+    if (nf <= 0 || nf > e->ul_frames || nf > kPackMaxFrames) return fail(LTK_E_INVALID, "ultralight pass: frame count outside the arena");
+    if (!e->ul_gtab || !like.prog) return fail(LTK_E_STATE, "no Ultralight arena");
+    if (!e->ul_geo) e->ul_geo = ul_geometry_of(*like.prog);
+    hipStream_t s = e->compute;
+    auto enq = [&]() -> int { return ul_enqueue(e, *e->ul_geo, nf, s, true, nullptr, true, nullptr, e->ul_gtab); };
+    if (knob(K_GRAPH) && !e->capture)
+        return e->prog_graphs.run(e, std::make_pair(ul_group_token(), nf), s, "ultralight grouped pass", nf, enq);
     return enq();
 }
 
 void ul_drop_graphs(ltk_engine* e, int avatar_id) {
     bool synced = false;
     for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
-        if (it->first.first != ul_graph_token(avatar_id)) { ++it; continue; }
+        if (!ul_token_is_avatar(it->first.first, avatar_id)) { ++it; continue; }
         if (it->second.exec) {
             if (!synced) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->compute); synced = true; }
             (void)hipGraphExecDestroy(it->second.exec);
@@ -351,7 +513,50 @@ void ul_unload(ltk_engine* e) {
     for (int i = 0; i < kUlBufs; ++i)
         if (e->ul_buf[i]) { (void)hipFree(e->ul_buf[i]); e->ul_buf[i] = nullptr; }
     if (e->ul_tab) { (void)hipFree(e->ul_tab); e->ul_tab = nullptr; }
+    if (e->ul_gtab) { (void)hipFree(e->ul_gtab); e->ul_gtab = nullptr; }
+    ul_program_delete(e->ul_geo);
+    e->ul_geo = nullptr;
     e->ul_frames = 0;
+}
+
+// The passes of one ltk_ultralight_infer_merged call (pure: no engine, no HIP).  Frames keep request order inside a pass; a request is a
+// contiguous span, split only at a pass boundary; one request plans what ltk_ultralight_infer runs for it.
+int ul_merge_plan(const int* avatar, const int* batch, int nreq, int cap, int mode, bool grouped_ok, bool grouped_knob,
+                  std::vector<UlMergePass>* out, std::string* err) {
+    out->clear();
+    auto bad = [&](const char* m) { if (err) *err = m; return -1; };
+    if (!avatar || !batch || nreq <= 0 || cap <= 0 || mode < 0 || mode > 2) return bad("merge plan: bad arguments");
+    for (int r = 0; r < nreq; ++r)
+        if (batch[r] <= 0) return bad("merge plan: a request without frames");
+    std::vector<int> distinct;                 // in order of first appearance
+    for (int r = 0; r < nreq; ++r)
+        if (std::find(distinct.begin(), distinct.end(), avatar[r]) == distinct.end()) distinct.push_back(avatar[r]);
+    if (mode == 2 && !grouped_ok) return bad("merge plan: the grouped path is not available");
+    const bool grouped = mode == 2 || (mode == 0 && distinct.size() > 1 && grouped_knob && grouped_ok);
+    auto cut = [&](const std::vector<int>& reqs, int path, int av) {
+        UlMergePass cur{path, av, 0, {}};
+        for (int r : reqs)
+            for (int f = 0; f < batch[r];) {
+                const int take = std::min(cap - cur.nf, batch[r] - f);
+                cur.spans.push_back(UlMergeSpan{r, f, take, cur.nf});
+                cur.nf += take; f += take;
+                if (cur.nf == cap) { out->push_back(cur); cur = UlMergePass{path, av, 0, {}}; }
+            }
+        if (cur.nf) out->push_back(cur);
+    };
+    std::vector<int> reqs;
+    if (grouped) {
+        for (int r = 0; r < nreq; ++r) reqs.push_back(r);
+        cut(reqs, UL_PATH_GROUPED, -1);
+        return 0;
+    }
+    for (int av : distinct) {
+        reqs.clear();
+        for (int r = 0; r < nreq; ++r)
+            if (avatar[r] == av) reqs.push_back(r);
+        cut(reqs, UL_PATH_PER_AVATAR, av);
+    }
+    return 0;
 }
 
 }  // namespace ltk
@@ -427,6 +632,107 @@ int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* 
         }
         return 0;
     });
+}
+
+int ltk_ultralight_infer_merged(ltk_engine* e, const ltk_ul_req* reqs, int nreq, int mode, void* stream, ltk_ul_merge_report* rep) {
+    if (!reqs || nreq <= 0 || mode < 0 || mode > 2) return fail(LTK_E_INVALID, "bad arguments");
+    // every request is checked before anything is launched: a caller that batched several sessions re-issues them one by one after a
+    // failure and only the offender fails again (scheduler.py)
+    for (int r = 0; r < nreq; ++r)
+        if (reqs[r].batch <= 0 || reqs[r].index < 0 || !reqs[r].d_feat || !reqs[r].d_pred) return fail(LTK_E_INVALID, "bad request " + std::to_string(r));
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::vector<std::shared_ptr<UlAvatar>> hold;          // the banks, programs and records stay alive until this call has synchronised
+    std::vector<int> av(nreq), nb(nreq);
+    for (int r = 0; r < nreq; ++r) {
+        hold.push_back(find_ul_avatar(e, reqs[r].avatar));
+        if (!hold.back()) return fail(LTK_E_STATE, "unknown Ultralight avatar id (request " + std::to_string(r) + ")");
+        av[r] = reqs[r].avatar; nb[r] = reqs[r].batch;
+    }
+    if (rep) memset(rep, 0, sizeof(*rep));
+    CHK(enter_device(e->device));
+    return infer_call(e, stream, [&]() -> int {
+        const int cap = std::min(e->ul_frames, kPackMaxFrames);
+        if (cap <= 0) return fail(LTK_E_STATE, "no Ultralight arena");
+        std::vector<UlMergePass> plan;
+        std::string err;
+        if (ul_merge_plan(av.data(), nb.data(), nreq, cap, mode, e->ul_gtab != nullptr, knob(K_UL_GROUPED) != 0, &plan, &err)) return fail(LTK_E_STATE, err);
+        if (rep) {
+            std::vector<int> seen;
+            for (int a : av)
+                if (std::find(seen.begin(), seen.end(), a) == seen.end()) seen.push_back(a);
+            rep->n_avatars = (int)seen.size();
+        }
+        for (const UlMergePass& ps : plan) {
+            // the tables of a pass are uploaded in front of it in stream order; a frame's bank crop, features, destination and (grouped)
+            // weight record are those of the request that owns it
+            FacePtrs fp; MelPtrs mp; OutPtrs op;
+            UlGroupTab gt;
+            std::vector<int> own(ps.nf);        // the frame count of the ltk_ultralight_infer pass that would carry this frame
+            for (const UlMergeSpan& sp : ps.spans) {
+                const ltk_ul_req& q = reqs[sp.req];
+                const UlAvatar& a = *hold[sp.req];
+                for (int i = 0; i < sp.count; ++i) {
+                    const int f = sp.first + i, at = sp.at + i;
+                    const int idx = mirror_index(a.n, q.index + f);      // ultralight_avatar.py:150
+                    fp.p[at] = a.d_face + (size_t)idx * kUlFace * kUlFace * 3;
+                    mp.p[at] = (const float*)q.d_feat + (size_t)f * 16 * 1024;
+                    op.p[at] = (uint8_t*)q.d_pred + (size_t)f * kUlRes * kUlRes * 3;
+                    gt.w[at] = a.prog->d_group;
+                    own[at] = std::min(cap, q.batch - f / cap * cap);
+                }
+            }
+            launch_upload_tables(&fp, &mp, &op, ps.nf, e->ul_tab, e->compute);
+            if (ps.path == UL_PATH_GROUPED) launch_upload_group_table(&gt, ps.nf, e->ul_gtab, e->compute);
+            if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "pointer table upload failed");
+            UlAvatar& first = *hold[ps.spans[0].req];
+            const int rc = ps.path == UL_PATH_GROUPED ? ul_pass_grouped(e, first, ps.nf) : ul_pass(e, first, ps.nf, true, nullptr, true, nullptr, &own);
+            if (rc) return rc;
+            if (rep) {
+                if (rep->n_passes < LTK_UL_MERGE_MAX_PASSES) {
+                    rep->path[rep->n_passes] = ps.path; rep->nf[rep->n_passes] = ps.nf; rep->avatar[rep->n_passes] = ps.avatar;
+                }
+                rep->n_passes++;
+                rep->grouped += ps.path == UL_PATH_GROUPED ? 1 : 0;
+                rep->frames += ps.nf;
+            }
+        }
+        return 0;
+    });
+}
+
+int ltk_ultralight_info(ltk_engine* e, int* arena_frames, size_t* arena_bytes, size_t* bytes_per_frame, int* grouped) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (arena_frames) *arena_frames = e->ul_frames;
+    if (bytes_per_frame) *bytes_per_frame = e->ul_frame_bytes;
+    if (arena_bytes) *arena_bytes = e->ul_frame_bytes * (size_t)e->ul_frames;
+    if (grouped) *grouped = 1;             // ul_gconv.hip and the grouped kernels of dw_kernels.hip are part of every build
+    return LTK_OK;
+}
+
+int ltk_debug_ul_merge_plan(const int* avatar, const int* batch, int nreq, int cap, int mode, int grouped_available, int grouped_knob,
+                            int* pass_path, int* pass_avatar, int* pass_nf, int max_passes, int* n_passes,
+                            int* span_pass, int* span_req, int* span_first, int* span_count, int* span_at, int max_spans, int* n_spans) {
+    if (!avatar || !batch || nreq <= 0 || !pass_path || !pass_avatar || !pass_nf || !n_passes || !span_pass || !span_req || !span_first ||
+        !span_count || !span_at || !n_spans || max_passes <= 0 || max_spans <= 0)
+        return fail(LTK_E_INVALID, "bad arguments");
+    std::vector<UlMergePass> plan;
+    std::string err;
+    const bool knob_on = grouped_knob < 0 ? knob(K_UL_GROUPED) != 0 : grouped_knob != 0;
+    if (ul_merge_plan(avatar, batch, nreq, cap, mode, grouped_available != 0, knob_on, &plan, &err)) return fail(LTK_E_INVALID, err);
+    int np = 0, ns = 0;
+    for (const UlMergePass& ps : plan) {
+        if (np >= max_passes) return fail(LTK_E_INVALID, "merge plan: more passes than the caller's arrays hold");
+        pass_path[np] = ps.path; pass_avatar[np] = ps.avatar; pass_nf[np] = ps.nf;
+        for (const UlMergeSpan& sp : ps.spans) {
+            if (ns >= max_spans) return fail(LTK_E_INVALID, "merge plan: more spans than the caller's arrays hold");
+            span_pass[ns] = np; span_req[ns] = sp.req; span_first[ns] = sp.first; span_count[ns] = sp.count; span_at[ns] = sp.at;
+            ++ns;
+        }
+        ++np;
+    }
+    *n_passes = np; *n_spans = ns;
+    return LTK_OK;
 }
 
 int ltk_ultralight_op_count(ltk_engine* e, int avatar_id) {

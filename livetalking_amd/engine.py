@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import HubertReq, LtkError, MtReq, NamedTensor, UlReq, W2lReq  # noqa: F401
+from ._lib import HubertReq, LtkError, MtReq, NamedTensor, UlMergeReport, UlReq, W2lReq  # noqa: F401
 
 
 def _as_f32(a) -> np.ndarray:
@@ -269,6 +269,76 @@ class Engine:
             arr[i].avatar = int(aid); arr[i].index = int(index); arr[i].batch = int(batch)
             arr[i].d_feat = C.c_void_p(feat_ptr); arr[i].d_pred = C.c_void_p(pred_ptr)
         _lib.check(self._lib.ltk_ultralight_infer(self._h, arr, len(reqs), C.c_void_p(stream)))
+
+    def ultralight_infer_merged(self, reqs: Sequence[tuple], mode: int = 0, stream: int = 0, report: bool = False):
+        """ultralight_infer with the requests' passes merged (include/ltk.h: ltk_ultralight_infer_merged): one launch sequence per pass
+        of the call plan instead of one per request.  mode 0: the rule (knob UL_GROUPED decides for several avatars), 1: per avatar,
+        2: grouped.  report=True -> {"passes": [(path, frames, avatar)], "avatars", "grouped", "frames"} of what was launched."""
+        arr = (UlReq * len(reqs))()
+        for i, (aid, index, batch, feat_ptr, pred_ptr) in enumerate(reqs):
+            arr[i].avatar = int(aid); arr[i].index = int(index); arr[i].batch = int(batch)
+            arr[i].d_feat = C.c_void_p(feat_ptr); arr[i].d_pred = C.c_void_p(pred_ptr)
+        rep = UlMergeReport() if report else None
+        _lib.check(self._lib.ltk_ultralight_infer_merged(self._h, arr, len(reqs), int(mode), C.c_void_p(stream),
+                                                         C.byref(rep) if report else None))
+        if not report:
+            return None
+        n = min(rep.n_passes, _lib.UL_MERGE_MAX_PASSES)
+        return {"passes": [(rep.path[i], rep.nf[i], rep.avatar[i]) for i in range(n)], "n_passes": rep.n_passes, "avatars": rep.n_avatars,
+                "grouped": rep.grouped, "frames": rep.frames}
+
+    def ultralight_info(self) -> dict:
+        """The Ultralight arena: frames per pass, bytes, bytes per frame, and whether the grouped path is built."""
+        fr, gr = C.c_int(0), C.c_int(0)
+        ab, bf = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(self._lib.ltk_ultralight_info(self._h, C.byref(fr), C.byref(ab), C.byref(bf), C.byref(gr)))
+        return {"frames": fr.value, "bytes": ab.value, "bytes_per_frame": bf.value, "grouped": bool(gr.value)}
+
+    @property
+    def ul_max_frames(self) -> int:
+        """Frames one Ultralight pass carries (the scheduler's limit for kind "ultralight"); 0 before the first avatar."""
+        return min(self.ultralight_info()["frames"], 256)
+
+    @staticmethod
+    def ul_merge_plan(reqs: Sequence[tuple], cap: int, mode: int = 0, grouped_available: bool = True, grouped_knob: int = -1):
+        """ltk_debug_ul_merge_plan (no GPU, no engine): reqs = (avatar, batch) -> [(path, avatar, frames, [(request, first frame of the
+        request, count, first frame in the pass)])]."""
+        lib = _lib.load()
+        n = len(reqs)
+        av = (C.c_int * max(n, 1))(*[int(a) for a, _ in reqs])
+        nb = (C.c_int * max(n, 1))(*[int(b) for _, b in reqs])
+        total = sum(max(int(b), 0) for _, b in reqs)
+        mp = max(1, total // max(int(cap), 1) + n + 1)
+        ms = mp + n + 1
+        pp, pa, pn = (C.c_int * mp)(), (C.c_int * mp)(), (C.c_int * mp)()
+        sp, sr, sf, sc, sa = ((C.c_int * ms)() for _ in range(5))
+        npass, nspan = C.c_int(0), C.c_int(0)
+        _lib.check(lib.ltk_debug_ul_merge_plan(av, nb, n, int(cap), int(mode), int(bool(grouped_available)), int(grouped_knob),
+                                               pp, pa, pn, mp, C.byref(npass), sp, sr, sf, sc, sa, ms, C.byref(nspan)))
+        plan = [(pp[i], pa[i], pn[i], []) for i in range(npass.value)]
+        for j in range(nspan.value):
+            plan[sp[j]][3].append((sr[j], sf[j], sc[j], sa[j]))
+        return plan
+
+    def ul_gconv_f16(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, sets: Sequence[int], k: int = 1, stride: int = 1, pad: int = 0,
+                     scale=None, shift=None, d_res_ptr: int = 0, relu: bool = False, d_y_ptr: int = 0, views: Optional[dict] = None):
+        """The grouped dense conv on its own (include/ltk.h: ltk_ul_gconv_f16): weight (n_sets, Cout, Cin, k, k), scale / shift
+        (n_sets, Cout), sets[n] = image n's weight set; views = {x_ld, x_coff, y_ld, y_coff, res_ld, res_coff}.  -> the report as a dict."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        n_sets, Cout = int(w.shape[0]), int(w.shape[1])
+        sc = np.ascontiguousarray(scale, dtype=np.float32) if scale is not None else None
+        sf = np.ascontiguousarray(shift, dtype=np.float32) if shift is not None else None
+        st = np.ascontiguousarray(np.asarray(sets, dtype=np.int32))
+        opts = _lib.ConvOpts()
+        for key, v in (views or {}).items():
+            setattr(opts, key, int(v))
+        rep = _lib.ConvReport()
+        _lib.check(self._lib.ltk_ul_gconv_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(H), int(W), int(Cin), w.ctypes.data, n_sets,
+                                              st.ctypes.data, Cout, int(k), int(stride), int(pad), sc.ctypes.data if sc is not None else None,
+                                              sf.ctypes.data if sf is not None else None, C.c_void_p(d_res_ptr) if d_res_ptr else None,
+                                              int(bool(relu)), C.c_void_p(d_y_ptr), C.byref(opts), C.byref(rep)))
+        return {"kernel": rep.kernel.decode(), "tile_px": rep.PXW, "tile_co": rep.NBT, "ksteps": rep.T, "blocks": rep.grid,
+                "grid": (rep.items >> 16, rep.items & 0xFFFF, rep.NB)}
 
     def ultralight_paste_back(self, avatar_id: int, idx: int, d_pred_ptr: int, out: np.ndarray, stream: int = 0):
         """out: C-contiguous uint8 (H,W,3) host array, filled in place (ultralight_avatar.py:173-184)."""

@@ -24,7 +24,8 @@ one request in flight (its inference thread blocks in `infer()`), and every requ
 tensor.  One scheduler per (engine, kind); kinds: "wav2lip" -> Engine.wav2lip_infer, "musetalk" -> Engine.musetalk_infer,
 "hubert" -> Engine.hubert_step_batch (the live HuBERT steps of concurrent Ultralight sessions: a request is
 (pcm, batch, first_row, row_step, rows, out_ptr), its size unit one clip, at most HUBERT_BATCH_CLIPS per engine call; it enters
-through `submit`).
+through `submit`), "ultralight" -> Engine.ultralight_infer_merged (the U-Net passes of concurrent Ultralight sessions as one launch
+sequence per pass of the engine's merge plan; at most Engine.ul_max_frames frames per call, so that a call is one pass).
 """
 from __future__ import annotations
 
@@ -36,7 +37,8 @@ import time
 
 # kind -> the engine method that takes a list of requests; resolved on first use (an engine need not have the methods of the kinds
 # it never serves)
-_ENGINE_CALL = {"wav2lip": "wav2lip_infer", "musetalk": "musetalk_infer", "hubert": "hubert_step_batch"}
+_ENGINE_CALL = {"wav2lip": "wav2lip_infer", "musetalk": "musetalk_infer", "hubert": "hubert_step_batch",
+                "ultralight": "ultralight_infer_merged"}
 HUBERT_BATCH_CLIPS = 16          # csrc/musetalk.h kHubertBatchClips: clips per batched program run
 
 
@@ -98,6 +100,9 @@ class BatchingScheduler:
             return self._max_frames
         if self.kind == "hubert":
             return HUBERT_BATCH_CLIPS
+        if self.kind == "ultralight":
+            lim = getattr(self.engine, "ul_max_frames", 0)
+            return int(lim) if lim else 1 << 30
         lim = getattr(self.engine, "max_frames" if self.kind == "wav2lip" else "mt_max_frames", 0)
         return int(lim) if lim else 1 << 30
 
