@@ -448,7 +448,10 @@ int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6
 int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6, const float* feat, int B, float* pred);
 /* the launches of an Ultralight avatar's program in execution order: the tap name of each (as ltk_ultralight_forward_host lists them,
  * and "audio_feat", the packed feature chunk) and its type: 0 dense conv (as ltk_musetalk_op_name), 10 depthwise conv, 11 upsample,
- * 12 input conv, 13 feature pack, 14 head */
+ * 12 input conv, 13 feature pack, 14 head, 15 a fused inverted residual.  The list follows knob UL_FUSE_IR as it stands (environment
+ * LTK_UL_FUSE_IR or ltk_debug_set_knob; default 0: 86 ops): with the knob on, an inverted residual that ul_ir_kernel takes is listed
+ * ONCE, as type 15 under its project conv's name "<block>.conv.6" (60 ops); its "<block>.conv.0" / ".conv.3" tensors do not exist in
+ * such a pass and ltk_debug_get reports them as absent. */
 int ltk_ultralight_op_count(ltk_engine* e, int avatar_id);
 int ltk_ultralight_op_name(ltk_engine* e, int avatar_id, int op, char* buf, int buf_len, int* type);
 /* average milliseconds of one pass of `frames` frames as ltk_ultralight_infer enqueues it (replayed graph under knob GRAPH), on
@@ -615,6 +618,39 @@ int ltk_debug_conv_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, 
 int ltk_ul_gconv_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, const float* weight, int n_sets, const int32_t* set,
                      int Cout, int k, int stride, int pad, const float* scale, const float* shift, const void* d_res, int relu, void* d_y,
                      const ltk_conv_opts* opts, ltk_conv_report* rep);
+
+/* One inverted residual of the Ultralight program in one launch (ul_ir_kernel, csrc/ul_ir.hip; knob UL_FUSE_IR puts it into the
+ * program): e1 = f16_sat(relu(w1 . x * scale1 + shift1)) [mid channels], e2 = f16_sat(relu(dw3x3(e1; stride, zero padding of the
+ * hidden map) * scale_d + shift_d)), y = f16_sat(w2 . e2 * scale2 + shift2 + res); the hidden tensors stay in LDS.
+ *
+ * ltk_debug_ul_ir_plan: what the planner decides about a block, on the host alone (no engine, no GPU).  N <= 256 images, any H, W >= 1,
+ * Cin, mid and Cout multiples of 16, stride 1 or 2 (Ho = (H - 1) / stride + 1), has_res only with Cin == Cout and stride 1, Cout / 16 one
+ * of 1, 2, 3, 4, 8, 16 (the accumulators the kernel is built for), opts (or NULL): the channel views of x, y and res as ltk_conv2d_f16_ex
+ * takes them (every other field must be 0); tap: the instantiation that also stores e1 / e2.  Returns LTK_OK with rep->accepted = 1 and
+ * the plan, or LTK_OK with rep->accepted = 0 and rep->reason (also ltk_last_error) where the planner refuses. */
+typedef struct ltk_ul_ir_report {
+    char kernel[64];            /* "ul_ir_kernel<JT,tap>" */
+    char reason[160];           /* why the planner refused; "" when accepted */
+    int accepted;
+    int Ho, Wo;
+    int TH, TW;                 /* a block's tile of output pixels */
+    int MC, chunks;             /* hidden channels per chunk, chunks */
+    int hidden_px;              /* hidden pixels a block expands per chunk (tile + halo) */
+    int lds_bytes, lds_limit;
+    int grid_x, grid_y, grid_z, blocks, threads;
+} ltk_ul_ir_report;
+int ltk_debug_ul_ir_plan(int N, int H, int W, int Cin, int mid, int Cout, int stride, int has_res, int tap, const ltk_conv_opts* opts,
+                         ltk_ul_ir_report* rep);
+
+/* The op on its own (the twin of ltk_ul_gconv_f16).  d_x device fp16 [N][x_ld/16][H][W][16]; w1 [mid][Cin], wd [mid][3][3], w2 [Cout][mid]
+ * host fp32 torch layout (w1, w2 rounded to fp16, wd stays fp32); scale / shift pairs host fp32 (NULL = 1 / 0); d_res (or NULL) and d_y
+ * device fp16 at the output's geometry.  d_e1 / d_e2 (both or neither): device fp16 tap buffers [N][mid/16][H][W][16] and
+ * [N][mid/16][Ho][Wo][16]; with them the tap instantiation also stores the hidden tensors, every element by the block that owns it.
+ * rep (or NULL): the planner's report.  What the planner refuses: LTK_E_INVALID with its text, nothing launched. */
+int ltk_ul_ir_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, int mid, int Cout, int stride, const float* w1,
+                  const float* wd, const float* w2, const float* scale1, const float* shift1, const float* scale_d, const float* shift_d,
+                  const float* scale2, const float* shift2, const void* d_res, void* d_y, const ltk_conv_opts* opts, void* d_e1, void* d_e2,
+                  ltk_ul_ir_report* rep);
 
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */

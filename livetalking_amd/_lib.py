@@ -65,6 +65,12 @@ class ConvReport(C.Structure):
                                                                      "FT", "UB", "l2w", "l2h", "NB", "s2half", "phases", "lds", "args_hash")]
 
 
+class UlIrReport(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("reason", C.c_char * 160)] + [(n, C.c_int) for n in (
+        "accepted", "Ho", "Wo", "TH", "TW", "MC", "chunks", "hidden_px", "lds_bytes", "lds_limit", "grid_x", "grid_y", "grid_z", "blocks",
+        "threads")]
+
+
 class NormOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
 
@@ -112,6 +118,9 @@ SYMBOLS = {
     "ltk_ul_gconv_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ConvOpts),
                                    C.POINTER(ConvReport)]),
+    "ltk_debug_ul_ir_plan": (C.c_int, [C.c_int] * 9 + [C.POINTER(ConvOpts), C.POINTER(UlIrReport)]),
+    "ltk_ul_ir_f16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 11 + [C.POINTER(ConvOpts), C.c_void_p, C.c_void_p,
+                                C.POINTER(UlIrReport)]),
     "ltk_ultralight_paste_back": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_ultralight_paste_back_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_ultralight_forward_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

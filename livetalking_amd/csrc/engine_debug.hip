@@ -1,6 +1,7 @@
 // ------------------------------------------------------------------ test / measurement hooks of both models
 #include "debug_util.h"
 #include "ul_gconv.h"
+#include "ul_ir.h"
 
 extern "C" {
 
@@ -830,6 +831,78 @@ int ltk_ul_gconv_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Ci
     const hipError_t se = hipStreamSynchronize(s);          // before the operands go
     if (lrc) return conv_status(lrc, err);
     if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("ul_gconv kernel: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
+namespace {
+
+// the planner's answer for a hook call: 0 with *rep the plan, or -1 with rep->reason (and *err) the refusal
+int ul_ir_hook_plan(ltk::UlIrIO* io, int N, int H, int W, int Cin, int mid, int Cout, int stride, int has_res, bool tap, const ltk_conv_opts* opts,
+                    ltk_ul_ir_report* rep, std::string* err) {
+    using namespace ltk;
+    io->N = N; io->H = H; io->W = W; io->Cin = Cin; io->mid = mid; io->Cout = Cout; io->stride = stride; io->has_res = has_res ? 1 : 0;
+    io->x_ld = opts && opts->x_ld ? opts->x_ld : Cin; io->x_coff = opts ? opts->x_coff : 0;
+    io->y_ld = opts && opts->y_ld ? opts->y_ld : Cout; io->y_coff = opts ? opts->y_coff : 0;
+    io->res_ld = opts && opts->res_ld ? opts->res_ld : Cout; io->res_coff = opts ? opts->res_coff : 0;
+    UlIrPlan pl;
+    int rc;
+    if (opts && (opts->act || opts->ups || opts->force_pxw || opts->force_nbt || opts->force_ksplit || opts->family)) {
+        *err = "ul_ir: only the channel views of the options apply";
+        memset(&pl, 0, sizeof(pl));
+        rc = -1;
+    } else {
+        rc = ul_ir_plan(*io, tap, &pl, err);
+    }
+    if (rep) {
+        memset(rep, 0, sizeof(*rep));
+        if (rc) {
+            snprintf(rep->reason, sizeof(rep->reason), "%s", err->c_str());
+        } else {
+            snprintf(rep->kernel, sizeof(rep->kernel), "%s", pl.kernel);
+            rep->accepted = 1;
+            rep->Ho = pl.Ho; rep->Wo = pl.Wo; rep->TH = pl.TH; rep->TW = pl.TW; rep->MC = pl.MC; rep->chunks = pl.chunks;
+            rep->hidden_px = pl.hidden_px; rep->lds_bytes = pl.lds_bytes; rep->lds_limit = pl.lds_limit;
+            rep->grid_x = pl.grid_x; rep->grid_y = pl.grid_y; rep->grid_z = pl.grid_z; rep->blocks = pl.blocks; rep->threads = pl.threads;
+        }
+    }
+    return rc;
+}
+
+}  // namespace
+
+int ltk_debug_ul_ir_plan(int N, int H, int W, int Cin, int mid, int Cout, int stride, int has_res, int tap, const ltk_conv_opts* opts,
+                         ltk_ul_ir_report* rep) {
+    if (!rep) return fail(LTK_E_INVALID, "bad arguments");
+    ltk::UlIrIO io;
+    std::string err;
+    if (ul_ir_hook_plan(&io, N, H, W, Cin, mid, Cout, stride, has_res, tap != 0, opts, rep, &err)) (void)fail(LTK_E_INVALID, err);
+    return LTK_OK;
+}
+
+int ltk_ul_ir_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, int mid, int Cout, int stride, const float* w1,
+                  const float* wd, const float* w2, const float* scale1, const float* shift1, const float* scale_d, const float* shift_d,
+                  const float* scale2, const float* shift2, const void* d_res, void* d_y, const ltk_conv_opts* opts, void* d_e1, void* d_e2,
+                  ltk_ul_ir_report* rep) {
+    // the planner first, on the host alone (also with no engine): what it refuses is refused before anything is allocated or launched
+    UlIrIO io;
+    std::string err;
+    if (ul_ir_hook_plan(&io, N, H, W, Cin, mid, Cout, stride, d_res != nullptr, d_e1 || d_e2, opts, rep, &err)) return fail(LTK_E_INVALID, err);
+    if ((d_e1 == nullptr) != (d_e2 == nullptr)) return fail(LTK_E_INVALID, "ul_ir: both tap buffers or neither");
+    if (!e || !d_x || !w1 || !wd || !w2 || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    size_t off[4];
+    std::vector<uint8_t> img(ul_ir_pack(nullptr, nullptr, nullptr, Cin, mid, Cout, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, off));
+    ul_ir_pack(w1, wd, w2, Cin, mid, Cout, scale1, shift1, scale_d, shift_d, scale2, shift2, img.data(), off);
+    DevBuf d_w;
+    const int rc = upload(img.data(), img.size(), &d_w);
+    if (rc) return rc;
+    io.x = (const f16*)d_x; io.y = (f16*)d_y; io.res = (const f16*)d_res; io.e1 = (f16*)d_e1; io.e2 = (f16*)d_e2;
+    std::lock_guard<std::mutex> g(e->mu);
+    hipStream_t s = e->compute;
+    const int lrc = launch_ul_ir(ul_ir_weights((const uint8_t*)d_w.p, off), io, s, nullptr, &err);
+    const hipError_t se = hipStreamSynchronize(s);          // before the operands go
+    if (lrc) return conv_status(lrc, err);
+    if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ul_ir kernel: ") + hipGetErrorString(se));
     return LTK_OK;
 }
 

@@ -37,7 +37,8 @@ namespace ltk {
     X(AUDIO0, 3)               /* bit 0: audio_encoder.0 as a VALU kernel reading the float32 mel windows (audio0_kernel); bit 1: audio_encoder.3 on audio3_kernel; 0: pack_mel + conv_mfma_kernel */ \
     X(CONV_S2D, 1)             /* 1: face_encoder_blocks.1.0 / 2.0 (shallow stride-2 layers) on convs2d_kernel; 0: conv_mfma_kernel (first generation) */ \
     X(DEFER, 1)                /* 1: a solo ltk_wav2lip_infer_deferred call returns with its pass in flight, once the pass before it is complete; 0: every call waits for its own */ \
-    X(UL_GROUPED, 0)           /* 1: an ltk_ultralight_infer_merged call that carries several avatars runs ONE launch sequence over all its frames on the grouped kernels (per-image weights, ul_gconv.hip); 0: one merged sequence per avatar */
+    X(UL_GROUPED, 0)           /* 1: an ltk_ultralight_infer_merged call that carries several avatars runs ONE launch sequence over all its frames on the grouped kernels (per-image weights, ul_gconv.hip); 0: one merged sequence per avatar */ \
+    X(UL_FUSE_IR, 0)           /* 1 (opt-in): a per-avatar Ultralight pass runs each inverted residual on a map of >= 32 x 32 pixels as ONE launch (ul_ir_kernel, hidden tile in LDS) instead of expand + depthwise + project; read at enqueue */
 
 // Notes.
 // GRAPH       the per-call pointer tables live in device memory, filled by one small launch in front of the graph.
@@ -65,6 +66,13 @@ namespace ltk {
 // CONV_S2D    16 -> 32 @256^2, 32 -> 64 @128^2 (conv7_mfma.hip): a wave = one output row x 32 output channels, weights in registers,
 //             pixel operands straight from global memory, no LDS.
 // UL_GROUPED  mode 0 of ltk_ultralight_infer_merged only (modes 1 / 2 force a form); the default follows profiles/ultralight_merge.txt.
+// UL_FUSE_IR  csrc/ul_ir.hip: 13 of the 26 blocks, 60 launches per pass instead of 86; the weights are packed for it at register time whatever
+//             the knob says, so it can change at run time (captured passes are keyed by knob_epoch()).  The grouped path (UL_GROUPED,
+//             mode 2) ignores it.  The fused op has one summation order at every frame count: one launch over all frames of a merged pass.
+//             ltk_ultralight_op_name lists a fused block once (type 15) under its project conv's name, and ltk_debug_capture taps only that
+//             output: the .conv.0 / .conv.3 tensors do not exist in a fused pass.  SAT_CHECK: the Ultralight program has no saturation
+//             scan; one added to it would see the fused op's output only, never the hidden tensors.  Default 0 until a follow-up meets
+//             the rule in profiles/ultralight_fuse_ir.txt.
 // DEFER       engine_internal.h infer_call / defer_window.h: a lone session's host turn-around (completion wake-up, Python, the next
 //             call's launches: 40-55 us of a 1.2-ms step) then runs under the pass in flight instead of between two passes.
 

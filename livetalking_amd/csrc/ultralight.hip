@@ -7,13 +7,14 @@
 // Its VALU kernels are dw_kernels.hip; what the other engine sources call is declared in engine_internal.h.
 #include "engine_internal.h"
 #include "ul_gconv.h"
+#include "ul_ir.h"
 
 namespace ltk {
 
 enum UlBuf { U_FEAT = 0, U_X0, U_E1, U_E2, U_P, U_Q, U_CAT1, U_CAT2, U_CAT3, U_CAT4, U_FCAT, U_COUNT };
 static_assert(U_COUNT <= kUlBufs, "engine_internal.h kUlBufs");
 
-enum UlOpType { UL_CONV = 0, UL_DW, UL_UP, UL_IN, UL_FEAT, UL_HEAD };
+enum UlOpType { UL_CONV = 0, UL_DW, UL_UP, UL_IN, UL_FEAT, UL_HEAD, UL_IR };      // UL_IR: only in the listing of a fused program (ul_listing)
 
 struct UlOp {
     int type = UL_CONV;
@@ -22,6 +23,8 @@ struct UlOp {
     float* d_dw = nullptr;          // UL_DW: [C/16][9][16] weights, then scale [C], shift [C]
     f16* d_gw = nullptr;            // UL_CONV, grouped path: the weights as ul_gconv_pack lays them out, then (d_gss) scale [C], shift [C]
     float* d_gss = nullptr;
+    uint8_t* d_ir = nullptr;        // UL_CONV, the expand conv of an inverted residual the fused kernel takes (knob UL_FUSE_IR): the block's
+    size_t ir_off[4] = {0, 0, 0, 0};   // operand image for ul_ir_kernel (ul_ir_pack) - this op, the depthwise conv and the project conv behind it
     int cin = 0, k = 1, pad = 0;    // UL_CONV geometry (the geometry-only program of the grouped path has no plan)
     int C = 0, Creal = 0;           // channels the op writes (layout) / of the reference's tensor
     int stride = 1, relu = 0;
@@ -37,6 +40,7 @@ struct UlProgram {
     UlHeadW headw;
     size_t buf_halfs[U_COUNT] = {0};      // per frame
     double macs_per_frame = 0;
+    size_t ir_bytes = 0;                  // operand images of the fused inverted residuals
     UlGroupW* d_group = nullptr;          // the avatar's record of the grouped path (ul_gconv.h): every op's operands by op index
 };
 
@@ -47,12 +51,50 @@ void ul_program_delete(UlProgram* p) {
         if (op.d_dw) (void)hipFree(op.d_dw);
         if (op.d_gw) (void)hipFree(op.d_gw);
         if (op.d_gss) (void)hipFree(op.d_gss);
+        if (op.d_ir) (void)hipFree(op.d_ir);
     }
     if (p->d_group) (void)hipFree(p->d_group);
     delete p;
 }
 
 double ul_macs_per_frame(const UlAvatar& a) { return a.prog ? a.prog->macs_per_frame : 0.0; }
+
+// The program fuses the inverted residuals whose input map has at least this many pixels (32 x 32: the blocks on the 160^2 .. 40^2 maps and
+// the audio tower's first two).  The blocks on the 20^2 maps and below have 512 to 2048 hidden channels and stream weights: ul_ir_kernel
+// re-reads them per 8 x 8 tile, and fusing them was not tried.
+constexpr int kUlIrMinMapPx = 32 * 32;
+
+// ops[at] .. ops[at + 2] = expand, depthwise, project of an inverted residual that has a fused operand image: the fused launch over n
+// frames, if the planner accepts it at that count (x, y, res: the arena's buffers, or null for the plan alone)
+bool ul_ir_io(const UlProgram& p, size_t at, int n, f16* const* bufs, UlIrIO* io) {
+    if (at + 2 >= p.ops.size() || !p.ops[at].d_ir) return false;
+    const UlOp &ex = p.ops[at], &dw = p.ops[at + 1], &pr = p.ops[at + 2];
+    *io = UlIrIO();
+    io->N = n; io->H = ex.H; io->W = ex.W; io->Cin = ex.cin; io->mid = ex.C; io->Cout = pr.C; io->stride = dw.stride;
+    io->x_ld = ex.in_ld; io->x_coff = ex.in_coff;
+    io->y_ld = pr.out_ld; io->y_coff = pr.out_coff;
+    io->has_res = pr.res_buf >= 0 ? 1 : 0; io->res_ld = pr.res_ld; io->res_coff = pr.res_coff;
+    if (bufs) {
+        io->x = bufs[ex.in_buf]; io->y = bufs[pr.out_buf];
+        io->res = pr.res_buf >= 0 ? bufs[pr.res_buf] : nullptr;
+    }
+    UlIrPlan pl;
+    std::string err;
+    return ul_ir_plan(*io, false, &pl, &err) == 0;
+}
+
+// (name, type) of every launch of a per-avatar pass under the knob's current value: a fused inverted residual once, as UL_IR under
+// its project conv's name
+std::vector<std::pair<std::string, int>> ul_listing(const UlProgram& p) {
+    std::vector<std::pair<std::string, int>> out;
+    const bool fuse = knob(K_UL_FUSE_IR) != 0;
+    UlIrIO io;
+    for (size_t at = 0; at < p.ops.size(); ++at) {
+        if (fuse && ul_ir_io(p, at, 1, nullptr, &io)) { at += 2; out.emplace_back(p.ops[at].name, (int)UL_IR); }
+        else out.emplace_back(p.ops[at].name, p.ops[at].type);
+    }
+    return out;
+}
 
 namespace {
 
@@ -165,7 +207,36 @@ struct Builder {
             if ((rc = conv(pre + ".conv.0", pre + ".conv.1", false, in, mid, 1, 1, 0, 1, nullptr, U_E1, mid, 0, &e1))) return rc;
         }
         if ((rc = dw(pre + ".conv.3", pre + ".conv.4", e1, mid, stride, U_E2, &e2))) return rc;
-        return conv(pre + ".conv.6", pre + ".conv.7", false, e2, cout, 1, 1, 0, 0, res ? &in : nullptr, out_buf, out_ld, out_coff, out);
+        if ((rc = conv(pre + ".conv.6", pre + ".conv.7", false, e2, cout, 1, 1, 0, 0, res ? &in : nullptr, out_buf, out_ld, out_coff, out))) return rc;
+        return in.C == 6 ? 0 : ir_fused(pre, in, mid, cout, stride, res, out_ld, out_coff);
+    }
+    // the same block's operands for ul_ir_kernel (knob UL_FUSE_IR, read at enqueue: the three ops above stay), where the program wants the
+    // block fused and the planner accepts its geometry at some frame count
+    int ir_fused(const std::string& pre, const Tn& in, int mid, int cout, int stride, bool res, int out_ld, int out_coff) {
+        if (in.H * in.W < kUlIrMinMapPx) return 0;
+        UlIrIO io;
+        io.N = 1; io.H = in.H; io.W = in.W; io.Cin = in.C; io.mid = mid; io.Cout = cout; io.stride = stride;
+        io.x_ld = in.ld; io.x_coff = in.coff; io.y_ld = out_ld; io.y_coff = out_coff;
+        io.has_res = res ? 1 : 0; io.res_ld = in.ld; io.res_coff = in.coff;
+        UlIrPlan pl;
+        std::string err;
+        if (ul_ir_plan(io, false, &pl, &err)) return 0;
+        const float* w1 = sd.get(pre + ".conv.0.weight", (size_t)mid * in.C);
+        const float* wd = sd.get(pre + ".conv.3.weight", (size_t)mid * 9);
+        const float* w2 = sd.get(pre + ".conv.6.weight", (size_t)cout * mid);
+        if (!w1 || !wd || !w2) return fail(LTK_E_INVALID, "state_dict is missing (or has a wrong shape for) " + pre + ".conv.{0,3,6}.weight");
+        std::vector<float> s1, b1, s_d, b_d, s2, b2;
+        int rc;
+        if ((rc = fold_bn(pre + ".conv.1", mid, nullptr, &s1, &b1)) || (rc = fold_bn(pre + ".conv.4", mid, nullptr, &s_d, &b_d)) ||
+            (rc = fold_bn(pre + ".conv.7", cout, nullptr, &s2, &b2)))
+            return rc;
+        UlOp& ex = p->ops[p->ops.size() - 3];
+        std::vector<uint8_t> img(ul_ir_pack(nullptr, nullptr, nullptr, in.C, mid, cout, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ex.ir_off));
+        ul_ir_pack(w1, wd, w2, in.C, mid, cout, s1.data(), b1.data(), s_d.data(), b_d.data(), s2.data(), b2.data(), img.data(), ex.ir_off);
+        CHK(hipMalloc((void**)&ex.d_ir, img.size()));
+        CHK(hipMemcpy(ex.d_ir, img.data(), img.size(), hipMemcpyHostToDevice));
+        p->ir_bytes += img.size();
+        return 0;
     }
     // DoubleConvDW (unet.py:38-49): IR(in -> out, stride), IR(out -> out, 1, residual); the result lands at (out_buf, out_ld, out_coff)
     int dconv(const std::string& pre, const Tn& in, int cout, int stride, int out_buf, int out_ld, int out_coff, Tn* out) {
@@ -338,12 +409,23 @@ int ul_conv_as_own_calls(const UlOp& op, const ConvIO& io, const std::vector<int
 int ul_enqueue(ltk_engine* e, UlProgram& p, int nf, hipStream_t s, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32,
                const UlGroupTab* gtab = nullptr, const std::vector<int>* own = nullptr) {
     std::string err;
-    int opi = -1;
-    for (UlOp& op : p.ops) {
-        ++opi;
+    // knob UL_FUSE_IR: a per-avatar pass runs an inverted residual that has a fused operand image as ONE ul_ir_kernel launch over all its
+    // frames (one summation order whatever the frame count: nothing for ul_conv_as_own_calls to do), from the expand conv's input view
+    // into the project conv's output view; U_E1 / U_E2 are not touched.  The grouped path ignores the knob.
+    const bool fuse = !gtab && knob(K_UL_FUSE_IR) != 0;
+    for (size_t at = 0; at < p.ops.size(); ++at) {
+        UlIrIO fio;
+        const bool fused = fuse && ul_ir_io(p, at, nf, e->ul_buf, &fio);
+        const UlOp& head = p.ops[at];
+        if (fused) at += 2;
+        UlOp& op = p.ops[at];              // fused: the project conv, whose name and output view the launch has
+        const int opi = (int)at;
         const f16* x = op.in_buf >= 0 ? e->ul_buf[op.in_buf] : nullptr;
         f16* y = e->ul_buf[op.out_buf];
-        switch (op.type) {
+        if (fused) {
+            const int rc = launch_ul_ir(ul_ir_weights(head.d_ir, head.ir_off), fio, s, nullptr, &err);
+            if (rc) return conv_status(rc, op.name + ": " + err);
+        } else switch (op.type) {
         case UL_IN:
             if (gtab) launch_ul_in_grouped(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, gtab, y, s);
             else launch_ul_in(bank ? &e->ul_tab->faces : nullptr, d_img6, nf, p.inw, y, s);
@@ -738,16 +820,17 @@ int ltk_debug_ul_merge_plan(const int* avatar, const int* batch, int nreq, int c
 int ltk_ultralight_op_count(ltk_engine* e, int avatar_id) {
     if (!e) return 0;
     const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
-    return ap && ap->prog ? (int)ap->prog->ops.size() : 0;
+    return ap && ap->prog ? (int)ul_listing(*ap->prog).size() : 0;
 }
 
 int ltk_ultralight_op_name(ltk_engine* e, int avatar_id, int op, char* buf, int buf_len, int* type) {
     if (!e || !buf || buf_len <= 0) return fail(LTK_E_INVALID, "bad arguments");
     const std::shared_ptr<UlAvatar> ap = find_ul_avatar(e, avatar_id);
     if (!ap || !ap->prog) return fail(LTK_E_STATE, "unknown Ultralight avatar id");
-    if (op < 0 || op >= (int)ap->prog->ops.size()) return fail(LTK_E_INVALID, "no such op");
-    snprintf(buf, (size_t)buf_len, "%s", ap->prog->ops[op].name.c_str());
-    if (type) *type = ap->prog->ops[op].type == UL_CONV ? 0 : 9 + ap->prog->ops[op].type;      // 0 as ltk_musetalk_op_name; 10.. its own
+    const std::vector<std::pair<std::string, int>> ls = ul_listing(*ap->prog);      // follows knob UL_FUSE_IR
+    if (op < 0 || op >= (int)ls.size()) return fail(LTK_E_INVALID, "no such op");
+    snprintf(buf, (size_t)buf_len, "%s", ls[op].first.c_str());
+    if (type) *type = ls[op].second == UL_CONV ? 0 : 9 + ls[op].second;      // 0 as ltk_musetalk_op_name; 10.. its own
     return LTK_OK;
 }
 

@@ -340,6 +340,46 @@ class Engine:
         return {"kernel": rep.kernel.decode(), "tile_px": rep.PXW, "tile_co": rep.NBT, "ksteps": rep.T, "blocks": rep.grid,
                 "grid": (rep.items >> 16, rep.items & 0xFFFF, rep.NB)}
 
+    @staticmethod
+    def _ul_ir_report(rep) -> dict:
+        return {"accepted": bool(rep.accepted), "reason": rep.reason.decode(), "kernel": rep.kernel.decode(), "Ho": rep.Ho, "Wo": rep.Wo,
+                "tile": (rep.TH, rep.TW), "MC": rep.MC, "chunks": rep.chunks, "hidden_px": rep.hidden_px, "lds_bytes": rep.lds_bytes,
+                "lds_limit": rep.lds_limit, "grid": (rep.grid_x, rep.grid_y, rep.grid_z), "blocks": rep.blocks, "threads": rep.threads}
+
+    @staticmethod
+    def ul_ir_plan(N, H, W, Cin, mid, Cout, stride=1, has_res=False, tap=False, views: Optional[dict] = None) -> dict:
+        """What the fused inverted residual's planner decides (ltk_debug_ul_ir_plan; no GPU, no engine): accepted or refused with the
+        reason as text, the instantiation's name, the tile, MC and chunk count, hidden pixels per tile, LDS bytes, grid and blocks."""
+        opts = _lib.ConvOpts()
+        for key, v in (views or {}).items():
+            setattr(opts, key, int(v))
+        rep = _lib.UlIrReport()
+        _lib.check(_lib.load().ltk_debug_ul_ir_plan(int(N), int(H), int(W), int(Cin), int(mid), int(Cout), int(stride), int(bool(has_res)),
+                                                    int(bool(tap)), C.byref(opts), C.byref(rep)))
+        return Engine._ul_ir_report(rep)
+
+    def ul_ir_f16(self, d_x_ptr: int, N, H, W, Cin, stride, w1: np.ndarray, wd: np.ndarray, w2: np.ndarray, affine1=(None, None),
+                  affine_d=(None, None), affine2=(None, None), d_res_ptr: int = 0, d_y_ptr: int = 0, views: Optional[dict] = None,
+                  d_e1_ptr: int = 0, d_e2_ptr: int = 0) -> dict:
+        """One inverted residual in one launch (include/ltk.h: ltk_ul_ir_f16): w1 (mid, Cin), wd (mid, 3, 3), w2 (Cout, mid); affine* =
+        (scale, shift) fp32 or None; views as ul_gconv_f16; d_e1_ptr / d_e2_ptr: the tap buffers.  -> the planner's report."""
+        a1 = np.ascontiguousarray(w1, dtype=np.float32)
+        ad = np.ascontiguousarray(wd, dtype=np.float32)
+        a2 = np.ascontiguousarray(w2, dtype=np.float32)
+        mid, Cout = int(a1.shape[0]), int(a2.shape[0])
+        keep = [np.ascontiguousarray(v, dtype=np.float32) if v is not None else None for pair in (affine1, affine_d, affine2) for v in pair]
+        ptr = lambda v: v.ctypes.data if v is not None else None
+        opts = _lib.ConvOpts()
+        for key, v in (views or {}).items():
+            setattr(opts, key, int(v))
+        rep = _lib.UlIrReport()
+        _lib.check(self._lib.ltk_ul_ir_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(H), int(W), int(Cin), mid, Cout, int(stride),
+                                           a1.ctypes.data, ad.ctypes.data, a2.ctypes.data, *[ptr(v) for v in keep],
+                                           C.c_void_p(d_res_ptr) if d_res_ptr else None, C.c_void_p(d_y_ptr), C.byref(opts),
+                                           C.c_void_p(d_e1_ptr) if d_e1_ptr else None, C.c_void_p(d_e2_ptr) if d_e2_ptr else None,
+                                           C.byref(rep)))
+        return Engine._ul_ir_report(rep)
+
     def ultralight_paste_back(self, avatar_id: int, idx: int, d_pred_ptr: int, out: np.ndarray, stream: int = 0):
         """out: C-contiguous uint8 (H,W,3) host array, filled in place (ultralight_avatar.py:173-184)."""
         _lib.check(self._lib.ltk_ultralight_paste_back(self._h, int(avatar_id), int(idx), C.c_void_p(d_pred_ptr), out.ctypes.data, 0,
@@ -364,7 +404,8 @@ class Engine:
 
     def ultralight_ops(self, avatar_id: int):
         """[(tap name, type)] of the avatar's launch program in execution order; type 0 dense conv (as musetalk_ops()), 10 depthwise
-        conv, 11 upsample, 12 input conv, 13 feature pack, 14 head."""
+        conv, 11 upsample, 12 input conv, 13 feature pack, 14 head, 15 a fused inverted residual (knob UL_FUSE_IR: listed once, under its
+        project conv's name; the list follows the knob's current value)."""
         out = []
         buf = C.create_string_buffer(160)
         t = C.c_int()
