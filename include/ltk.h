@@ -454,6 +454,23 @@ int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6,
  * such a pass and ltk_debug_get reports them as absent. */
 int ltk_ultralight_op_count(ltk_engine* e, int avatar_id);
 int ltk_ultralight_op_name(ltk_engine* e, int avatar_id, int op, char* buf, int buf_len, int* type);
+/* The same listing with its geometry, on the host alone (no engine, no GPU): the architecture is one for every avatar.  fuse 0 / 1: the
+ * listing with knob UL_FUSE_IR off / on; -1: as the knob stands.  Per launch: name and type as above; the input, output and residual
+ * views - arena buffer index (-1: none; the input conv, the feature pack and the head read or write the caller's tables), channel pitch
+ * `ld` and first channel `coff` of the view - and the maps H x W -> Ho x Wo; C / Creal: channels written in the layout / of the
+ * reference's tensor; cin: layout channels read; k, stride, pad, relu.  A fused inverted residual (type 15) has its expand conv's input
+ * view, map and cin, its depthwise conv's k / stride / pad and its project conv's everything else.  buf_halfs[b]: fp16 elements per frame
+ * of arena buffer b (ltk_ultralight_info's bytes per frame = 2 * their sum).  LTK_E_INVALID when an array is NULL or too small (96 ops
+ * and 12 buffers are enough). */
+typedef struct ltk_ul_op_info {
+    char name[64];
+    int type;
+    int in_buf, in_ld, in_coff, H, W;
+    int out_buf, out_ld, out_coff, Ho, Wo;
+    int res_buf, res_ld, res_coff;
+    int C, Creal, cin, k, stride, pad, relu;
+} ltk_ul_op_info;
+int ltk_debug_ultralight_program(int fuse, ltk_ul_op_info* ops, int max_ops, int* n_ops, uint64_t* buf_halfs, int max_bufs, int* n_bufs);
 /* average milliseconds of one pass of `frames` frames as ltk_ultralight_infer enqueues it (replayed graph under knob GRAPH), on
  * dummy inputs, and the MACs (dense + depthwise + head) it executes */
 int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, float* ms_per_pass, double* macs_per_pass);

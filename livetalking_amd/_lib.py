@@ -71,6 +71,12 @@ class UlIrReport(C.Structure):
         "threads")]
 
 
+class UlOpInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, C.c_int) for n in (
+        "type", "in_buf", "in_ld", "in_coff", "H", "W", "out_buf", "out_ld", "out_coff", "Ho", "Wo", "res_buf", "res_ld", "res_coff",
+        "C", "Creal", "cin", "k", "stride", "pad", "relu")]
+
+
 class NormOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
 
@@ -152,6 +158,8 @@ SYMBOLS = {
                                               C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "ltk_ultralight_op_count": (C.c_int, [C.c_void_p, C.c_int]),
     "ltk_ultralight_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
+    "ltk_debug_ultralight_program": (C.c_int, [C.c_int, C.POINTER(UlOpInfo), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int,
+                                               C.POINTER(C.c_int)]),
     "ltk_hubert_op_count": (C.c_int, [C.c_void_p]),
     "ltk_hubert_op_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),

@@ -709,7 +709,9 @@ int ltk_ultralight_forward_host(ltk_engine* e, int avatar_id, const float* img6,
         for (int i = 0; i < nf; ++i) mp.p[i] = (const float*)d_feat.p + (size_t)i * 16 * 1024;
         launch_upload_tables(nullptr, &mp, nullptr, nf, e->ul_tab, e->compute);
         CHK(hipGetLastError());
-        const int rc = ul_pass(e, *ap, nf, false, (const float*)d_img.p, false, (float*)d_pred.p);
+        UlPassArgs args;
+        args.d_img6 = (const float*)d_img.p; args.d_pred_f32 = (float*)d_pred.p;
+        const int rc = ul_pass(e, *ap, nf, args);
         const hipError_t se = hipStreamSynchronize(e->compute);
         if (rc) return rc;
         if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight forward: ") + hipGetErrorString(se));
@@ -736,15 +738,15 @@ int ltk_ultralight_time(ltk_engine* e, int avatar_id, int frames, int iters, flo
     for (int i = 0; i < frames; ++i) { fp.p[i] = ap->d_face; mp.p[i] = (const float*)d_feat.p; op.p[i] = (uint8_t*)d_frames.p + (size_t)i * kUlRes * kUlRes * 3; }
     launch_upload_tables(&fp, &mp, &op, frames, e->ul_tab, e->compute);
     CHK(hipGetLastError());
-    int rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr);      // eager
-    if (!rc) rc = ul_pass(e, *ap, frames, true, nullptr, true, nullptr); // captures under knob GRAPH
+    int rc = ul_pass(e, *ap, frames);      // eager
+    if (!rc) rc = ul_pass(e, *ap, frames); // captures under knob GRAPH
     float ms = 0.f;
-    if (!rc) rc = time_iters(e->compute, iters, [&]() { return ul_pass(e, *ap, frames, true, nullptr, true, nullptr); }, &ms);
+    if (!rc) rc = time_iters(e->compute, iters, [&]() { return ul_pass(e, *ap, frames); }, &ms);
     const hipError_t se = hipStreamSynchronize(e->compute);       // before the scratch buffers go
     if (rc) return rc;
     if (se != hipSuccess) return fail(LTK_E_HIP, std::string("ultralight pass: ") + hipGetErrorString(se));
     *ms_per_pass = ms / iters;
-    if (macs_per_pass) *macs_per_pass = ul_macs_per_frame(*ap) * frames;
+    if (macs_per_pass) *macs_per_pass = ul_macs_per_frame() * frames;
     return LTK_OK;
 }
 

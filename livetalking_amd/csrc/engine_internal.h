@@ -133,26 +133,20 @@ struct MtAvatar {
 
 // Ultralight avatar (avatars/ultralight_avatar.py:63-81): the model is per avatar, so the launch program (ultralight.hip) lives with
 // the bank.  boxes = coords.pkl as (x1, y1, x2, y2).
-struct UlProgram;
+struct UlProgram;                                     // ultralight.hip: the avatar's operands, one record per op of the architecture
 struct UlGroupTab;                                    // ul_gconv.h
-void ul_program_delete(UlProgram* p);                 // ultralight.hip
 struct UlAvatar {
-    UlProgram* prog = nullptr;
+    std::unique_ptr<UlProgram> prog;
     uint8_t* d_face = nullptr;       // [n][168][168][3]
     uint8_t* d_full = nullptr;       // [n][H][W][3]
     std::vector<int32_t> boxes;
     int n = 0, H = 0, W = 0;
     int device = 0;
     int id = 0;
-    UlAvatar() = default;
+    UlAvatar();                      // ultralight.hip, where UlProgram is complete
     UlAvatar(const UlAvatar&) = delete;
     UlAvatar& operator=(const UlAvatar&) = delete;
-    ~UlAvatar() {
-        (void)hipSetDevice(device);
-        if (d_face) (void)hipFree(d_face);
-        if (d_full) (void)hipFree(d_full);
-        ul_program_delete(prog);
-    }
+    ~UlAvatar();                     // selects the device, frees the banks, then the program's operands
 };
 constexpr int kUlBufs = 12;           // activation buffers of the Ultralight program (ultralight.hip UlBuf)
 
@@ -335,7 +329,6 @@ struct ltk_engine {
     int ul_frames = 0;
     DevTables* ul_tab = nullptr;          // per-frame bank crop / HuBERT chunk / output pointers of the pass being enqueued
     UlGroupTab* ul_gtab = nullptr;        // per-frame weight records of a grouped pass (ul_gconv.h), uploaded like ul_tab
-    UlProgram* ul_geo = nullptr;          // the grouped path's geometry-only program, built at the first grouped pass
     size_t ul_frame_bytes = 0;            // arena bytes per frame
     // merged per-avatar passes (ul_pass with `own`): the run lengths of the frames' own-call frame counts -> the number such a pass's
     // captured graph is keyed by (kUlMaxComps of them; a pass of a composition past that runs uncaptured)
@@ -616,13 +609,18 @@ int launch_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, const flo
 int launch_prefetch(ltk_engine* e, int nf, int slot);
 int run_program(ltk_engine* e, MtGraph* prog, int nf);                                                      // mt_engine.hip
 // ultralight.hip.  ul_pass: one pass over frames [0, nf) of the arena, the per-frame tables already in e->ul_tab, under e->mu.
-// bank: the faces table holds uint8 bank crops (else d_img6: float32 NCHW test input); u8_out: the outs table holds the frame
-// destinations; d_pred_f32 (test hook): float32 NCHW sigmoid output.  The product configuration replays from e->prog_graphs.
-// own (ltk_ultralight_infer_merged): own[i] = the frame count of the ltk_ultralight_infer pass that would carry frame i on its own
-// request's behalf.  Every conv then sums a frame's channels in the order that pass would (conv3's split-K factor follows a launch's
-// frame count), so a frame's bytes do not depend on which requests share its pass; nullptr or all == nf: the plain pass.
-int ul_pass(ltk_engine* e, UlAvatar& a, int nf, bool bank, const float* d_img6, bool u8_out, float* d_pred_f32, const std::vector<int>* own = nullptr);
-double ul_macs_per_frame(const UlAvatar& a);
+// The defaults are the product configuration, which replays from e->prog_graphs.
+struct UlPassArgs {
+    const float* d_img6 = nullptr;          // source: null = the uint8 bank crops of the faces table; else (test hook) float32 NCHW input
+    float* d_pred_f32 = nullptr;            // sink: null = the frame destinations of the outs table; else (test hook) float32 NCHW sigmoid output
+    const UlGroupTab* gtab = nullptr;       // a grouped pass: every frame's operands through this table (set by ultralight.hip alone)
+    // own[i] = the frame count of the pass that would carry frame i if its request came alone.  Every conv then sums a frame's channels
+    // in the order that pass would (conv3's split-K factor follows a launch's frame count), so a frame's bytes do not depend on which
+    // requests share its pass; nullptr or all == nf: the plain pass.
+    const std::vector<int>* own = nullptr;
+};
+int ul_pass(ltk_engine* e, const UlAvatar& a, int nf, UlPassArgs args = UlPassArgs());
+double ul_macs_per_frame();
 void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
 // ltk_ultralight_infer_merged's call plan (ultralight.hip ul_merge_plan; seen through ltk_debug_ul_merge_plan): which frames of which
 // request share a pass.  A span = frames [first, first + count) of request `req` at frames [at, at + count) of the pass.

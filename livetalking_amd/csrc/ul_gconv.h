@@ -13,7 +13,7 @@
 
 namespace ltk {
 
-constexpr int kUlMaxOps = 96;          // ops of the Ultralight program (86: ultralight.hip build_ul_program)
+constexpr int kUlMaxOps = 96;          // ops of the Ultralight program (86: ultralight.hip build_ul_arch)
 
 struct UlGroupOp {
     const f16* w;                      // dense conv: packed fp16 weights (ul_gconv_pack)

@@ -320,6 +320,18 @@ class Engine:
             plan[sp[j]][3].append((sr[j], sf[j], sc[j], sa[j]))
         return plan
 
+    @staticmethod
+    def ul_program(fuse: int = -1, max_ops: int = 96, max_bufs: int = 12) -> dict:
+        """ltk_debug_ultralight_program (no GPU, no engine): the launches of a per-avatar pass with the fused inverted residual off (0),
+        on (1) or as knob UL_FUSE_IR stands (-1) -> {"ops": [dict of include/ltk.h ltk_ul_op_info's fields], "buf_halfs": [...]}."""
+        ops = (_lib.UlOpInfo * max(int(max_ops), 1))()
+        halfs = (C.c_uint64 * max(int(max_bufs), 1))()
+        n_ops, n_bufs = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.load().ltk_debug_ultralight_program(int(fuse), ops, int(max_ops), C.byref(n_ops), halfs, int(max_bufs), C.byref(n_bufs)))
+        fields = [n for n, _ in _lib.UlOpInfo._fields_]
+        return {"ops": [{n: (getattr(o, n).decode() if n == "name" else getattr(o, n)) for n in fields} for o in ops[:n_ops.value]],
+                "buf_halfs": [int(h) for h in halfs[:n_bufs.value]]}
+
     def ul_gconv_f16(self, d_x_ptr: int, N, H, W, Cin, weight: np.ndarray, sets: Sequence[int], k: int = 1, stride: int = 1, pad: int = 0,
                      scale=None, shift=None, d_res_ptr: int = 0, relu: bool = False, d_y_ptr: int = 0, views: Optional[dict] = None):
         """The grouped dense conv on its own (include/ltk.h: ltk_ul_gconv_f16): weight (n_sets, Cout, Cin, k, k), scale / shift

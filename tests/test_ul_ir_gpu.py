@@ -148,10 +148,7 @@ class one_summation_order:
         Engine.set_knob("SPLITK", 1)
 
 
-FUSED = ["down1.maxpool_conv.0.double_conv.0", "down1.maxpool_conv.0.double_conv.1", "down2.maxpool_conv.0.double_conv.0",
-         "down2.maxpool_conv.0.double_conv.1", "down3.maxpool_conv.0.double_conv.0", "audio_model.conv1", "audio_model.conv2",
-         "up2.conv.double_conv.0", "up2.conv.double_conv.1", "up3.conv.double_conv.0", "up3.conv.double_conv.1",
-         "up4.conv.double_conv.0", "up4.conv.double_conv.1"]
+FUSED = ref.FUSED            # (tests/test_ul_program_host.py checks the same list without a GPU)
 
 
 @pytest.fixture(scope="module")

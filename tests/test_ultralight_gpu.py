@@ -233,6 +233,15 @@ def test_infer_gathers_crops_masks_and_replays(eng, sd):
             mx, _, share = ref.frame_stats(got, ref.frames_u8(host))
             assert mx <= 1 and share < 0.02, (mx, share)
         assert not np.array_equal(runs[0][0][0], runs[0][1][0])
+        # the arena and an avatar's listing are the pure architecture's (Engine.ul_program: no GPU, no avatar)
+        from livetalking_amd.engine import Engine
+        assert eng.ultralight_info()["bytes_per_frame"] == 2 * sum(Engine.ul_program(0)["buf_halfs"])
+        try:
+            for knob in (0, 1):
+                Engine.set_knob("UL_FUSE_IR", knob)
+                assert eng.ultralight_ops(b) == [(o["name"], o["type"]) for o in Engine.ul_program(knob)["ops"]]
+        finally:
+            Engine.set_knob("UL_FUSE_IR", 0)
     finally:
         eng.release_avatar(a)
         eng.release_avatar(b)

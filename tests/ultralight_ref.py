@@ -218,3 +218,98 @@ def op_names():
         out.append(p + ".up")
         dconv(p + ".conv")
     return out + ["outc.conv"]
+
+
+# ---------------------------------------------------------------------------------------------------- the launch program, symbolically
+# the inverted residuals the program runs as one launch under knob UL_FUSE_IR (input map >= 32 x 32 and the planner accepts them)
+FUSED = ["down1.maxpool_conv.0.double_conv.0", "down1.maxpool_conv.0.double_conv.1", "down2.maxpool_conv.0.double_conv.0",
+         "down2.maxpool_conv.0.double_conv.1", "down3.maxpool_conv.0.double_conv.0", "audio_model.conv1", "audio_model.conv2",
+         "up2.conv.double_conv.0", "up2.conv.double_conv.1", "up3.conv.double_conv.0", "up3.conv.double_conv.1",
+         "up4.conv.double_conv.0", "up4.conv.double_conv.1"]
+
+
+def _c16(c):
+    return (c + 15) // 16 * 16
+
+
+def expected_reads(fuse: bool):
+    """What every launch reads, from the layer tables alone: {op name: (input, residual)}, each a list of (producer, layout channels)
+    in channel order (torch.cat order); [] where the op reads the caller's tables or has no residual."""
+    reads = {}
+
+    def ir(p, src, cout, residual):
+        mid = 2 * sum(c for _, c in src) if src else 12           # (inc: 6 input channels from the bank crop)
+        res = src if residual else []
+        if fuse and p in FUSED:
+            reads[p + ".conv.6"] = (src, res)
+        else:
+            reads[p + ".conv.0"] = (src, [])
+            reads[p + ".conv.3"] = ([(p + ".conv.0", _c16(mid))], [])
+            reads[p + ".conv.6"] = ([(p + ".conv.3", _c16(mid))], res)
+        return [(p + ".conv.6", cout)]
+
+    def dconv(p, src, cout):
+        return ir(p + ".double_conv.1", ir(p + ".double_conv.0", src, cout, False), cout, True)
+
+    x = ir("inc.inconv.0", [], 32, False)
+    skips = [x]
+    for p, _, cout, _ in DOWN:
+        x = dconv(p, x, cout)
+        skips.append(x)
+    reads["audio_feat"] = ([], [])
+    a = [("audio_feat", 16)]
+    for item in AUDIO:
+        if item[0] == "ir":
+            a = ir(item[1], a, item[3], item[4])
+        else:
+            reads[item[1]] = (a, [])
+            a = [(item[1], item[4])]
+    x = skips.pop() + a
+    for p, _, cout, _ in FUSE:
+        x = dconv(p, x, cout)
+    for p, _, cout in UP:
+        reads[p + ".up"] = (x, [])
+        x = dconv(p + ".conv", [(p + ".up", x[0][1])] + skips.pop(), cout)
+    reads["outc.conv"] = (x, [])
+    return reads
+
+
+def program_reads(ops):
+    """The same from a listing (Engine.ul_program(...)["ops"]), walked on the host: every op stamps its name on the channels of its
+    output view; a reader collects the stamps on its input and residual views.  A buffer is one tensor of (ld, H, W) at a time: a write
+    in another shape clobbers it, a read in another shape sees "<stale>"."""
+    bufs = {}           # buffer -> [(ld, H, W), {channel: stamp}]
+
+    def read(buf, ld, coff, n, H, W):
+        if buf < 0:
+            return []
+        shape, ch = bufs.get(buf, (None, {}))
+        runs = []
+        for c in range(coff, coff + n):
+            s = ch.get(c, "<unwritten>") if shape == (ld, H, W) else "<stale>"
+            if runs and runs[-1][0] == s:
+                runs[-1][1] += 1
+            else:
+                runs.append([s, 1])
+        return [(s, k) for s, k in runs]
+
+    out = {}
+    for o in ops:
+        assert o["name"] not in out, o["name"]
+        out[o["name"]] = (read(o["in_buf"], o["in_ld"], o["in_coff"], o["cin"], o["H"], o["W"]),
+                          read(o["res_buf"], o["res_ld"], o["res_coff"], o["C"], o["Ho"], o["Wo"]))
+        if o["out_buf"] >= 0:
+            shape = (o["out_ld"], o["Ho"], o["Wo"])
+            if bufs.get(o["out_buf"], (None,))[0] != shape:
+                bufs[o["out_buf"]] = [shape, {}]
+            for c in range(o["out_coff"], o["out_coff"] + o["C"]):
+                bufs[o["out_buf"]][1][c] = o["name"]
+    return out
+
+
+def check_dataflow(ops, fuse: bool):
+    """AssertionError unless every launch of the listing reads exactly the producers the layer tables imply."""
+    got, want = program_reads(ops), expected_reads(fuse)
+    assert list(got) == list(want), "op order"
+    for name in want:
+        assert got[name] == (list(map(tuple, want[name][0])), list(map(tuple, want[name][1]))), (name, got[name], want[name])
