@@ -334,6 +334,22 @@ int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n);
 int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows,
                      void* d_out, void* stream);
 
+/* The live steps of nreq concurrent MuseTalk sessions in one call (scheduler.py kind "whisper").  Every request is what
+ * ltk_whisper_step takes.  Requests are forwarded in runs of at most 16 in request order, every run of more than one as the images of
+ * ONE run of a 16-clip encoder program over the loaded encoder's packed weights: one log-mel launch pair, one ~60-launch program
+ * (replayed from a captured graph from its second sight of a clip count) and one chunk gather for all of them.  No clip's spectral
+ * maximum, attention or chunk clamp sees another clip, and a clip's log-mel features are the single step's bit for bit.  The 16-clip
+ * program and its staging are built on the first batched run (ltk_whisper_batch_info reports their size); a run of one request runs
+ * as ltk_whisper_step does, and nreq == 1 IS ltk_whisper_step.  All requests are validated before the first launch (LTK_E_INVALID
+ * names the request; LTK_E_STATE without a loaded encoder); returns when every d_out is complete; an error return leaves nothing in
+ * flight. */
+typedef struct ltk_whisper_req {
+    const float* pcm; int n_samples;              /* host, 0 < n_samples <= 479000 */
+    int batch, first_row, row_step, rows;         /* as ltk_whisper_step; 0 < rows <= 64 */
+    void* d_out;                                  /* device float32 [batch][rows*5][384] */
+} ltk_whisper_req;
+int ltk_whisper_step_batch(ltk_engine* e, const ltk_whisper_req* reqs, int nreq);
+
 /* =========================== HuBERT-large audio features (Ultralight, avatars/ultralight/audio2feature.py) =========================== */
 
 /* audio2feature.py:9-11: transformers HubertModel in the configuration of facebook/hubert-large-ls960-ft (feat_extract_norm "layer",
@@ -386,6 +402,15 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
 /* named tensor of the last Whisper step as [C][T] float32: "input_features", "hidden_states.0".."hidden_states.4",
  * or an op name ("conv1", "layers.0.self_attn.out_proj", ...) */
 int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats);
+/* ... of clip `clip` of the batched run (ltk_whisper_step_batch) that ran last, under the same names: [C][T] float32 */
+int ltk_whisper_debug_get_clip(ltk_engine* e, const char* name, int clip, float* out, size_t n_floats);
+/* clips per batched program run, 1 once the batched program is built (0 before the first batched run), and its activation bytes at full
+ * capacity (0 until built); any may be NULL */
+int ltk_whisper_batch_info(ltk_engine* e, int* capacity, int* built, size_t* activation_bytes);
+/* How ltk_whisper_step_batch cuts a call of nreq requests, on the host alone (no engine, no GPU): run_of[r] / slot_of[r] = the run that
+ * carries request r and its place in it, run_batched[i] = 1 if run i is one batched program run (0: the single-clip path), runs in
+ * execution order, *n_runs of them (all arrays hold nreq entries) */
+int ltk_debug_whisper_batch_plan(int nreq, int* run_of, int* slot_of, int* run_batched, int* n_runs);
 
 /* named tensor of the HuBERT program that ran last as [C][T] float32: an op name (ltk_hubert_op_name; an attention's output is
  * "<op>.attn"), or "input_values": the normalised waveform fp32 [n_samples] of that clip */

@@ -50,6 +50,11 @@ class HubertReq(C.Structure):
                 ("rows", C.c_int), ("d_out", C.c_void_p)]
 
 
+class WhisperReq(C.Structure):
+    _fields_ = [("pcm", C.c_void_p), ("n_samples", C.c_int), ("batch", C.c_int), ("first_row", C.c_int), ("row_step", C.c_int),
+                ("rows", C.c_int), ("d_out", C.c_void_p)]
+
+
 class EgressReq(C.Structure):
     _fields_ = [("source", C.c_int), ("avatar", C.c_int), ("idx", C.c_int), ("d_pred", C.c_void_p), ("h_frame", C.c_void_p),
                 ("speaking", C.c_int), ("alpha", C.c_double), ("keep", C.c_int), ("format", C.c_int), ("chroma", C.c_int)]
@@ -147,6 +152,10 @@ SYMBOLS = {
     "ltk_whisper_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int]),
     "ltk_whisper_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_whisper_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),
+    "ltk_whisper_step_batch": (C.c_int, [C.c_void_p, C.POINTER(WhisperReq), C.c_int]),
+    "ltk_whisper_debug_get_clip": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ltk_whisper_batch_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "ltk_debug_whisper_batch_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ltk_hubert_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int]),
     "ltk_hubert_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "ltk_hubert_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -9,9 +9,18 @@ float32 [B][50][384] instead of a list of numpy arrays.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from ...hostshim import BaseASR
+
+# 1: the live steps of concurrent sessions go through the engine's "whisper" scheduler and share one encoder run per tick
+# (Engine.whisper_step_batch; a lone session's request goes straight down as today's whisper_step); 0: every step is its own
+# whisper_step call.  Read once.  On by default: profiles/whisper_batch_step.txt (scripts/whisper_batch_time.py) shows the batched call
+# no slower than the separate calls from 2 clips on (0.597 against 1.006 ms at 2, 2.313 against 8.093 ms at 16).
+_WHISPER_BATCH_DEFAULT = "1"
+_WHISPER_BATCH = os.environ.get("LTK_WHISPER_BATCH", _WHISPER_BATCH_DEFAULT) != "0"
 
 
 # what `whisper_logmel_kernel` computes = WhisperFeatureExtractor's defaults = whisper-tiny's preprocessor_config.json
@@ -70,6 +79,10 @@ class WhisperASR(BaseASR):
         feat = torch.empty((self.batch_size, 50, 384), dtype=torch.float32, device=self.engine.torch_device)
         # whisper.py:71-73: audio_feat_win [0,5], start l/2, multiplier 2 -> rows [2*(i + l/2), +10)
         first_row = int((self.stride_left_size / 2) * 2)
-        self.engine.whisper_step(inputs, self.batch_size, first_row, feat.data_ptr(), row_step=2, rows=10)
+        if _WHISPER_BATCH:
+            from ...scheduler import get_scheduler
+            get_scheduler(self.engine, "whisper").submit((inputs, self.batch_size, first_row, 2, 10, feat.data_ptr()), 1)
+        else:
+            self.engine.whisper_step(inputs, self.batch_size, first_row, feat.data_ptr(), row_step=2, rows=10)
         self.feat_queue.put(feat)
         self.frames = self.frames[-(self.stride_left_size + self.stride_right_size):]

@@ -101,7 +101,11 @@ void ltk_engine_destroy(ltk_engine* e) {
     e->prog_graphs.drop();
     ul_unload(e);
     if (e->mt) mt_graph_delete(e->mt);
+    if (e->whisper_b) mt_graph_delete(e->whisper_b);      // holds copies of e->whisper's weight handles and frees none of them
     if (e->whisper) mt_graph_delete(e->whisper);
+    if (e->d_wbpcm) (void)hipFree(e->d_wbpcm);
+    if (e->d_wblogspec) (void)hipFree(e->d_wblogspec);
+    if (e->d_wbgmax) (void)hipFree(e->d_wbgmax);
     hubert_unload(e);
     if (e->vae_enc) mt_graph_delete(e->vae_enc);
     if (e->d_wbasis) (void)hipFree(e->d_wbasis);

@@ -1052,6 +1052,42 @@ int ltk_whisper_debug_get(ltk_engine* e, const char* name, float* out, size_t n_
     return read_named(e, e->whisper, "Whisper", name, 1, "", out, n_floats);
 }
 
+int ltk_whisper_debug_get_clip(ltk_engine* e, const char* name, int clip, float* out, size_t n_floats) {
+    if (!e || !name || !out || clip < 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->whisper_b || !e->whisper_b_nf) return fail(LTK_E_STATE, "no batched Whisper run yet");
+    if (clip >= e->whisper_b_nf) return fail(LTK_E_INVALID, "the last batched run carried " + std::to_string(e->whisper_b_nf) + " clips");
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->whisper_b, name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no Whisper tensor named ") + name);
+    const size_t cnt = (size_t)C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats per clip");
+    return read_cb16(e, t + (size_t)clip * ld * H * W, 1, C, ld, coff, H, W, out);
+}
+
+int ltk_whisper_batch_info(ltk_engine* e, int* capacity, int* built, size_t* activation_bytes) {
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
+    if (capacity) *capacity = kWhisperBatchClips;
+    if (built) *built = e->whisper_b ? 1 : 0;
+    if (activation_bytes) *activation_bytes = e->whisper_b ? mt_activation_bytes(e->whisper_b) : 0;
+    return LTK_OK;
+}
+
+int ltk_debug_whisper_batch_plan(int nreq, int* run_of, int* slot_of, int* run_batched, int* n_runs) {
+    if (nreq <= 0 || !run_of || !slot_of || !run_batched || !n_runs) return fail(LTK_E_INVALID, "bad arguments");
+    const std::vector<WhisperRun> runs = whisper_batch_plan(nreq, kWhisperBatchClips);
+    for (size_t i = 0; i < runs.size(); ++i) {
+        run_batched[i] = runs[i].batched ? 1 : 0;
+        for (int j = 0; j < runs[i].count; ++j) { run_of[runs[i].first + j] = (int)i; slot_of[runs[i].first + j] = j; }
+    }
+    *n_runs = (int)runs.size();
+    return LTK_OK;
+}
+
 // ---------------------------------------------------------------- HuBERT: the program's tensors and ops, and its kernels on their own
 int ltk_hubert_debug_get(ltk_engine* e, const char* name, float* out, size_t n_floats) {
     if (!e || !name || !out) return fail(LTK_E_INVALID, "bad arguments");

@@ -298,6 +298,13 @@ struct ltk_engine {
     float* d_wlogspec = nullptr;          // [80][3000]
     float* d_wpcm = nullptr;              // staging, 30 s
     int* d_wgmax = nullptr;
+    // ltk_whisper_step_batch: the encoder for kWhisperBatchClips clips over `whisper`'s packed weights, built with its staging on the
+    // first batched run (an engine that serves one session never pays for it) and freed with the engine
+    MtGraph* whisper_b = nullptr;
+    int whisper_b_nf = 0;                 // clips of the batched run that ran last (debug read-back)
+    float* d_wbpcm = nullptr;             // [kWhisperBatchClips][480000] samples: clip c at c * 480000
+    float* d_wblogspec = nullptr;         // [kWhisperBatchClips][80][3000]
+    int* d_wbgmax = nullptr;              // [kWhisperBatchClips] maximum words
     float* d_pe = nullptr;                // PositionalEncoding table [50][384]
     float* d_mt_feat = nullptr;           // staging: fp32 [max_frames][50][384]
     float* d_mt_lat = nullptr;            // staging for the host-input hook: fp32 [max_frames][8][32][32]

@@ -200,27 +200,134 @@ int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n) {
     return LTK_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// under e->mu: one clip through the single-clip program (upload, log-mel, encoder, chunk gather), enqueued on the compute stream
+int whisper_step_locked(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out) {
+    hipStream_t s = e->compute;
+    CHK(hipMemcpyAsync(e->d_wpcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+    int cbt, cb0;
+    f16* mel = mt_latent_in(e->whisper, &cbt);
+    launch_whisper_logmel(e->d_wpcm, n_samples, e->d_wbasis, e->d_wlogspec, e->d_wgmax, mel, s);
+    int rc = run_program(e, e->whisper, 1);
+    if (rc) rc = fail(LTK_E_INVALID, std::string("whisper: ") + mt_graph_error(e->whisper));
+    if (!rc) {
+        WhisperStates st;
+        for (int i = 0; i < 5; ++i) { st.p[i] = mt_whisper_state(e->whisper, i, &cbt, &cb0); st.cb0[i] = cb0; }
+        launch_whisper_chunks(st, 1500, batch, first_row, row_step, rows, (float*)d_out, s);
+        if (hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, "whisper kernels failed to launch");
+    }
+    return rc;
+}
+
+// under e->mu, on the first batched run: the 16-clip program over the loaded encoder's weights and its staging.  All or nothing: a
+// failed build leaves the engine as it was (the single-clip path keeps working) and is tried again by the next batched run.
+int whisper_batch_build(ltk_engine* e) {
+    if (e->whisper_b) return LTK_OK;
+    MtGraph* g = mt_graph_new();
+    mt_set_sat_counter(g, e->d_sat);
+    const int brc = mt_build_whisper_batch_graph(g, e->whisper, kWhisperBatchClips);
+    float *pcm = nullptr, *logspec = nullptr;
+    int* gmax = nullptr;
+    const bool ok = !brc && hipMalloc((void**)&pcm, (size_t)kWhisperBatchClips * 480000 * sizeof(float)) == hipSuccess &&
+                    hipMalloc((void**)&logspec, (size_t)kWhisperBatchClips * 80 * 3000 * sizeof(float)) == hipSuccess &&
+                    hipMalloc((void**)&gmax, (size_t)kWhisperBatchClips * sizeof(int)) == hipSuccess;
+    if (!ok) {
+        const int rc = brc == -1 ? fail(LTK_E_INVALID, std::string("whisper: ") + mt_graph_error(g))
+                                 : fail(LTK_E_NOMEM, "whisper: the batched program's buffers could not be allocated");
+        (void)hipGetLastError();
+        if (pcm) (void)hipFree(pcm);
+        if (logspec) (void)hipFree(logspec);
+        if (gmax) (void)hipFree(gmax);
+        mt_graph_delete(g);
+        return rc;
+    }
+    e->whisper_b = g; e->d_wbpcm = pcm; e->d_wblogspec = logspec; e->d_wbgmax = gmax;
+    return LTK_OK;
+}
+
+// under e->mu: requests reqs[0..nf) as the nf images of one run of the batched program
+int whisper_batch_run_locked(ltk_engine* e, const ltk_whisper_req* reqs, int nf) {
+    int rc = whisper_batch_build(e);
+    if (rc) return rc;
+    hipStream_t s = e->compute;
+    // every clip by a pageable copy of its own, as the single step's: the runtime has read the caller's samples when the call returns,
+    // so no host staging block of ours can be refilled under a copy of the call in flight in front (the device block is stream-ordered)
+    WhisperClipTab ct = {};
+    for (int i = 0; i < nf; ++i) {
+        ct.n_samples[i] = reqs[i].n_samples; ct.pcm_off[i] = i * 480000;
+        CHK(hipMemcpyAsync(e->d_wbpcm + (size_t)ct.pcm_off[i], reqs[i].pcm, (size_t)reqs[i].n_samples * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    int cbt, cb0;
+    f16* mel = mt_latent_in(e->whisper_b, &cbt);
+    launch_whisper_logmel_batch(e->d_wbpcm, ct, nf, e->d_wbasis, e->d_wblogspec, e->d_wbgmax, mel, (size_t)cbt * 3000 * 16, s);
+    rc = run_program(e, e->whisper_b, nf);
+    if (rc) return fail(LTK_E_INVALID, std::string("whisper: ") + mt_graph_error(e->whisper_b));
+    e->whisper_b_nf = nf;
+    WhisperStatesN st;
+    for (int i = 0; i < 5; ++i) {
+        st.p[i] = mt_whisper_state(e->whisper_b, i, &cbt, &cb0);
+        st.cb0[i] = cb0; st.img_halfs[i] = (size_t)cbt * 1500 * 16;
+    }
+    WhisperChunkTab tab;
+    tab.n = nf; tab.total = 0;
+    for (int i = 0; i < nf; ++i) {
+        tab.r[i] = {(float*)reqs[i].d_out, i, reqs[i].batch, reqs[i].first_row, reqs[i].row_step, reqs[i].rows, tab.total};
+        tab.total += reqs[i].batch * reqs[i].rows * 5 * 48;
+    }
+    for (int i = nf; i < kWhisperBatchClips; ++i) tab.r[i] = {nullptr, 0, 0, 0, 0, 0, tab.total};
+    launch_whisper_chunks_batch(st, tab, 1500, s);
+    if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "whisper kernels failed to launch");
+    return LTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out,
                      void* stream) {
     if (!e || !pcm || !d_out || n_samples <= 0 || n_samples > 479000 || batch <= 0 || rows <= 0 || rows > 64)
         return fail(LTK_E_INVALID, "bad arguments");
     if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
     CHK(enter_device(e->device));
-    return infer_call(e, stream, [&]() -> int {
-        hipStream_t s = e->compute;
-        CHK(hipMemcpyAsync(e->d_wpcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
-        int cbt, cb0;
-        f16* mel = mt_latent_in(e->whisper, &cbt);
-        launch_whisper_logmel(e->d_wpcm, n_samples, e->d_wbasis, e->d_wlogspec, e->d_wgmax, mel, s);
-        int rc = run_program(e, e->whisper, 1);
-        if (rc) rc = fail(LTK_E_INVALID, std::string("whisper: ") + mt_graph_error(e->whisper));
-        if (!rc) {
-            WhisperStates st;
-            for (int i = 0; i < 5; ++i) { st.p[i] = mt_whisper_state(e->whisper, i, &cbt, &cb0); st.cb0[i] = cb0; }
-            launch_whisper_chunks(st, 1500, batch, first_row, row_step, rows, (float*)d_out, s);
-            if (hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, "whisper kernels failed to launch");
+    return infer_call(e, stream, [&]() -> int { return whisper_step_locked(e, pcm, n_samples, batch, first_row, row_step, rows, d_out); });
+}
+
+// N concurrent live steps in one call.  whisper_batch_plan cuts the call into runs of at most kWhisperBatchClips in request order; a
+// run of more than one uploads its clips into one device block, takes every clip's log-mel features with its own maximum word in one
+// launch pair, forwards them as the images of ONE run of the batched program (captured per clip count as every program, run_program)
+// and gathers every request's chunks from its own image in one launch.  A run of one request takes ltk_whisper_step's path.
+int ltk_whisper_step_batch(ltk_engine* e, const ltk_whisper_req* reqs, int nreq) {
+    if (!reqs || nreq <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::vector<WhisperRun> runs = whisper_batch_plan(nreq, kWhisperBatchClips);
+    for (int r = 0; r < nreq; ++r)          // every request before the first launch: a refused call has touched nothing
+        if (!reqs[r].pcm || !reqs[r].d_out || reqs[r].n_samples <= 0 || reqs[r].n_samples > 479000 || reqs[r].batch <= 0 || reqs[r].rows <= 0 ||
+            reqs[r].rows > 64)
+            return fail(LTK_E_INVALID, "bad request " + std::to_string(r) + " (0 < n_samples <= 479000, batch positive, 0 < rows <= 64)");
+    for (const WhisperRun& run : runs) {    // the work items of a run's one gather launch are counted in an int
+        long long items = 0;
+        for (int i = 0; i < run.count; ++i) {
+            items += (long long)reqs[run.first + i].batch * reqs[run.first + i].rows * 240;
+            if (items > 0x7fffffffll) return fail(LTK_E_INVALID, "bad request " + std::to_string(run.first + i) + " (batch too large)");
         }
-        return rc;
+    }
+    if (!e) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
+    if (nreq == 1)
+        return ltk_whisper_step(e, reqs[0].pcm, reqs[0].n_samples, reqs[0].batch, reqs[0].first_row, reqs[0].row_step, reqs[0].rows, reqs[0].d_out,
+                                nullptr);
+    CHK(enter_device(e->device));
+    return infer_call(e, nullptr, [&]() -> int {
+        for (const WhisperRun& run : runs) {
+            const ltk_whisper_req* q = reqs + run.first;
+            const int rc = run.batched ? whisper_batch_run_locked(e, q, run.count)
+                                       : whisper_step_locked(e, q->pcm, q->n_samples, q->batch, q->first_row, q->row_step, q->rows, q->d_out);
+            if (rc) return rc;
+        }
+        return LTK_OK;
     });
 }
 

@@ -46,6 +46,14 @@ int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* vae_sd, int n
 // Whisper encoder graph (one 30-s window per run): input log-mel tensor = mt_latent_in(), 5 hidden states
 int mt_build_whisper_graph(MtGraph* g, const ltk_named_tensor* encoder_sd, int n);
 f16* mt_whisper_state(MtGraph* g, int i, int* cbt, int* cb0);
+// Batched live steps (ltk_whisper_step_batch): the same op list over the packed weights of the loaded single-clip graph (MtGraph::share),
+// with activations of its own for `frames` clips (kWhisperBatchClips, nn_kernels.h); clip c = image c of every tensor.  0, or -4 when
+// the activations could not be allocated.
+int mt_build_whisper_batch_graph(MtGraph* g, const MtGraph* single, int frames);
+// How a call of nreq requests is cut (pure host): runs of at most `cap` in request order - every clip is the same 30-s window, so there
+// is nothing to group by; a run of one request takes the single-clip path (batched = false).
+struct WhisperRun { int first = 0, count = 0; bool batched = false; };
+std::vector<WhisperRun> whisper_batch_plan(int nreq, int cap);
 // HuBERT-large (hubert.hip): the packed weights live in ONE graph that is never run (mt_build_hubert_weights, from
 // HubertModel.state_dict() with the positional conv's weight norm already folded); a program for a clip of n_samples is built
 // over it and owns its activations only.  Input: the normalised fp32 waveform in mt_hubert_pcm_in(); output: last_hidden_state,

@@ -98,5 +98,19 @@ void launch_vae_latents(const f16* moments, int nfaces, const float* d_noise, fl
 void launch_whisper_logmel(const float* d_pcm, int n_samples, const float* d_basis, float* d_logspec, int* d_gmax, f16* y, hipStream_t s);
 struct WhisperStates { const f16* p[5]; int cb0[5]; };     // each state: CB16 [cbt >= 24][T][16], first block cb0 (buffers are 24 blocks wide)
 void launch_whisper_chunks(const WhisperStates& st, int T, int batch, int first_row, int row_step, int rows, float* out, hipStream_t s);
+// ... of up to kWhisperBatchClips clips in one launch each (ltk_whisper_step_batch): clip c = n_samples[c] samples at pcm_off[c] floats
+// of one device pcm block, its own row of logspec ([clips][80][3000]), its own maximum word gmax[c], its features in image c of y
+// (img_halfs apart).  A clip's arithmetic is whisper_logmel_kernel's: its features are the single step's, bit for bit.
+constexpr int kWhisperBatchClips = 16;
+struct WhisperClipTab { int n_samples[kWhisperBatchClips], pcm_off[kWhisperBatchClips], n_active[kWhisperBatchClips]; };
+void launch_whisper_logmel_batch(const float* d_pcm, WhisperClipTab tab, int clips, const float* d_basis, float* d_logspec, int* d_gmax,
+                                 f16* y, size_t img_halfs, hipStream_t s);
+// the chunk gathers of every request of a run in one launch: request q reads image `slot` of the five states (img_halfs[i] apart) and
+// writes fp32 [batch][rows*5][384] at its own `out`; item0 = its first work item (8 channels of one state of one row), rows clamped to
+// [0, T - 1] per request
+struct WhisperChunkReq { float* out; int slot, batch, first_row, row_step, rows, item0; };
+struct WhisperChunkTab { WhisperChunkReq r[kWhisperBatchClips]; int n, total; };
+struct WhisperStatesN { const f16* p[5]; int cb0[5]; size_t img_halfs[5]; };
+void launch_whisper_chunks_batch(const WhisperStatesN& st, const WhisperChunkTab& tab, int T, hipStream_t s);
 
 }  // namespace ltk

@@ -1339,6 +1339,98 @@ void launch_whisper_logmel(const float* d_pcm, int n_samples, const float* d_bas
     hipLaunchKernelGGL(whisper_logmel_finish_kernel, dim3((5 * kWFrames * 2 + 255) / 256), dim3(256), 0, s, d_logspec, n_active, d_gmax, y);
 }
 
+// The same front end for the clips of one batched run: blockIdx.y = the clip, whose samples, logspec row and maximum word are its own
+// (the clamp max(x, clip_max - 8) never sees another clip's maximum).  fp64 DFT and summation order as above, statement for statement:
+// a clip's features equal whisper_logmel_kernel's bit for bit.
+__global__ __launch_bounds__(256) void whisper_logmel_batch_kernel(const float* __restrict__ pcm_all, const WhisperClipTab tab,
+                                                                    const float* __restrict__ basis, float* __restrict__ logspec_all,
+                                                                    int* __restrict__ gmax_all) {
+    __shared__ double frame[kWNfft];
+    __shared__ double tw_c[kWNfft];
+    __shared__ double tw_s[kWNfft];
+    __shared__ double power[kWBins + 7];
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x;
+    const int clip = blockIdx.y;
+    if (t >= tab.n_active[clip]) return;                     // the grid is as wide as the run's longest clip (whole block: no barrier is skipped)
+    const float* __restrict__ pcm = pcm_all + tab.pcm_off[clip];
+    const int n_samples = tab.n_samples[clip];
+    float* __restrict__ logspec = logspec_all + (size_t)clip * kWMels * kWFrames;
+    for (int n = tid; n < kWNfft; n += 256) {
+        int i = t * kWHop - kWNfft / 2 + n;
+        if (i < 0) i = -i;
+        const double x = (i < n_samples) ? (double)pcm[i] : 0.0;
+        double sn, cs;
+        sincospi(2.0 * (double)n / (double)kWNfft, &sn, &cs);
+        frame[n] = x * (0.5 - 0.5 * cs);
+        tw_c[n] = cs;
+        tw_s[n] = sn;
+    }
+    __syncthreads();
+    if (tid < kWBins) {
+        double re = 0.0, im = 0.0;
+        int idx = 0;
+        for (int n = 0; n < kWNfft; ++n) {
+            const double v = frame[n];
+            re += v * tw_c[idx];
+            im -= v * tw_s[idx];
+            idx += tid;
+            if (idx >= kWNfft) idx -= kWNfft;
+        }
+        power[tid] = re * re + im * im;
+    }
+    __syncthreads();
+    if (tid < kWMels) {
+        double acc = 0.0;
+        for (int k = 0; k < kWBins; ++k) acc += (double)basis[tid * kWBins + k] * power[k];
+        const float v = (float)log10(fmax(acc, 1e-10));
+        logspec[(size_t)tid * kWFrames + t] = v;
+        atomicMax(gmax_all + clip, __float_as_int(v + 16.0f));
+    }
+}
+
+__global__ __launch_bounds__(256) void whisper_logmel_finish_batch_kernel(const float* __restrict__ logspec_all, const WhisperClipTab tab,
+                                                                           const int* __restrict__ gmax_all, f16* __restrict__ y_all,
+                                                                           size_t img_halfs) {
+    const int i = blockIdx.x * 256 + threadIdx.x;      // (cb, frame, half)
+    if (i >= 5 * kWFrames * 2) return;
+    const int clip = blockIdx.y;
+    const int n_active = tab.n_active[clip];
+    const float* __restrict__ logspec = logspec_all + (size_t)clip * kWMels * kWFrames;
+    f16* __restrict__ y = y_all + (size_t)clip * img_halfs;
+    const int half = i & 1, t = (i >> 1) % kWFrames, cb = (i >> 1) / kWFrames;
+    const float gmax = fmaxf(__int_as_float(gmax_all[clip]) - 16.0f, -10.0f);
+    f16x8 o;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int m = cb * 16 + half * 8 + c;
+        float v = (t < n_active) ? logspec[(size_t)m * kWFrames + t] : -10.0f;
+        v = fmaxf(v, gmax - 8.0f);
+        o[c] = (f16)((v + 4.0f) / 4.0f);
+    }
+    *reinterpret_cast<f16x8*>(y + ((size_t)cb * kWFrames + t) * 16 + half * 8) = o;
+}
+
+void launch_whisper_logmel_batch(const float* d_pcm, WhisperClipTab tab, int clips, const float* d_basis, float* d_logspec, int* d_gmax,
+                                 f16* y, size_t img_halfs, hipStream_t s) {
+    int widest = 0;
+    for (int c = 0; c < kWhisperBatchClips; ++c) {
+        int n_active = 0;
+        if (c < clips) {
+            n_active = (tab.n_samples[c] + kWNfft / 2 + kWHop - 1) / kWHop + 1;
+            if (n_active > kWFrames) n_active = kWFrames;
+        } else {
+            tab.n_samples[c] = 0; tab.pcm_off[c] = 0;
+        }
+        tab.n_active[c] = n_active;
+        if (n_active > widest) widest = n_active;
+    }
+    (void)hipMemsetAsync(d_gmax, 0, (size_t)kWhisperBatchClips * sizeof(int), s);
+    hipLaunchKernelGGL(whisper_logmel_batch_kernel, dim3(widest, clips), dim3(256), 0, s, d_pcm, tab, d_basis, d_logspec, d_gmax);
+    hipLaunchKernelGGL(whisper_logmel_finish_batch_kernel, dim3((5 * kWFrames * 2 + 255) / 256, clips), dim3(256), 0, s, d_logspec, tab, d_gmax,
+                       y, img_halfs);
+}
+
 // avatars/audio_features/whisper.py:35-56 + base_asr.py:91-133: frame i takes encoder rows
 // [first_row + i*row_step, +rows) (clamped), each row = the 5 hidden states -> out fp32 [batch][rows*5][384]
 __global__ __launch_bounds__(256) void whisper_chunks_kernel(const WhisperStates st, int T, int batch, int first_row, int row_step,
@@ -1358,6 +1450,29 @@ __global__ __launch_bounds__(256) void whisper_chunks_kernel(const WhisperStates
 void launch_whisper_chunks(const WhisperStates& st, int T, int batch, int first_row, int row_step, int rows, float* out, hipStream_t s) {
     const int total = batch * rows * 5 * 48;
     hipLaunchKernelGGL(whisper_chunks_kernel, dim3((total + 255) / 256), dim3(256), 0, s, st, T, batch, first_row, row_step, rows, out);
+}
+
+// ... of every request of a batched run: an item finds its request by its first item in the table, then gathers as above from image
+// `slot` of the states into that request's own output
+__global__ __launch_bounds__(256) void whisper_chunks_batch_kernel(const WhisperStatesN st, const WhisperChunkTab tab, int T) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= tab.total) return;
+    int q = 0;
+    while (q + 1 < tab.n && i >= tab.r[q + 1].item0) ++q;
+    const WhisperChunkReq rq = tab.r[q];
+    const int j = i - rq.item0;                             // (frame, row, state, c8) of this request
+    const int c8 = j % 48, s5 = (j / 48) % 5, r = (j / 240) % rq.rows, f = j / (240 * rq.rows);
+    int row = rq.first_row + f * rq.row_step + r;
+    row = min(max(row, 0), T - 1);
+    const f16* src = st.p[s5] + (size_t)rq.slot * st.img_halfs[s5];
+    const f16x8 v = *reinterpret_cast<const f16x8*>(src + ((size_t)(st.cb0[s5] + (c8 >> 1)) * T + row) * 16 + (c8 & 1) * 8);
+    float* o = rq.out + (((size_t)f * rq.rows + r) * 5 + s5) * 384 + c8 * 8;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = (float)v[c];
+}
+
+void launch_whisper_chunks_batch(const WhisperStatesN& st, const WhisperChunkTab& tab, int T, hipStream_t s) {
+    hipLaunchKernelGGL(whisper_chunks_batch_kernel, dim3((tab.total + 255) / 256), dim3(256), 0, s, st, tab, T);
 }
 
 // =============================================================================================== VAE encode bridges

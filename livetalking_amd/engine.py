@@ -15,7 +15,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import HubertReq, LtkError, MtReq, NamedTensor, UlMergeReport, UlReq, W2lReq  # noqa: F401
+from ._lib import HubertReq, LtkError, MtReq, NamedTensor, UlMergeReport, UlReq, W2lReq, WhisperReq  # noqa: F401
 
 
 def _as_f32(a) -> np.ndarray:
@@ -566,6 +566,43 @@ class Engine:
         out = np.empty(shape, dtype=np.float32)
         _lib.check(self._lib.ltk_whisper_debug_get(self._h, name.encode(), out.ctypes.data, out.size))
         return out
+
+    def whisper_step_batch(self, reqs: Sequence[tuple]):
+        """The live steps of several MuseTalk sessions in one call: reqs = [(pcm, batch, first_row, row_step, rows, d_out_ptr)].  Up to
+        16 clips share one run of the batched encoder program (ltk_whisper_step_batch); one request is whisper_step."""
+        arr = (WhisperReq * len(reqs))()
+        keep = []                                      # the pcm arrays stay alive across the call
+        for i, (pcm, batch, first_row, row_step, rows, d_out_ptr) in enumerate(reqs):
+            pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
+            keep.append(pcm)
+            arr[i].pcm, arr[i].n_samples = pcm.ctypes.data, pcm.shape[0]
+            arr[i].batch, arr[i].first_row, arr[i].row_step, arr[i].rows = int(batch), int(first_row), int(row_step), int(rows)
+            arr[i].d_out = d_out_ptr
+        _lib.check(self._lib.ltk_whisper_step_batch(self._h, arr, len(reqs)))
+        del keep
+
+    def whisper_batch_info(self) -> dict:
+        """capacity: clips per batched run; built: 1 once the batched program exists (the first batched run builds it);
+        activation_bytes: its activations at full capacity (0 until built)."""
+        cap, built, act = C.c_int(), C.c_int(), C.c_size_t()
+        _lib.check(self._lib.ltk_whisper_batch_info(self._h, C.byref(cap), C.byref(built), C.byref(act)))
+        return {"capacity": cap.value, "built": built.value, "activation_bytes": int(act.value)}
+
+    def whisper_debug_get_clip(self, name: str, clip: int, shape) -> np.ndarray:
+        """A named tensor (the names whisper_debug_get takes) of clip `clip` of the batched run that ran last."""
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.ltk_whisper_debug_get_clip(self._h, name.encode(), int(clip), out.ctypes.data, out.size))
+        return out
+
+    def whisper_batch_plan(self, nreq: int):
+        """How whisper_step_batch cuts a call of nreq requests (host only): [(batched, [requests in slot order])] in execution order."""
+        n = max(int(nreq), 1)
+        run_of, slot_of, batched, n_runs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)(), C.c_int()
+        _lib.check(self._lib.ltk_debug_whisper_batch_plan(int(nreq), run_of, slot_of, batched, C.byref(n_runs)))
+        runs = [(bool(batched[i]), []) for i in range(n_runs.value)]
+        for r in sorted(range(int(nreq)), key=lambda r: (run_of[r], slot_of[r])):
+            runs[run_of[r]][1].append(r)
+        return runs
 
     # ------------------------------------------------------------------ hubert audio features (Ultralight)
     @staticmethod

@@ -25,7 +25,10 @@ tensor.  One scheduler per (engine, kind); kinds: "wav2lip" -> Engine.wav2lip_in
 "hubert" -> Engine.hubert_step_batch (the live HuBERT steps of concurrent Ultralight sessions: a request is
 (pcm, batch, first_row, row_step, rows, out_ptr), its size unit one clip, at most HUBERT_BATCH_CLIPS per engine call; it enters
 through `submit`), "ultralight" -> Engine.ultralight_infer_merged (the U-Net passes of concurrent Ultralight sessions as one launch
-sequence per pass of the engine's merge plan; at most Engine.ul_max_frames frames per call, so that a call is one pass).
+sequence per pass of the engine's merge plan; at most Engine.ul_max_frames frames per call, so that a call is one pass),
+"whisper" -> Engine.whisper_step_batch (the live Whisper steps of concurrent MuseTalk sessions: a request is
+(pcm, batch, first_row, row_step, rows, out_ptr), its size unit one clip, at most WHISPER_BATCH_CLIPS per engine call, so that a call is
+one run of the batched encoder program; it enters through `submit`).
 """
 from __future__ import annotations
 
@@ -38,8 +41,9 @@ import time
 # kind -> the engine method that takes a list of requests; resolved on first use (an engine need not have the methods of the kinds
 # it never serves)
 _ENGINE_CALL = {"wav2lip": "wav2lip_infer", "musetalk": "musetalk_infer", "hubert": "hubert_step_batch",
-                "ultralight": "ultralight_infer_merged"}
+                "ultralight": "ultralight_infer_merged", "whisper": "whisper_step_batch"}
 HUBERT_BATCH_CLIPS = 16          # csrc/musetalk.h kHubertBatchClips: clips per batched program run
+WHISPER_BATCH_CLIPS = 16         # csrc/nn_kernels.h kWhisperBatchClips: clips per run of the batched Whisper program
 
 
 class _Req:
@@ -100,6 +104,8 @@ class BatchingScheduler:
             return self._max_frames
         if self.kind == "hubert":
             return HUBERT_BATCH_CLIPS
+        if self.kind == "whisper":
+            return WHISPER_BATCH_CLIPS
         if self.kind == "ultralight":
             lim = getattr(self.engine, "ul_max_frames", 0)
             return int(lim) if lim else 1 << 30
@@ -113,7 +119,7 @@ class BatchingScheduler:
 
     def submit(self, args, units):
         """The generic entry: `args` is one request as the kind's engine method takes it, `units` its size in the kind's unit (frames;
-        clips for "hubert").  Same rules and return as infer()."""
+        clips for "hubert" and "whisper").  Same rules and return as infer()."""
         batch = int(units)
         with self._cv:
             # A lone session (nothing in flight, nothing queued, no window to hold, no multi-request batch lately): the call goes straight
