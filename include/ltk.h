@@ -397,6 +397,56 @@ int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq);
 int ltk_vae_encoder_load(ltk_engine* e, const ltk_named_tensor* vae_sd, int n, int max_faces);
 int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, const float* noise, float* latents_out);
 
+/* =========================== fp16 headroom watch: the first calls on a real checkpoint =========================== */
+
+/* The conv epilogues clamp to +-65504 (+-448 on the e4m3 tensors of the fp8 path) and nothing reports it: a checkpoint whose
+ * activations reach the limit renders wrong frames silently.  A watch is armed for the next `calls` inference calls of ONE program and
+ * disarms itself after them.  A watched call issues exactly the compute launches it would issue unwatched - same routes, tiles,
+ * split-K factors, fused head, fused inverted residuals - launch by launch instead of from a captured graph (the graph cache is neither
+ * read nor written, no knob changes, no graph is dropped), with one scan launch behind every op whose output is in memory, on that
+ * op's stream: its frames and features are byte-identical to the unwatched call's.  One engine call counts as one call, whatever its
+ * nreq; arming and counting happen under the engine's enqueue lock.  Unarmed, no call launches anything it did not launch before.
+ * Reference: the reference runs these networks in fp32 on the CPU and under fp16 autocast on CUDA (avatars/wav2lip_avatar.py:51-70,
+ * avatars/musetalk_avatar.py:57-66, avatars/ultralight_avatar.py:63-81); it has no such check.
+ *
+ * Programs and their op listings (the report's index): LTK_HEALTH_WAV2LIP the layers of ltk_wav2lip_layer_name (type 0);
+ * LTK_HEALTH_MUSETALK ltk_musetalk_op_name (U-Net + VAE decoder); LTK_HEALTH_WHISPER the Whisper encoder's ops (types as
+ * ltk_musetalk_op_name; the 16-clip program of ltk_whisper_step_batch counts into the same table); LTK_HEALTH_HUBERT
+ * ltk_hubert_op_name (every clip length's program and the batched programs count into one table); LTK_HEALTH_ULTRALIGHT one
+ * avatar's ltk_ultralight_op_name as knob UL_FUSE_IR stands when the report is read.
+ * What a watch does not see (observed = 0, counters zero): an output that never reaches memory on the route the call took - the
+ * 32-channel map inside the fused Wav2Lip head (output_block.0), the hidden tensors of a fused Ultralight inverted residual (the block
+ * is listed once, with its project conv's output), the byte-writing heads; an op the call did not run (the face encoder under knob
+ * FACE_CACHE); Ultralight passes on the grouped path.  Float32 outputs (features, sigmoid hooks) are not scanned.
+ * A watched ltk_wav2lip_infer call takes the whole-pass route (the prefetched encoder's frames are byte-identical), is not deferred -
+ * its counters are complete when it returns - and leaves the prefetch slots and session records alone: the calls behind the window
+ * find prefetching as the first calls of a session do. */
+enum { LTK_HEALTH_WAV2LIP = 0, LTK_HEALTH_MUSETALK = 1, LTK_HEALTH_ULTRALIGHT = 2, LTK_HEALTH_WHISPER = 3, LTK_HEALTH_HUBERT = 4 };
+
+typedef struct ltk_health_op {
+    char name[64];
+    int type;                      /* the listing's op type */
+    int observed;                  /* 0: output never in memory on this route */
+    int q8;                        /* 0: fp16, 1: e4m3 */
+    unsigned long long elements, at_limit, near_limit, nonfinite;
+    float max_abs, limit;          /* limit: 65504 or 448 */
+} ltk_health_op;
+
+/* elements: values scanned; at_limit: |v| exactly at the type's limit (what a clamp leaves behind); near_limit: finite values in the
+ * top binade (fp16 |v| >= 32768, e4m3 |v| >= 256), the at_limit ones included; nonfinite: inf / NaN; max_abs: the largest finite |v|.
+ *
+ * ltk_health_watch: arms the next `calls` calls of `program` and zeroes its counters; calls = 0 disarms (what was counted stays
+ * readable).  avatar_id is read for LTK_HEALTH_ULTRALIGHT only.  LTK_E_STATE when the program is not loaded (the avatar unknown),
+ * LTK_E_INVALID for an unknown program or negative calls.
+ * ltk_health_report: waits for the device, then the listing with the counters accumulated over the watched calls since the watch was
+ * armed; *n_ops = ops in the listing (also set when cap is too small: LTK_E_INVALID), calls_seen / calls_left (may be NULL) = watched
+ * calls so far / still to come.
+ * ltk_health_scan: the scan kernel on its own (unit tests): one tensor view, d_x device fp16 [N][cbt][P][16] (q8 = 0) or e4m3
+ * [N][cbt][P][32] (q8 = 1), channel blocks [cb0, cb0 + CB); *rec = its record (name empty).  Returns when it is complete. */
+int ltk_health_watch(ltk_engine* e, int program, int avatar_id, int calls);
+int ltk_health_report(ltk_engine* e, int program, int avatar_id, ltk_health_op* ops, int cap, int* n_ops, int* calls_seen, int* calls_left);
+int ltk_health_scan(ltk_engine* e, const void* d_x, int N, int cbt, int cb0, int CB, long long P, int q8, ltk_health_op* rec);
+
 /* ---- test / measurement hooks (not on the production call path) ---- */
 
 /* named tensor of the last Whisper step as [C][T] float32: "input_features", "hidden_states.0".."hidden_states.4",
@@ -448,6 +498,11 @@ int ltk_hubert_chunks_host(ltk_engine* e, const float* feat, int T, int batch, i
  * (AutoencoderKL.decode sample, RGB), frames uint8 [B][256][256][3] BGR. */
 int ltk_musetalk_forward_host(ltk_engine* e, const float* latents, const float* feat, int B, float* unet_out, float* image,
                               uint8_t* frames);
+/* fp8 conv path: the e4m3 output tensor of op `op` (ltk_musetalk_op_name; the GroupNorm + SiLU ops in front of the ResnetBlock2D convs)
+ * as the last pass left it, raw codes, uint8 [frames][C][H * W]; n_bytes must be exactly that.  Such tensors share buffers: an op's
+ * codes are intact only until a later op writes the same buffer (the last e4m3 op of the program always is).  LTK_E_INVALID when the op
+ * does not exist or writes fp16. */
+int ltk_musetalk_debug_get_q8(ltk_engine* e, const char* op, int frames, uint8_t* out, size_t n_bytes);
 /* copy a named intermediate of the last MuseTalk forward as NCHW float32 (first `frames` frames) */
 int ltk_musetalk_debug_get(ltk_engine* e, const char* name, int frames, float* out, size_t n_floats);
 /* average milliseconds of one U-Net + VAE pass over `frames` frames, and its conv/linear MACs */

@@ -90,6 +90,17 @@ class NormReport(C.Structure):
     _fields_ = [("kernel", C.c_char * 64)] + [(n, C.c_int) for n in ("impl", "segs", "members", "grid")]
 
 
+class HealthOp(C.Structure):
+    _fields_ = [("name", C.c_char * 64), ("type", C.c_int), ("observed", C.c_int), ("q8", C.c_int), ("elements", C.c_ulonglong),
+                ("at_limit", C.c_ulonglong), ("near_limit", C.c_ulonglong), ("nonfinite", C.c_ulonglong), ("max_abs", C.c_float),
+                ("limit", C.c_float)]
+
+
+# include/ltk.h LTK_HEALTH_*: the programs a headroom watch can be armed for
+HEALTH_WAV2LIP, HEALTH_MUSETALK, HEALTH_ULTRALIGHT, HEALTH_WHISPER, HEALTH_HUBERT = range(5)
+HEALTH_PROGRAMS = {"wav2lip": HEALTH_WAV2LIP, "musetalk": HEALTH_MUSETALK, "ultralight": HEALTH_ULTRALIGHT, "whisper": HEALTH_WHISPER,
+                   "hubert": HEALTH_HUBERT}
+
 DEFER_SYNC = 2      # flag of ltk_wav2lip_infer_deferred
 
 # every symbol include/ltk.h declares: (restype, argtypes)
@@ -148,7 +159,12 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p]),
     "ltk_musetalk_forward_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ltk_musetalk_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ltk_musetalk_debug_get_q8": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
     "ltk_musetalk_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    "ltk_health_watch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "ltk_health_report": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(HealthOp), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int)]),
+    "ltk_health_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(HealthOp)]),
     "ltk_whisper_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int]),
     "ltk_whisper_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ltk_whisper_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),

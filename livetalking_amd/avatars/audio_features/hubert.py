@@ -72,17 +72,30 @@ class EngineAudio2Feature:
     the Wav2Vec2Processor's one job - zero mean, unit variance over the utterance - is part of the device program) or a
     HubertModel state dict."""
 
-    def __init__(self, engine, source=HUBERT_DIR):
+    def __init__(self, engine, source=HUBERT_DIR, opt=None):
         if isinstance(source, (str, os.PathLike)):
             from transformers import HubertModel
             source = HubertModel.from_pretrained(source).state_dict()
         self.engine = engine
         engine.load_hubert(source)
+        from ...health import monitor_for
+        self.health_monitor = monitor_for(engine, "hubert", opt)  # LTK_HEALTH_WATCH=N / opt.health_watch: the model's first N calls are watched
+
+    def health(self):
+        """(ops, calls_seen, calls_left) of the headroom watch over the model's first calls; None when no watch was armed."""
+        h = getattr(self, "health_monitor", None)
+        return h.report() if h is not None else None
+
+    def _health_tick(self):
+        h = getattr(self, "health_monitor", None)
+        if h is not None and h.pending:             # the first call behind the watched window logs its line
+            h.tick()
 
     def get_hubert_from_16k_speech(self, speech):
         speech = np.asarray(speech)
         if speech.ndim == 2:
             speech = speech[:, 0]
+        self._health_tick()
         return self.engine.hubert_features(speech)
 
     def step(self, pcm, batch, first_row, row_step=2, rows=16):
@@ -91,6 +104,7 @@ class EngineAudio2Feature:
         call goes straight down in its own thread."""
         import torch
         out = torch.empty((batch, rows, 1024), dtype=torch.float32, device=self.engine.torch_device)
+        self._health_tick()
         if _HUBERT_BATCH:
             from ...scheduler import get_scheduler
             get_scheduler(self.engine, "hubert").submit((pcm, batch, first_row, row_step, rows, out.data_ptr()), 1)
@@ -137,6 +151,10 @@ class HubertASR(BaseASR):
         if not hasattr(audio_processor, "get_hubert_from_16k_speech"):
             raise TypeError("audio_processor must provide get_hubert_from_16k_speech(pcm)")
         self.audio_processor = audio_processor
+        if getattr(audio_processor, "health_monitor", True) is None and hasattr(audio_processor, "engine"):
+            # an engine-side processor loaded without the knob: opt.health_watch of the first session that brings it arms the watch
+            from ...health import monitor_for
+            audio_processor.health_monitor = monitor_for(audio_processor.engine, "hubert", opt)
         self.audio_feat_length = audio_feat_length
         self.last_is_silence = True
 

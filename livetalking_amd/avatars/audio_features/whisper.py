@@ -13,6 +13,7 @@ import os
 
 import numpy as np
 
+from ...health import monitor_for
 from ...hostshim import BaseASR
 
 # 1: the live steps of concurrent sessions go through the engine's "whisper" scheduler and share one encoder run per tick
@@ -57,13 +58,24 @@ class Audio2Feature:
             check_whisper_dir(model_path)
             encoder_state_dict = WhisperModel.from_pretrained(model_path).encoder.state_dict()
         engine.load_whisper(encoder_state_dict)
+        self.health_monitor = monitor_for(engine, "whisper")      # LTK_HEALTH_WATCH=N: the encoder's first N steps are watched
+
+    def health(self):
+        """(ops, calls_seen, calls_left) of the headroom watch over the encoder's first steps; None when no watch was armed."""
+        h = getattr(self, "health_monitor", None)
+        return h.report() if h is not None else None
 
 
 class WhisperASR(BaseASR):
+    _health = None                    # the encoder's headroom monitor while LTK_HEALTH_WATCH asks for one (health.py)
+
     def __init__(self, opt, parent, audio_processor: Audio2Feature):
         super().__init__(opt, parent)
         self.audio_processor = audio_processor
         self.engine = audio_processor.engine
+        self._health = getattr(audio_processor, "health_monitor", None)
+        if self._health is None and hasattr(self.engine, "health_watch"):          # opt.health_watch of the first session that brings it
+            self._health = audio_processor.health_monitor = monitor_for(self.engine, "whisper", opt)
         import torch  # device buffers only
         self._torch = torch
 
@@ -79,6 +91,9 @@ class WhisperASR(BaseASR):
         feat = torch.empty((self.batch_size, 50, 384), dtype=torch.float32, device=self.engine.torch_device)
         # whisper.py:71-73: audio_feat_win [0,5], start l/2, multiplier 2 -> rows [2*(i + l/2), +10)
         first_row = int((self.stride_left_size / 2) * 2)
+        h = self._health
+        if h is not None and h.pending:             # the first step behind the watched window logs its line
+            h.tick()
         if _WHISPER_BATCH:
             from ...scheduler import get_scheduler
             get_scheduler(self.engine, "whisper").submit((inputs, self.batch_size, first_row, 2, 10, feat.data_ptr()), 1)

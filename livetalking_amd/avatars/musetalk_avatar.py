@@ -28,6 +28,7 @@ from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror
 from ..scheduler import get_scheduler
 from ..sharding import EnginePool, visible_devices
 from .audio_features.whisper import Audio2Feature, WhisperASR
+from ..health import lookup as health_lookup, monitor_for
 
 
 _PASTE_BATCH = os.environ.get("LTK_PASTE_BATCH", "1") != "0"     # 0: one composite + one pageable copy per paste_back_frame call
@@ -69,6 +70,12 @@ class MuseTalkModel:
                 aid = self.engines[slot].register_musetalk_avatar(latent_list, frame_list, coord_list, mask_list, mask_coords_list)
                 self._avatars[key] = aid
             return aid
+
+    def health(self):
+        """Per engine: (ops, calls_seen, calls_left) of the headroom watch over the U-Net + VAE decoder's first calls
+        (LTK_HEALTH_WATCH=N / opt.health_watch; livetalking_amd/health.py), None where no watch was armed."""
+        mons = [health_lookup(eng, "musetalk") for eng in self.engines]
+        return [m.report() if m is not None else None for m in mons]
 
 
 # AutoencoderKL checkpoints published before diffusers 0.13 (sd-vae-ft-mse among them) store the mid-block attention under
@@ -176,6 +183,7 @@ def load_model(unet_state_dict=None, vae_state_dict=None, whisper_encoder_state_
         eng = Engine(dev)
         eng.load_musetalk(unet_state_dict, vae_state_dict, max_frames=max_frames, fp8=fp8,
                           fp8_act_scale=float(os.environ.get("LTK_MT_FP8_ASCALE", "0")))
+        monitor_for(eng, "musetalk")              # LTK_HEALTH_WATCH=N: the first N calls on this checkpoint are watched
         return eng
 
     devices = visible_devices() if device is None else [int(device)]
@@ -223,6 +231,7 @@ def warm_up(batch_size, model):
 @register("avatar", "musetalk")
 class MuseReal(DeviceEgressMixin, BaseAvatar):
     _egress_source = SRC_MUSETALK     # opt.egress = "bgr24" | "i420": device-side process_frames (egress.py)
+    _health = None                    # the engine's headroom monitor while LTK_HEALTH_WATCH / opt.health_watch asks for one (health.py)
 
     def __init__(self, opt, model, avatar):
         super().__init__(opt)
@@ -236,6 +245,7 @@ class MuseReal(DeviceEgressMixin, BaseAvatar):
         self._frame_hw = (int(h), int(w))
         self._sched = get_scheduler(self.engine, "musetalk")
         self._paste_eg = None           # lazily: the BGR24 egress session behind the batched paste_back_frame
+        self._health = monitor_for(self.engine, "musetalk", opt)
         self.asr = WhisperASR(opt, self, model.audio_processors[self._slot])
         self.asr.warm_up()
 
@@ -252,6 +262,8 @@ class MuseReal(DeviceEgressMixin, BaseAvatar):
         if feat.shape[0] != B:
             raise ValueError(f"expected {B} whisper chunks, got {feat.shape[0]}")
         pred = torch.empty((B, 256, 256, 3), dtype=torch.uint8, device=dev)
+        if self._health is not None and self._health.pending:      # the first call behind the watched window logs its line
+            self._health.tick()
         self._sched.infer(self._aid, int(index), B, feat.data_ptr(), pred.data_ptr())
         items = list(pred.unbind(0))
         if hasattr(self.engine, "egress_batch"):        # opt.egress sessions convert the batch's frames in one go (egress.py)

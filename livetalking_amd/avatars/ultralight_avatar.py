@@ -29,6 +29,7 @@ import numpy as np
 
 from ..egress import SRC_ULTRALIGHT, DeviceEgressMixin, FrameGroup
 from ..engine import Engine
+from ..health import monitor_for
 from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror_index: part of the reference module's namespace)
 from ..scheduler import get_scheduler
 from .audio_features.hubert import HubertASR
@@ -64,21 +65,33 @@ class UltralightNet:
         self.max_frames = int(max_frames or os.environ.get("LTK_UL_MAX_FRAMES", "32"))
         self._aid = None
         self._lock = threading.Lock()
+        self.health_monitor = None       # LTK_HEALTH_WATCH=N: the avatar's first N calls are watched from its registration on
 
-    def avatar_id(self) -> int:
+    def avatar_id(self, opt=None) -> int:
+        """Registers the avatar on first use.  `opt`: a session's options - opt.health_watch arms the avatar's watch when
+        LTK_HEALTH_WATCH did not at the registration."""
         with self._lock:
             if self._aid is None:
                 if self.engine is None:
                     self.engine = _engine(0)
                 faces, frames, coords = self._bank
                 self._aid = self.engine.register_ultralight_avatar(self.state_dict, faces, frames, coords, max_frames=self.max_frames)
+            if self.health_monitor is None:
+                self.health_monitor = monitor_for(self.engine, "ultralight", opt, self._aid)
             return self._aid
+
+    def health(self):
+        """(ops, calls_seen, calls_left) of the headroom watch over this avatar's first calls (livetalking_amd/health.py); None when
+        no watch was armed."""
+        h = getattr(self, "health_monitor", None)
+        return h.report() if h is not None else None
 
     def release(self):
         with self._lock:
             if self._aid is not None:
                 self.engine.release_avatar(self._aid)
                 self._aid = None
+                self.health_monitor = None          # the table went with the avatar
 
     def eval(self):
         return self
@@ -94,7 +107,7 @@ def load_model(opt):
             if audio_processor is None:
                 for dead in [e for e in _hubert_processors if e._h is None]:
                     del _hubert_processors[dead]
-                audio_processor = _hubert_processors[eng] = _hubert.EngineAudio2Feature(eng, _hubert.HUBERT_DIR)
+                audio_processor = _hubert_processors[eng] = _hubert.EngineAudio2Feature(eng, _hubert.HUBERT_DIR, opt=opt)
     else:
         audio_processor = _hubert.load_model()
     model = None
@@ -136,13 +149,15 @@ def warm_up(batch_size, avatar, modelres):
 @register("avatar", "ultralight")
 class LightReal(DeviceEgressMixin, BaseAvatar):
     _egress_source = SRC_ULTRALIGHT   # opt.egress = "bgr24" | "i420": device-side process_frames (egress.py)
+    _health = None                    # the avatar's headroom monitor while LTK_HEALTH_WATCH asks for one (health.py)
 
     def __init__(self, opt, model, avatar):
         super().__init__(opt)
         audio_processor, _ = model
         self.model, self.frame_list_cycle, self.face_list_cycle, self.coord_list_cycle = avatar
-        self._aid = self.model.avatar_id()
+        self._aid = self.model.avatar_id(opt)
         self.engine = self.model.engine
+        self._health = getattr(self.model, "health_monitor", None)
         h, w = self.frame_list_cycle[0].shape[:2]
         self._frame_hw = (int(h), int(w))
         self.asr = HubertASR(opt, self, audio_processor, audio_feat_length=[4, 4])
@@ -165,6 +180,9 @@ class LightReal(DeviceEgressMixin, BaseAvatar):
         if feat.shape[0] != B:
             raise ValueError(f"expected {B} feature chunks, got {feat.shape[0]}")
         pred = torch.empty((B, 160, 160, 3), dtype=torch.uint8, device=feat.device)
+        h = self._health
+        if h is not None and h.pending:             # the first call behind the watched window logs its line
+            h.tick()
         if _UL_SCHED and hasattr(self.engine, "ultralight_infer_merged"):
             # concurrent sessions' passes merge into one launch sequence (scheduler kind "ultralight"); a lone session takes the
             # scheduler's solo path: one request, the launches and bytes of the direct call

@@ -27,6 +27,7 @@ import numpy as np
 
 from ..egress import SRC_WAV2LIP, DeviceEgressMixin, FrameGroup
 from ..engine import Engine
+from ..health import lookup as health_lookup, monitor_for
 from ..hostshim import BaseAvatar, mirror_index, register  # noqa: F401  (mirror_index: part of the reference module's namespace)
 from ..scheduler import get_scheduler
 from ..sharding import EnginePool, visible_devices
@@ -71,6 +72,12 @@ class Wav2LipModel:
     def eval(self):
         return self
 
+    def health(self):
+        """Per engine: (ops, calls_seen, calls_left) of the headroom watch over the model's first calls (LTK_HEALTH_WATCH=N /
+        opt.health_watch; livetalking_amd/health.py), None where no watch was armed."""
+        mons = [health_lookup(eng, "wav2lip") for eng in self.engines]
+        return [m.report() if m is not None else None for m in mons]
+
 
 def _state_dict_from_checkpoint(path):
     import torch
@@ -91,6 +98,7 @@ def load_model(path, state_dict=None, max_frames=None, device=None):
     def factory(dev):
         eng = Engine(dev)
         eng.load_wav2lip(state_dict, max_frames=max_frames)
+        monitor_for(eng, "wav2lip")               # LTK_HEALTH_WATCH=N: the first N calls on this checkpoint are watched
         return eng
 
     devices = visible_devices() if device is None else [int(device)]
@@ -186,6 +194,7 @@ _FRAME_HANDLE = None
 @register("avatar", "wav2lip")
 class LipReal(DeviceEgressMixin, BaseAvatar):
     _egress_source = SRC_WAV2LIP      # opt.egress = "bgr24" | "i420": device-side process_frames (egress.py)
+    _health = None                    # the engine's headroom monitor while LTK_HEALTH_WATCH / opt.health_watch asks for one (health.py)
 
     def __init__(self, opt, model, avatar):
         super().__init__(opt)
@@ -202,6 +211,7 @@ class LipReal(DeviceEgressMixin, BaseAvatar):
         # (a fake engine of the tests has no such entry and stays as it is)
         if hasattr(self.engine, "order_frames"):
             self.engine.defer_handles = True
+        self._health = monitor_for(self.engine, "wav2lip", opt)
         self.asr = MelASR(opt, self, engine=self.engine)
         self.asr.warm_up()
 
@@ -221,6 +231,8 @@ class LipReal(DeviceEgressMixin, BaseAvatar):
         if mel.shape[0] != B:
             raise ValueError(f"expected {B} mel windows, got {mel.shape[0]}")
         pred = torch.empty((B, 256, 256, 3), dtype=torch.uint8, device=mel.device)
+        if self._health is not None and self._health.pending:      # the first call behind the watched window logs its line
+            self._health.tick()
         deferred = self._sched.infer(self._aid, int(index), B, mel.data_ptr(), pred.data_ptr())
         self._last_mel = mel            # keep inputs alive until the call returned (it has)
         # (everything from here to the next engine call is time the GPU idles when this is the only session: one unbind instead of

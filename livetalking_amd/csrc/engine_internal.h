@@ -135,8 +135,10 @@ struct MtAvatar {
 // the bank.  boxes = coords.pkl as (x1, y1, x2, y2).
 struct UlProgram;                                     // ultralight.hip: the avatar's operands, one record per op of the architecture
 struct UlGroupTab;                                    // ul_gconv.h
+struct HealthWatch;                                   // below
 struct UlAvatar {
     std::unique_ptr<UlProgram> prog;
+    std::unique_ptr<HealthWatch> health;  // the avatar's headroom watch, one record per op of the architecture table; under the engine's enqueue lock
     uint8_t* d_face = nullptr;       // [n][168][168][3]
     uint8_t* d_full = nullptr;       // [n][H][W][3]
     std::vector<int32_t> boxes;
@@ -149,6 +151,47 @@ struct UlAvatar {
     ~UlAvatar();                     // selects the device, frees the banks, then the program's operands
 };
 constexpr int kUlBufs = 12;           // activation buffers of the Ultralight program (ultralight.hip UlBuf)
+
+// ---------------------------------------------------------------- headroom watch (ltk_health_watch, include/ltk.h)
+// One table of op records (misc_kernels.h HealthRec) beside a launch program, indexed by the program's own op listing, owned by whoever
+// owns the program (the engine; an Ultralight avatar).  Armed for the next `left` engine calls of the program; a watched call runs its
+// usual launches eagerly with one launch_health_scan behind every op whose output is in memory.  Everything here is touched under the
+// engine's enqueue lock (ltk_engine::mu) only.
+struct HealthWatch {
+    HealthRec* d = nullptr;               // [n] records; the scan kernel is their only writer, arming zeroes them
+    int n = 0;
+    int left = 0, seen = 0;               // calls still to watch / watched since the watch was armed
+    std::vector<unsigned char> observed;  // [n] a scan was launched for the op since the watch was armed
+    HealthWatch() = default;
+    HealthWatch(const HealthWatch&) = delete;
+    HealthWatch& operator=(const HealthWatch&) = delete;
+    ~HealthWatch() { release(); }         // (the owner has selected the device)
+    int alloc(int n_ops) {
+        release();
+        if (n_ops <= 0) return 0;
+        if (hipMalloc((void**)&d, (size_t)n_ops * sizeof(HealthRec)) != hipSuccess) { d = nullptr; (void)hipGetLastError(); return -1; }
+        if (hipMemset(d, 0, (size_t)n_ops * sizeof(HealthRec)) != hipSuccess) { release(); return -1; }
+        n = n_ops;
+        observed.assign((size_t)n_ops, 0);
+        return 0;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        d = nullptr; n = 0; left = 0; seen = 0; observed.clear();
+    }
+    // the engine call being enqueued: is it watched?  Counts it.
+    bool begin() {
+        if (!d || left <= 0) return false;
+        --left; ++seen;
+        return true;
+    }
+    // op `i` of the watched call wrote the view: one scan launch behind it on its stream
+    void scan(int i, const void* x, int N, int cbt, int cb0, int CB, long long P, int q8, hipStream_t s) {
+        if (!d || i < 0 || i >= n) return;
+        launch_health_scan(x, N, cbt, cb0, CB, P, q8, d + i, s);
+        observed[(size_t)i] = 1;
+    }
+};
 
 // RAII HIP event: error returns between create and destroy do not leak it
 struct Ev {
@@ -211,6 +254,11 @@ struct ltk_engine {
     float* d_partial_pf = nullptr;        // ... of the prefetch stream (aux2, knob PREFETCH)
     unsigned long long* d_sat = nullptr;  // [2] saturation counters of knob SAT_CHECK (ltk_debug_saturation): halfs at the fp16 limit, non-finite halfs
     size_t partial_cap = 0, partial_aux_cap = 0, partial_pf_cap = 0;
+    // headroom watches (ltk_health_watch), allocated when their program is loaded: Wav2Lip by layer; the MuseTalk, Whisper and HuBERT
+    // programs by op (the batched Whisper program and every HuBERT program share their model's table).  w2l_scan: set while a watched
+    // Wav2Lip call is being enqueued, run_convs scans every layer it launches into it.
+    HealthWatch hw_w2l, hw_mt, hw_whisper, hw_hubert;
+    HealthWatch* w2l_scan = nullptr;
     // Lock rule.  `mu` owns the enqueue order on compute / aux / aux2 and everything a pass works with: the loaded programs (layers,
     // mt, whisper, vae_enc, their settings), the arena and pointer tables, the prefetch slots / solo_seq / pf_* counters, both graph
     // caches, capture / taps, and an Avatar's d_feat / feat_rec_bytes / feat_epoch; it may be held across HIP calls that wait.
@@ -625,10 +673,16 @@ struct UlPassArgs {
     // in the order that pass would (conv3's split-K factor follows a launch's frame count), so a frame's bytes do not depend on which
     // requests share its pass; nullptr or all == nf: the plain pass.
     const std::vector<int>* own = nullptr;
+    // a watched call's per-avatar pass (ltk_health_watch): eagerly, every op's output scanned into the record of its index in the
+    // architecture table; a grouped pass has no avatar and is never watched
+    HealthWatch* health = nullptr;
 };
 int ul_pass(ltk_engine* e, const UlAvatar& a, int nf, UlPassArgs args = UlPassArgs());
 double ul_macs_per_frame();
 void ul_drop_graphs(ltk_engine* e, int avatar_id);     // under e->mu: the captured passes of a released avatar
+// the listing as knob UL_FUSE_IR stands (ltk_ultralight_op_name) with, per entry, its index in the architecture table = its record in
+// an avatar's HealthWatch
+void ul_health_listing(std::vector<std::string>* names, std::vector<int>* types, std::vector<int>* arch_index);
 // ltk_ultralight_infer_merged's call plan (ultralight.hip ul_merge_plan; seen through ltk_debug_ul_merge_plan): which frames of which
 // request share a pass.  A span = frames [first, first + count) of request `req` at frames [at, at + count) of the pass.
 enum { UL_PATH_PER_AVATAR = 0, UL_PATH_GROUPED = 1 };

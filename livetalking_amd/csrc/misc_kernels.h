@@ -71,6 +71,18 @@ void launch_upload_tables(const FacePtrs* faces, const MelPtrs* mels, const OutP
 // (|v| == 448 / NaN).  One atomic per wave that found something.
 void launch_sat_scan(const f16* x, int N, int cbt, int cb0, int CB, long long P, int q8, unsigned long long* ctr, hipStream_t s);
 
+// Headroom scan (ltk_health_watch, ltk_health_scan): ONE op's record, accumulated over the same tensor view launch_sat_scan takes.
+// Magnitude codes (the value's bits with the sign dropped) order like the values, so the largest finite code is the largest |v|.
+//   fp16: at_limit code 0x7bff (65504), near_limit 0x7800 <= code < 0x7c00 (the top binade, 32768 ..), nonfinite code >= 0x7c00
+//   e4m3: at_limit code 0x7e (448),     near_limit 0x78 <= code < 0x7f (256 ..),                        nonfinite code 0x7f
+// elements counts every value of the view; max_code is the largest finite code.  The kernel is the record's only writer; the host
+// zeroes it when a watch is armed.
+struct HealthRec {
+    unsigned long long elements, at_limit, near_limit, nonfinite;
+    unsigned max_code, pad;
+};
+void launch_health_scan(const void* x, int N, int cbt, int cb0, int CB, long long P, int q8, HealthRec* rec, hipStream_t s);
+
 void launch_nhwc_to_nchw_f32(const f16* x, int N, int H, int W, int ld, int coff, int C, float* out, hipStream_t s);
 
 // audio.py:45-51 melspectrogram columns + mel.py:56-63 window gather.

@@ -221,6 +221,62 @@ void launch_sat_scan(const f16* x, int N, int cbt, int cb0, int CB, long long P,
     hipLaunchKernelGGL(sat_scan_kernel, dim3(grid), dim3(256), 0, s, x, cbt, cb0, CB, P, total, q8, ctr);
 }
 
+// One 16-byte load per item (two per 32-byte pixel row of a channel block, as sat_scan_kernel walks the view), grid-stride; counts and
+// the largest finite magnitude code reduced over the wave, then at most one atomic per wave and field (a clean tensor costs one
+// atomicMax per wave; `elements` is added once per launch).
+__global__ __launch_bounds__(256) void health_scan_kernel(const unsigned char* __restrict__ x, int cbt, int cb0, int CB, long long P, long long total,
+                                                           int q8, HealthRec* __restrict__ rec) {
+    unsigned hit = 0, near = 0, bad = 0, mx = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int half = (int)(i & 1);
+        const long long r = i >> 1;
+        const long long p = r % P;
+        const long long r2 = r / P;
+        const int cb = (int)(r2 % CB), n = (int)(r2 / CB);
+        const uint4 v = *reinterpret_cast<const uint4*>(x + (((size_t)n * cbt + cb0 + cb) * P + p) * 32 + half * 16);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (q8) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const unsigned m = (w[k] >> (8 * b)) & 0x7fu;
+                    const bool nf = m == 0x7fu;
+                    hit += m == 0x7eu; bad += nf; near += (m >= 0x78u) && !nf;
+                    mx = nf ? mx : max(mx, m);
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const unsigned m = (w[k] >> (16 * b)) & 0x7fffu;
+                    const bool nf = m >= 0x7c00u;
+                    hit += m == 0x7bffu; bad += nf; near += (m >= 0x7800u) && !nf;
+                    mx = nf ? mx : max(mx, m);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        hit += __shfl_xor(hit, m); near += __shfl_xor(near, m); bad += __shfl_xor(bad, m);
+        mx = max(mx, (unsigned)__shfl_xor(mx, m));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (hit) atomicAdd(&rec->at_limit, (unsigned long long)hit);
+        if (near) atomicAdd(&rec->near_limit, (unsigned long long)near);
+        if (bad) atomicAdd(&rec->nonfinite, (unsigned long long)bad);
+        if (mx) atomicMax(&rec->max_code, mx);
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&rec->elements, (unsigned long long)total * (q8 ? 16u : 8u));
+    }
+}
+
+void launch_health_scan(const void* x, int N, int cbt, int cb0, int CB, long long P, int q8, HealthRec* rec, hipStream_t s) {
+    const long long total = (long long)N * CB * P * 2;
+    if (total <= 0 || !rec) return;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(health_scan_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const unsigned char*>(x), cbt, cb0, CB, P, total, q8, rec);
+}
+
 void launch_nhwc_to_nchw_f32(const f16* x, int N, int H, int W, int ld, int coff, int C, float* out, hipStream_t s) {
     const size_t total = (size_t)N * C * H * W;
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, N, H * W, ld, coff, C, out);

@@ -59,6 +59,12 @@ int ltk_musetalk_load(ltk_engine* e, const ltk_named_tensor* unet_sd, int n_unet
         mt_graph_delete(mg);
         return arc;
     }
+    if (e->hw_mt.alloc(mt_op_count(mg))) {
+        (void)hipFree(e->d_pe); (void)hipFree(e->d_mt_feat); (void)hipFree(e->d_mt_lat);
+        e->d_pe = nullptr; e->d_mt_feat = nullptr; e->d_mt_lat = nullptr;
+        mt_graph_delete(mg);
+        return fail(LTK_E_NOMEM, "health table allocation failed");
+    }
     e->mt = mg;
     e->mt_max_frames = max_frames;
     return LTK_OK;
@@ -103,6 +109,20 @@ int ltk_musetalk_avatar_register(ltk_engine* e, const float* latents, const uint
 
 }  // extern "C"
 
+// under e->mu: while the guard lives, the runs of `g` are a watched call's (ltk_health_watch): scanned into `w`'s records, which the
+// program indexes by its op list (a program with another op count than the table is left alone)
+namespace {
+struct MtWatched {
+    MtGraph* g = nullptr;
+    MtWatched(MtGraph* g_, HealthWatch& w, bool on) {
+        if (on && g_ && w.d && mt_op_count(g_) == w.n) { g = g_; mt_set_health(g, w.d, w.observed.data()); }
+    }
+    MtWatched(const MtWatched&) = delete;
+    MtWatched& operator=(const MtWatched&) = delete;
+    ~MtWatched() { if (g) mt_set_health(g, nullptr, nullptr); }
+};
+}  // namespace
+
 // One run of a device program (the U-Net + VAE decoder pass, the Whisper encoder) on the compute stream, under e->mu.  Every op
 // of a program reads and writes the program's own persistent buffers with launch arguments that depend on the frame count only,
 // so the whole launch list (436 launches for a MuseTalk pass, ~60 for a Whisper step) is captured as ONE hipGraph the second time a
@@ -113,6 +133,7 @@ int ltk_musetalk_avatar_register(ltk_engine* e, const float* latents, const uint
 int ltk::run_program(ltk_engine* e, MtGraph* prog, int nf) {
     hipStream_t s = e->compute;
     auto enq = [&]() -> int { return mt_run(prog, nf, e->d_partial, e->partial_cap, s); };
+    if (mt_health_on(prog)) return enq();       // a watched call (ltk_health_watch): eagerly, scans between the ops, the graph cache untouched
     return knob(K_GRAPH) ? e->prog_graphs.run(e, {(const void*)prog, nf}, s, "program", nf, enq) : enq();
 }
 
@@ -159,6 +180,7 @@ int ltk_musetalk_infer(ltk_engine* e, const ltk_mt_req* reqs, int nreq, void* st
     const int total = (int)lptr.size();
     int rc = infer_call(e, stream, [&]() -> int {
         int rc = 0;
+        const MtWatched watch(e->mt, e->hw_mt, e->hw_mt.begin());
         for (int f0 = 0; f0 < total && !rc; f0 += e->mt_max_frames) {
             const int nf = std::min(e->mt_max_frames, total - f0);
             PtrList64 lp, fp;
@@ -196,6 +218,12 @@ int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n) {
     CHK(hipMalloc((void**)&e->d_wlogspec, (size_t)80 * 3000 * sizeof(float)));
     CHK(hipMalloc((void**)&e->d_wpcm, (size_t)480000 * sizeof(float)));
     CHK(hipMalloc((void**)&e->d_wgmax, 16));
+    if (e->hw_whisper.alloc(mt_op_count(wg))) {       // nothing half-loaded stays behind
+        (void)hipFree(e->d_wbasis); (void)hipFree(e->d_wlogspec); (void)hipFree(e->d_wpcm); (void)hipFree(e->d_wgmax);
+        e->d_wbasis = nullptr; e->d_wlogspec = nullptr; e->d_wpcm = nullptr; e->d_wgmax = nullptr;
+        mt_graph_delete(wg);
+        return fail(LTK_E_NOMEM, "health table allocation failed");
+    }
     e->whisper = wg;
     return LTK_OK;
 }
@@ -205,8 +233,10 @@ int ltk_whisper_load(ltk_engine* e, const ltk_named_tensor* encoder_sd, int n) {
 namespace {
 
 // under e->mu: one clip through the single-clip program (upload, log-mel, encoder, chunk gather), enqueued on the compute stream
-int whisper_step_locked(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out) {
+// (`watched`: the engine call is one of a headroom watch's, ltk_health_watch)
+int whisper_step_locked(ltk_engine* e, const float* pcm, int n_samples, int batch, int first_row, int row_step, int rows, void* d_out, bool watched) {
     hipStream_t s = e->compute;
+    const MtWatched watch(e->whisper, e->hw_whisper, watched);
     CHK(hipMemcpyAsync(e->d_wpcm, pcm, (size_t)n_samples * sizeof(float), hipMemcpyHostToDevice, s));
     int cbt, cb0;
     f16* mel = mt_latent_in(e->whisper, &cbt);
@@ -249,9 +279,10 @@ int whisper_batch_build(ltk_engine* e) {
 }
 
 // under e->mu: requests reqs[0..nf) as the nf images of one run of the batched program
-int whisper_batch_run_locked(ltk_engine* e, const ltk_whisper_req* reqs, int nf) {
+int whisper_batch_run_locked(ltk_engine* e, const ltk_whisper_req* reqs, int nf, bool watched) {
     int rc = whisper_batch_build(e);
     if (rc) return rc;
+    const MtWatched watch(e->whisper_b, e->hw_whisper, watched);      // the single-clip program's table: one op list
     hipStream_t s = e->compute;
     // every clip by a pageable copy of its own, as the single step's: the runtime has read the caller's samples when the call returns,
     // so no host staging block of ours can be refilled under a copy of the call in flight in front (the device block is stream-ordered)
@@ -293,7 +324,9 @@ int ltk_whisper_step(ltk_engine* e, const float* pcm, int n_samples, int batch, 
         return fail(LTK_E_INVALID, "bad arguments");
     if (!e->whisper) return fail(LTK_E_STATE, "ltk_whisper_load has not been called");
     CHK(enter_device(e->device));
-    return infer_call(e, stream, [&]() -> int { return whisper_step_locked(e, pcm, n_samples, batch, first_row, row_step, rows, d_out); });
+    return infer_call(e, stream, [&]() -> int {
+        return whisper_step_locked(e, pcm, n_samples, batch, first_row, row_step, rows, d_out, e->hw_whisper.begin());
+    });
 }
 
 // N concurrent live steps in one call.  whisper_batch_plan cuts the call into runs of at most kWhisperBatchClips in request order; a
@@ -321,10 +354,11 @@ int ltk_whisper_step_batch(ltk_engine* e, const ltk_whisper_req* reqs, int nreq)
                                 nullptr);
     CHK(enter_device(e->device));
     return infer_call(e, nullptr, [&]() -> int {
+        const bool watched = e->hw_whisper.begin();
         for (const WhisperRun& run : runs) {
             const ltk_whisper_req* q = reqs + run.first;
-            const int rc = run.batched ? whisper_batch_run_locked(e, q, run.count)
-                                       : whisper_step_locked(e, q->pcm, q->n_samples, q->batch, q->first_row, q->row_step, q->rows, q->d_out);
+            const int rc = run.batched ? whisper_batch_run_locked(e, q, run.count, watched)
+                                       : whisper_step_locked(e, q->pcm, q->n_samples, q->batch, q->first_row, q->row_step, q->rows, q->d_out, watched);
             if (rc) return rc;
         }
         return LTK_OK;
@@ -389,6 +423,7 @@ void ltk::hubert_unload(ltk_engine* e) {
     if (e->hubert_w) { mt_graph_delete(e->hubert_w); e->hubert_w = nullptr; }
     if (e->d_hpcm) { (void)hipFree(e->d_hpcm); e->d_hpcm = nullptr; e->hpcm_cap = 0; }
     if (e->d_hstats) { (void)hipFree(e->d_hstats); e->d_hstats = nullptr; }
+    e->hw_hubert.release();
     if (e->d_hrows) { (void)hipFree(e->d_hrows); e->d_hrows = nullptr; e->hrows_cap = 0; }
 }
 
@@ -412,10 +447,12 @@ int hubert_upload(ltk_engine* e, const float* pcm, long long n, hipStream_t s) {
 }
 
 // under e->mu: one forward of samples [off, off + len) of the uploaded utterance; *prog = the program that holds the result
-int hubert_forward(ltk_engine* e, long long off, int len, MtGraph** prog) {
+// (`watched`: the engine call is one of a headroom watch's; every program of the model scans into the model's one table)
+int hubert_forward(ltk_engine* e, long long off, int len, MtGraph** prog, bool watched) {
     int rc;
     MtGraph* g = hubert_program(e, len, &rc);
     if (!g) return rc;
+    const MtWatched watch(g, e->hw_hubert, watched);
     launch_hubert_normalise_n(e->d_hpcm + off, len, 1, e->d_hstats, e->d_hstats + 2, mt_hubert_pcm_in(g), e->compute);
     rc = run_program(e, g, 1);
     if (rc) return conv_status(rc, std::string("hubert: ") + mt_graph_error(g));
@@ -443,6 +480,10 @@ int ltk_hubert_load(ltk_engine* e, const ltk_named_tensor* sd, int n) {
         mt_graph_delete(wg);
         return fail(LTK_E_NOMEM, "hubert: hipMalloc failed");
     }
+    if (e->hw_hubert.alloc(mt_op_count(wg))) {
+        mt_graph_delete(wg);
+        return fail(LTK_E_NOMEM, "hubert: health table allocation failed");
+    }
     e->hubert_w = wg;
     return LTK_OK;
 }
@@ -461,6 +502,7 @@ int ltk_hubert_features(ltk_engine* e, const float* pcm, long long n_samples, fl
     int rc = hubert_upload(e, pcm, n_samples, s);
     if (rc) return drained(rc);
     // audio2feature.py:24-47: clips of 320 000 samples, each forwarded with the 80 samples behind it; then the tail if it has a kernel's length
+    const bool watched = e->hw_hubert.begin();
     std::vector<std::pair<long long, int>> clips;
     const long long n_iter = n_samples / kHubertClip;
     for (long long i = 0; i < n_iter; ++i)
@@ -469,7 +511,7 @@ int ltk_hubert_features(ltk_engine* e, const float* pcm, long long n_samples, fl
     long long total = 0;
     for (auto& c : clips) {
         MtGraph* prog = nullptr;
-        rc = hubert_forward(e, c.first, c.second, &prog);
+        rc = hubert_forward(e, c.first, c.second, &prog, watched);
         if (rc) break;
         const int T = mt_hubert_rows(prog);
         const int take = (int)std::max<long long>(0, std::min<long long>(T, expected - total));
@@ -511,7 +553,7 @@ int ltk_hubert_step(ltk_engine* e, const float* pcm, int n_samples, int batch, i
         int rc = hubert_upload(e, pcm, n_samples, s);
         if (rc) return rc;
         MtGraph* prog = nullptr;
-        rc = hubert_forward(e, 0, n_samples, &prog);
+        rc = hubert_forward(e, 0, n_samples, &prog, e->hw_hubert.begin());
         if (rc) return rc;
         int cbt, cb0;
         const f16* h = mt_hubert_out(prog, &cbt, &cb0);
@@ -538,6 +580,7 @@ int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq) {
     return infer_call(e, nullptr, [&]() -> int {
         if (!e->hubert_w) return fail(LTK_E_STATE, "ltk_hubert_load has not been called");
         hipStream_t s = e->compute;
+        const bool watched = e->hw_hubert.begin();
         std::vector<int> ns(nreq);
         for (int r = 0; r < nreq; ++r) ns[r] = reqs[r].n_samples;
         int cbt, cb0;
@@ -548,7 +591,7 @@ int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq) {
                 int rc = hubert_upload(e, q.pcm, n, s);
                 if (rc) return rc;
                 MtGraph* prog = nullptr;
-                rc = hubert_forward(e, 0, n, &prog);
+                rc = hubert_forward(e, 0, n, &prog, watched);
                 if (rc) return rc;
                 const f16* h = mt_hubert_out(prog, &cbt, &cb0);
                 launch_hubert_chunks(h, cb0, mt_hubert_rows(prog), q.batch, q.first_row, q.row_step, q.rows, (float*)q.d_out, s);
@@ -571,6 +614,7 @@ int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq) {
             MtGraph* g = hubert_cached_program(e, e->hubert_bprogs, kHubertBatchPrograms, n, kHubertBatchClips, &rc);
             if (!g) return rc;
             launch_hubert_normalise_n(e->d_hbpcm, n, nf, e->d_hbstats, e->d_hbstats + 2 * kHubertBatchClips, mt_hubert_pcm_in(g), s);
+            const MtWatched watch(g, e->hw_hubert, watched);
             rc = run_program(e, g, nf);
             if (rc) return conv_status(rc, std::string("hubert: ") + mt_graph_error(g));
             e->hubert_blast = g; e->hubert_blast_nf = nf;

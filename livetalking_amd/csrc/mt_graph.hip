@@ -365,6 +365,12 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
 
 static int mt_run_op(MtGraph& g, const MtOp& op, int nf, float* partial, size_t partial_cap, hipStream_t s) {
     const int rc = mt_run_op_body(g, op, nf, partial, partial_cap, s);
+    if (!rc && g.health && op.y.buf >= 0) {                            // a watched call: this op's record (an op without an output tensor stays unobserved)
+        const int gran = op.y.q8 ? 32 : 16;
+        const size_t oi = (size_t)(&op - g.ops.data());
+        launch_health_scan(g.bufs[op.y.buf], nf, op.y.ld / gran, op.y.coff / gran, op.y.C / gran, op.y.P(), op.y.q8 ? 1 : 0, g.health + oi, s);
+        if (g.health_obs) g.health_obs[oi] = 1;
+    }
     if (!rc && g.sat_ctr && op.y.buf >= 0 && knob(K_SAT_CHECK)) {      // debug: what this op clamped to (or pushed past) the limit of its output type
         const int gran = op.y.q8 ? 32 : 16;
         launch_sat_scan(g.bufs[op.y.buf], nf, op.y.ld / gran, op.y.coff / gran, op.y.C / gran, op.y.P(), op.y.q8 ? 1 : 0, g.sat_ctr, s);
@@ -426,6 +432,17 @@ int mt_gn_error(MtGraph* g) {
 }
 
 void mt_set_sat_counter(MtGraph* g, unsigned long long* d_ctr) { g->sat_ctr = d_ctr; }
+void mt_set_health(MtGraph* g, HealthRec* recs, unsigned char* observed) { g->health = recs; g->health_obs = observed; }
+bool mt_health_on(const MtGraph* g) { return g->health != nullptr; }
+const void* mt_op_out(MtGraph* g, const char* name, int* C, int* ld, int* coff, int* P, int* q8) {
+    for (const MtOp& op : g->ops)
+        if (op.name == name && op.y.buf >= 0) {
+            *C = op.y.C; *ld = op.y.ld; *coff = op.y.coff; *P = op.y.P(); *q8 = op.y.q8 ? 1 : 0;
+            return g->bufs[op.y.buf];
+        }
+    return nullptr;
+}
+int mt_op_out_q8(MtGraph* g, int i) { return i >= 0 && i < (int)g->ops.size() && g->ops[i].y.buf >= 0 && g->ops[i].y.q8 ? 1 : 0; }
 void mt_set_fp8(MtGraph* g, int on, float act_scale) { g->fp8 = on != 0; if (act_scale > 0.f) g->fp8_ascale = act_scale; }
 double mt_macs_fp8_per_frame(const MtGraph* g) { return g->macs_fp8; }
 int mt_run(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s) { return mt_graph_run(*g, nf, partial, partial_cap, s, 0, -1); }

@@ -25,6 +25,15 @@ void mt_set_fp8(MtGraph* g, int on, float act_scale);
 double mt_macs_fp8_per_frame(const MtGraph* g);
 // debug (knob SAT_CHECK): device counters [2] (halfs at the fp16 / e4m3 limit, non-finite ones) that every op's output is scanned into
 void mt_set_sat_counter(MtGraph* g, unsigned long long* d_ctr);
+// ltk_health_watch: while `recs` is set (one record per op, misc_kernels.h HealthRec), every run scans each op's output into its
+// record, one launch behind the op on its stream, and marks it in observed[op]; null (the default) launches nothing.  The engine sets
+// it for a watched call's runs only and runs those outside the graph cache (run_program).
+struct HealthRec;
+void mt_set_health(MtGraph* g, HealthRec* recs, unsigned char* observed);
+bool mt_health_on(const MtGraph* g);
+// the output view of the op named `name` (null: no such op, or it has no output tensor): the buffer, and the view's geometry
+const void* mt_op_out(MtGraph* g, const char* name, int* C, int* ld, int* coff, int* P, int* q8);
+int mt_op_out_q8(MtGraph* g, int i);           // 1: op i writes an e4m3 tensor (fp8 conv path), 0: fp16 (or nothing)
 // builds U-Net then VAE decoder; returns 0 or a negative code
 int mt_build(MtGraph* g, const ltk_named_tensor* unet_sd, int n_unet, const ltk_named_tensor* vae_sd, int n_vae, int frames);
 // tensors the engine feeds / reads

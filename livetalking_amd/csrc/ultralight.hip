@@ -454,6 +454,8 @@ int ul_enqueue(ltk_engine* e, const UlProgram* w, int nf, hipStream_t s, const U
         }
         if (rc) return conv_status(rc, op.name + ": " + err);
         CHK(hipGetLastError());
+        // a watched call: what this launch left in the arena (the head writes bytes; a fused block's hidden tensors never exist)
+        if (a.health && y && op.type != UL_HEAD) a.health->scan(opi, y, nf, oldb, ocb, op.C / 16, (long long)op.Ho * op.Wo, 0, s);
         if (e->capture) {           // ltk_debug_capture: every op's output as NCHW float32 under its name
             std::vector<float>& t = e->taps[op.name];
             t.resize((size_t)nf * op.Creal * op.Ho * op.Wo);
@@ -548,7 +550,7 @@ int ul_pass(ltk_engine* e, const UlAvatar& av, int nf, UlPassArgs a) {
     hipStream_t s = e->compute;
     auto enq = [&]() -> int { return ul_enqueue(e, av.prog.get(), nf, s, a); };
     // the product configuration (bank crops in, uint8 frames out) has no per-call arguments: captured and replayed (knob GRAPH)
-    if (knob(K_GRAPH) && !a.d_img6 && !a.d_pred_f32 && !e->capture) {
+    if (knob(K_GRAPH) && !a.d_img6 && !a.d_pred_f32 && !e->capture && !a.health) {
         if (!a.own) return e->prog_graphs.run(e, std::make_pair(ul_graph_token(av.id), nf), s, "ultralight pass", nf, enq);
         // the launches follow the run lengths of `own` alone: one graph per (avatar, composition)
         std::vector<int> comp;
@@ -582,6 +584,18 @@ int ul_pass_grouped(ltk_engine* e, int nf) {
 }
 
 }  // namespace
+
+void ul_health_listing(std::vector<std::string>* names, std::vector<int>* types, std::vector<int>* arch_index) {
+    const UlArch& A = ul_arch();
+    const bool fused = knob(K_UL_FUSE_IR) != 0;
+    const std::vector<ltk_ul_op_info> ls = ul_listing(fused ? 1 : 0);
+    size_t li = 0;
+    for (size_t at = 0; at < A.ops.size() && li < ls.size(); ++at, ++li) {      // ul_listing's walk
+        const UlBlock* b = fused ? ul_fused_block(A, at) : nullptr;
+        if (b) at = b->project;
+        names->push_back(ls[li].name); types->push_back(ls[li].type); arch_index->push_back((int)at);
+    }
+}
 
 void ul_drop_graphs(ltk_engine* e, int avatar_id) {
     ul_erase_graphs(e, [avatar_id](const void* tok) { return ul_token_is_avatar(tok, avatar_id); });
@@ -640,7 +654,9 @@ namespace {
 
 // The body of both infer entries, under e->mu: the passes ul_merge_plan cuts `nreq` checked requests into (hold[r]: request r's avatar,
 // kept alive until the call has synchronised), each behind its tables in stream order, and the report (or null).
-int ul_run_requests(ltk_engine* e, const ltk_ul_req* reqs, const std::shared_ptr<UlAvatar>* hold, int nreq, int mode, ltk_ul_merge_report* rep) {
+// `watched`: the avatars whose headroom watch counts this engine call (ul_health_begin); their per-avatar passes are scanned.
+int ul_run_requests(ltk_engine* e, const ltk_ul_req* reqs, const std::shared_ptr<UlAvatar>* hold, int nreq, int mode, ltk_ul_merge_report* rep,
+                    const std::vector<const UlAvatar*>& watched) {
     const int cap = std::min(e->ul_frames, kPackMaxFrames);
     if (cap <= 0) return fail(LTK_E_STATE, "no Ultralight arena");
     std::vector<int> av(nreq), nb(nreq);
@@ -675,6 +691,8 @@ int ul_run_requests(ltk_engine* e, const ltk_ul_req* reqs, const std::shared_ptr
         if (hipGetLastError() != hipSuccess) return fail(LTK_E_HIP, "pointer table upload failed");
         UlPassArgs a;
         a.own = &own;
+        if (ps.path != UL_PATH_GROUPED && std::find(watched.begin(), watched.end(), hold[ps.spans[0].req].get()) != watched.end())
+            a.health = hold[ps.spans[0].req]->health.get();
         const int rc = ps.path == UL_PATH_GROUPED ? ul_pass_grouped(e, ps.nf) : ul_pass(e, *hold[ps.spans[0].req], ps.nf, a);
         if (rc) return rc;
         if (rep) {
@@ -687,6 +705,17 @@ int ul_run_requests(ltk_engine* e, const ltk_ul_req* reqs, const std::shared_ptr
         }
     }
     return 0;
+}
+
+// under e->mu, once per engine call: every avatar of the call whose watch is armed counts the call
+std::vector<const UlAvatar*> ul_health_begin(const std::shared_ptr<UlAvatar>* hold, int nreq) {
+    std::vector<const UlAvatar*> watched;
+    for (int r = 0; r < nreq; ++r) {
+        const UlAvatar* a = hold[r].get();
+        if (std::find(watched.begin(), watched.end(), a) != watched.end() || !a->health || a->health->left <= 0) continue;
+        if (a->health->begin()) watched.push_back(a);
+    }
+    return watched;
 }
 
 }  // namespace
@@ -715,6 +744,8 @@ int ltk_ultralight_avatar_register(ltk_engine* e, const ltk_named_tensor* sd, in
     a.prog.reset(new UlProgram());
     int rc = build_ul_operands(a.prog.get(), sd, n_tensors);
     if (rc) return rc;                      // (the avatar's destructor frees the half-built program)
+    a.health.reset(new HealthWatch());
+    if (a.health->alloc((int)ul_arch().ops.size())) return fail(LTK_E_NOMEM, "health table allocation failed");
     const size_t fb = (size_t)n * kUlFace * kUlFace * 3, ub = (size_t)n * H * W * 3;
     CHK(hipMalloc((void**)&a.d_face, fb));
     CHK(hipMalloc((void**)&a.d_full, ub));
@@ -743,7 +774,8 @@ int ltk_ultralight_infer(ltk_engine* e, const ltk_ul_req* reqs, int nreq, void* 
     CHK(enter_device(e->device));
     return infer_call(e, stream, [&]() -> int {
         int rc = 0;
-        for (int r = 0; r < nreq && !rc; ++r) rc = ul_run_requests(e, reqs + r, hold.data() + r, 1, /* mode: per avatar */ 1, nullptr);
+        const std::vector<const UlAvatar*> watched = ul_health_begin(hold.data(), nreq);
+        for (int r = 0; r < nreq && !rc; ++r) rc = ul_run_requests(e, reqs + r, hold.data() + r, 1, /* mode: per avatar */ 1, nullptr, watched);
         return rc;
     });
 }
@@ -762,7 +794,7 @@ int ltk_ultralight_infer_merged(ltk_engine* e, const ltk_ul_req* reqs, int nreq,
     }
     if (rep) memset(rep, 0, sizeof(*rep));
     CHK(enter_device(e->device));
-    return infer_call(e, stream, [&]() -> int { return ul_run_requests(e, reqs, hold.data(), nreq, mode, rep); });
+    return infer_call(e, stream, [&]() -> int { return ul_run_requests(e, reqs, hold.data(), nreq, mode, rep, ul_health_begin(hold.data(), nreq)); });
 }
 
 int ltk_ultralight_info(ltk_engine* e, int* arena_frames, size_t* arena_bytes, size_t* bytes_per_frame, int* grouped) {

@@ -64,7 +64,8 @@ int ltk::launch_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, cons
     // one launch instead of ~70: a single session's step is 0..1.8 % faster end to end depending on the box's host (three interleaved pairs on the
     // last box: 1.3836 / 1.3904 / 1.3956 ms eager, 1.3619 / 1.3699 / 1.3596 ms replayed), and a host serving hundreds of sessions sustains 512 instead
     // of 448 of them (profiles/r04_delivered_graph_ab.txt).
-    const bool graphable = knob(K_GRAPH) && bank_faces && fused && e->c7 && s == e->compute;
+    // (a watched call, ltk_health_watch, runs these launches eagerly with its scans between them and leaves the graph cache alone)
+    const bool graphable = knob(K_GRAPH) && bank_faces && fused && e->c7 && s == e->compute && !e->w2l_scan;
     if (!graphable) {
         const bool product = bank_faces && fused && e->c7 && s == e->compute;
         if ((par || have_feats) && !product) return fail(LTK_E_STATE, "pipelined pass outside the product configuration");
@@ -198,6 +199,10 @@ static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, v
         // knob FACE_CACHE: every avatar of the call gets its skip cache on first use (and again after a knob change); the call then
         // runs without the face encoder.  The mode needs the product configuration (fused head, no layer capture).
         const bool cached = want_cache && !e->capture && knob(K_HEAD_FUSED);
+        // ltk_health_watch: a watched call takes the whole-pass route (the prefetched encoder's frames are byte-identical), eagerly, with
+        // a scan behind every layer; it is not deferred, and it neither reads nor writes the prefetch slots and session records, so the
+        // calls behind the window meet them as the calls of a fresh session do
+        const bool watched = e->hw_w2l.begin();
         if (cached) {
             for (auto& ap : hold)
                 if (!rc && (!ap->d_feat || ap->feat_epoch != knob_epoch())) rc = build_face_cache(e, *ap);
@@ -216,7 +221,7 @@ static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, v
         // knob PREFETCH: a single-request call of <= 32 frames finds the face-encoder outputs of its frames in the slot a previous call of
         // its session prefetched them into (key: avatar, first bank index, frame count), and - when it continues a session's sequence
         // (it was a hit, or it starts where a recent solo call of the same avatar and size ended) - prefetches the next call's in turn
-        const bool solo = nreq == 1 && !cached && knob(K_PREFETCH) && e->alt_frames > 0 && total <= std::min(e->alt_frames, mbs) &&
+        const bool solo = !watched && nreq == 1 && !cached && knob(K_PREFETCH) && e->alt_frames > 0 && total <= std::min(e->alt_frames, mbs) &&
                           !e->capture && knob(K_HEAD_FUSED) && e->c7;
         // knob DEFER: a solo call that was asked to may return with its pass in flight
         const bool defer = solo && dc && dc->want && knob(K_DEFER) != 0;
@@ -241,6 +246,7 @@ static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, v
             e->pfs[slot].stamp = ++e->pf_clock;
         }
         if (timing) tp1 = std::chrono::steady_clock::now();
+        e->w2l_scan = watched ? &e->hw_w2l : nullptr;
         for (int f0 = 0; f0 < total && !rc; f0 += mbs) {
             const int nf = std::min(mbs, total - f0);
             FacePtrs fp; MelPtrs mp; OutPtrs op;
@@ -249,6 +255,7 @@ static int w2l_infer_checked(ltk_engine* e, const ltk_w2l_req* reqs, int nreq, v
             if (hipGetLastError() != hipSuccess) rc = fail(LTK_E_HIP, "pointer table upload failed");
             else rc = launch_pass(e, nf, e->compute, true, nullptr, true, nullptr, cached, par, hit);
         }
+        e->w2l_scan = nullptr;
         if (hit) {                              // the next prefetch into this slot starts behind this pass
             if (hipEventRecord(e->pfs[slot].ev_read, e->compute) != hipSuccess) { if (!rc) rc = fail(LTK_E_HIP, "hipEventRecord failed"); }
             else e->pfs[slot].read = true;

@@ -310,6 +310,7 @@ void wav2lip_unload(ltk_engine* e) {
     (void)drain_pending(e);                                  // knob DEFER: a pass still in flight works in the buffers that go away below
     if (e->aux2) (void)hipStreamSynchronize(e->aux2);        // an outstanding prefetch writes them too
     e->graphs.drop();
+    e->hw_w2l.release(); e->w2l_scan = nullptr;
     if (e->d_tab) { (void)hipFree(e->d_tab); e->d_tab = nullptr; }
     for (Layer& L : e->layers) {
         conv_plan_destroy(&L.plan); rowgemm_plan_destroy(&L.rg);
@@ -567,6 +568,11 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
         // debug (knob SAT_CHECK): count what this layer's epilogue clamped to the fp16 limit (a fused head writes bytes: run it unfused)
         if (knob(K_SAT_CHECK) && !(io.head_w && io.head_outs))
             launch_sat_scan(io.y, n, L.out_ld / 16, L.out_coff / 16, (L.plan.Cout + 15) / 16, (long long)L.Ho * L.Wo, 0, e->d_sat, on_aux ? e->aux : s);
+        // a watched call (ltk_health_watch): this layer's record, on the layer's stream.  The fused head's 32-channel map never reaches
+        // memory: that layer stays unobserved
+        if (e->w2l_scan && !(io.head_w && io.head_outs))
+            e->w2l_scan->scan((int)(&L - e->layers.data()), io.y, n, L.out_ld / 16, L.out_coff / 16, (L.plan.Cout + 15) / 16, (long long)L.Ho * L.Wo, 0,
+                              on_aux ? e->aux : s);
         return 0;
     };
     // depth-first region: [df_first, end) of `order`
@@ -661,6 +667,7 @@ int ltk_wav2lip_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int max_f
             if (hipMalloc((void**)&e->d_tab_next, sizeof(DevTables)) != hipSuccess) return fail(LTK_E_NOMEM, "pointer table allocation failed");
             CHK(hipMemset(e->d_tab_next, 0, sizeof(DevTables)));
         }
+        if (e->hw_w2l.alloc((int)e->layers.size())) return fail(LTK_E_NOMEM, "health table allocation failed");
         return LTK_OK;
     }();
     if (rc) { wav2lip_unload(e); return rc; }       // nothing half-built stays behind (the error text is already set)

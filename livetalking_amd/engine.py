@@ -501,6 +501,12 @@ class Engine:
                                                        frames.ctypes.data if want_frames else None))
         return unet_out, image, frames
 
+    def musetalk_debug_get_q8(self, op: str, shape) -> np.ndarray:
+        """Raw e4m3 codes (uint8, shape (frames, C, H * W)) of an fp8-path op's output as the last pass left it (include/ltk.h)."""
+        out = np.empty(shape, dtype=np.uint8)
+        _lib.check(self._lib.ltk_musetalk_debug_get_q8(self._h, op.encode(), int(shape[0]), out.ctypes.data, out.size))
+        return out
+
     def musetalk_debug_get(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, dtype=np.float32)
         _lib.check(self._lib.ltk_musetalk_debug_get(self._h, name.encode(), int(shape[0]), out.ctypes.data, out.size))
@@ -726,6 +732,43 @@ class Engine:
         _lib.check(self._lib.ltk_hubert_chunks_host(self._h, feat.ctypes.data, feat.shape[0], int(batch), int(first_row), int(row_step),
                                                     int(rows), out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ fp16 headroom watch (include/ltk.h: ltk_health_*)
+    @staticmethod
+    def _health_program(program) -> int:
+        if isinstance(program, str):
+            if program not in _lib.HEALTH_PROGRAMS:
+                raise ValueError(f"unknown program {program!r}: one of {sorted(_lib.HEALTH_PROGRAMS)}")
+            return _lib.HEALTH_PROGRAMS[program]
+        return int(program)
+
+    @staticmethod
+    def _health_dict(o) -> dict:
+        return {"name": o.name.decode(), "type": int(o.type), "observed": int(o.observed), "q8": int(o.q8), "elements": int(o.elements),
+                "at_limit": int(o.at_limit), "near_limit": int(o.near_limit), "nonfinite": int(o.nonfinite), "max_abs": float(o.max_abs),
+                "limit": float(o.limit)}
+
+    def health_watch(self, program, calls: int, avatar_id: int = -1):
+        """Arm the next `calls` inference calls of `program` ("wav2lip", "musetalk", "ultralight", "whisper", "hubert" or an
+        LTK_HEALTH_* code): each runs its usual launches with a scan behind every op.  0 disarms.  avatar_id: Ultralight only."""
+        _lib.check(self._lib.ltk_health_watch(self._h, self._health_program(program), int(avatar_id), int(calls)))
+
+    def health_report(self, program, avatar_id: int = -1):
+        """(ops, calls_seen, calls_left): one dict per op of the program's listing (name, type, observed, q8, elements, at_limit,
+        near_limit, nonfinite, max_abs, limit), accumulated over the watched calls since the watch was armed.  Waits for the device."""
+        prog = self._health_program(program)
+        cap = 1024
+        ops = (_lib.HealthOp * cap)()
+        n, seen, left = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(self._lib.ltk_health_report(self._h, prog, int(avatar_id), ops, cap, C.byref(n), C.byref(seen), C.byref(left)))
+        return [self._health_dict(ops[i]) for i in range(n.value)], int(seen.value), int(left.value)
+
+    def health_scan(self, d_x: int, N: int, cbt: int, cb0: int, CB: int, P: int, q8: bool = False) -> dict:
+        """The scan kernel on one tensor view: device fp16 [N][cbt][P][16] (or e4m3 [N][cbt][P][32] with q8), channel blocks
+        [cb0, cb0 + CB).  The caller's work on d_x must be complete."""
+        rec = _lib.HealthOp()
+        _lib.check(self._lib.ltk_health_scan(self._h, int(d_x), int(N), int(cbt), int(cb0), int(CB), int(P), 1 if q8 else 0, C.byref(rec)))
+        return self._health_dict(rec)
 
     # ------------------------------------------------------------------ test / measurement hooks
     def wav2lip_forward_host(self, mel: np.ndarray, face6: np.ndarray) -> np.ndarray:
