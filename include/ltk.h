@@ -399,9 +399,10 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
 
 /* =========================== fp16 headroom watch: the first calls on a real checkpoint =========================== */
 
-/* The conv epilogues clamp to +-65504 (+-448 on the e4m3 tensors of the fp8 path) and nothing reports it: a checkpoint whose
- * activations reach the limit renders wrong frames silently.  A watch is armed for the next `calls` inference calls of ONE program and
- * disarms itself after them.  A watched call issues exactly the compute launches it would issue unwatched - same routes, tiles,
+/* The conv epilogues clamp to the fp16 range (fmed3f(t, -65504, 65504); +-448 on the e4m3 tensors of the fp8 path) and nothing reports
+ * it: a network whose activations reach the limit is no longer computing the reference's fp32 numbers, the fp16 parity tolerance does
+ * not hold from there on, and the checkpoint renders wrong frames silently.
+ * A watch is armed for the next `calls` inference calls of ONE program and disarms itself after them.  A watched call issues exactly the compute launches it would issue unwatched - same routes, tiles,
  * split-K factors, fused head, fused inverted residuals - launch by launch instead of from a captured graph (the graph cache is neither
  * read nor written, no knob changes, no graph is dropped), with one scan launch behind every op whose output is in memory, on that
  * op's stream: its frames and features are byte-identical to the unwatched call's.  One engine call counts as one call, whatever its
@@ -576,14 +577,6 @@ int ltk_debug_ul_merge_plan(const int* avatar, const int* batch, int nreq, int c
 
 /* After a forward with capture enabled, copy one layer's activation
  * (state_dict prefix, e.g. "face_encoder_blocks.1.0") as NCHW float32. */
-/* Saturation counters (debug; knob SAT_CHECK = 1, environment LTK_SAT_CHECK or ltk_debug_set_knob).  The conv epilogues clamp to
- * the fp16 range (fmed3f(t, -65504, 65504)): a network whose activations reach it is no longer computing the reference's fp32
- * numbers, and the fp16 parity tolerance does not hold from there on.  With the knob on, every layer's / op's output (Wav2Lip
- * layers, MuseTalk ops incl. the e4m3 tensors of the fp8 path) is scanned as it is produced: `n_at_limit` = values exactly at the
- * limit of their type (what a clamp leaves behind), `n_nonfinite` = inf / NaN (a kernel without a clamp overflowed).  Waits for
- * the device; `reset` != 0 zeroes the counters afterwards.  Reference: the reference runs these networks in fp32 on the CPU and
- * fp16 autocast on CUDA (avatars/wav2lip_avatar.py:51-70, avatars/musetalk_avatar.py:57-66); it has no such check. */
-int ltk_debug_saturation(ltk_engine* e, int reset, unsigned long long* n_at_limit, unsigned long long* n_nonfinite);
 int ltk_debug_capture(ltk_engine* e, int enable);
 int ltk_debug_get(ltk_engine* e, const char* layer, float* out, size_t n_floats);
 

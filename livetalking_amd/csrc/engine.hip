@@ -53,6 +53,13 @@ const char* ltk_version(void) { return "ltk_hip 0.1 (gfx950)"; }
 
 int ltk_engine_create(int device, ltk_engine** out) {
     if (!out) return fail(LTK_E_INVALID, "out is null");
+    // a knob that no longer exists would be ignored in silence: say so, once per process
+    static std::once_flag stale_env;
+    if (getenv("LTK_SAT_CHECK"))
+        std::call_once(stale_env, [] {
+            fprintf(stderr, "ltk: LTK_SAT_CHECK is set, but that knob has been removed and scans nothing: use LTK_HEALTH_WATCH=N "
+                            "(ltk_health_watch) or scripts/checkpoint_health.py instead\n");
+        });
     int ndev = 0;
     CHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(LTK_E_INVALID, "no such HIP device");
@@ -71,8 +78,6 @@ int ltk_engine_create(int device, ltk_engine** out) {
     CHK(hipMalloc((void**)&e->d_partial, e->partial_cap));
     CHK(hipMalloc((void**)&e->d_partial_aux, e->partial_aux_cap));
     CHK(hipMalloc((void**)&e->d_partial_pf, e->partial_pf_cap));
-    CHK(hipMalloc((void**)&e->d_sat, 2 * sizeof(unsigned long long)));
-    CHK(hipMemset(e->d_sat, 0, 2 * sizeof(unsigned long long)));
     std::vector<float> basis;
     std::vector<int32_t> lohi;
     build_mel_basis(&basis, &lohi);
@@ -120,7 +125,6 @@ void ltk_engine_destroy(ltk_engine* e) {
     if (e->d_partial) (void)hipFree(e->d_partial);
     if (e->d_partial_aux) (void)hipFree(e->d_partial_aux);
     if (e->d_partial_pf) (void)hipFree(e->d_partial_pf);
-    if (e->d_sat) (void)hipFree(e->d_sat);
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_join) (void)hipEventDestroy(e->ev_join);
     if (e->aux2) (void)hipStreamDestroy(e->aux2);

@@ -38,19 +38,6 @@ int ltk_wav2lip_forward_host(ltk_engine* e, const float* mel, const float* face6
     return LTK_OK;
 }
 
-int ltk_debug_saturation(ltk_engine* e, int reset, unsigned long long* n_at_limit, unsigned long long* n_nonfinite) {
-    if (!e) return fail(LTK_E_INVALID, "bad arguments");
-    CHK(enter_device(e->device));
-    std::lock_guard<std::mutex> g(e->mu);
-    CHK(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    CHK(hipMemcpy(h, e->d_sat, sizeof(h), hipMemcpyDeviceToHost));
-    if (n_at_limit) *n_at_limit = h[0];
-    if (n_nonfinite) *n_nonfinite = h[1];
-    if (reset) CHK(hipMemset(e->d_sat, 0, sizeof(h)));
-    return LTK_OK;
-}
-
 int ltk_debug_capture(ltk_engine* e, int enable) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
     (void)hipSetDevice(e->device);

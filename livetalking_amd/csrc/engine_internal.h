@@ -252,7 +252,6 @@ struct ltk_engine {
     float* d_partial = nullptr;           // conv3 split-K scratch of the compute stream
     float* d_partial_aux = nullptr;       // ... of the aux stream
     float* d_partial_pf = nullptr;        // ... of the prefetch stream (aux2, knob PREFETCH)
-    unsigned long long* d_sat = nullptr;  // [2] saturation counters of knob SAT_CHECK (ltk_debug_saturation): halfs at the fp16 limit, non-finite halfs
     size_t partial_cap = 0, partial_aux_cap = 0, partial_pf_cap = 0;
     // headroom watches (ltk_health_watch), allocated when their program is loaded: Wav2Lip by layer; the MuseTalk, Whisper and HuBERT
     // programs by op (the batched Whisper program and every HuBERT program share their model's table).  w2l_scan: set while a watched

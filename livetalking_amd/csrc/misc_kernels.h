@@ -64,17 +64,12 @@ struct DevTables {
 // host tables (any of them may be null: that table is left alone) -> *d_tab, entries [0, nframes), on stream s
 void launch_upload_tables(const FacePtrs* faces, const MelPtrs* mels, const OutPtrs* outs, int nframes, DevTables* d_tab, hipStream_t s);
 
-// fp16 CB16 (or [N][H][W][8] when ld <= 8) channel range (ld, coff, C) -> float32 NCHW (debug capture).
-// Saturation scan (debug, knob SAT_CHECK): counts, over the channel-blocked tensor view [N][cbt][P][16] blocks [cb0, cb0 + CB), the
-// halfs sitting AT the fp16 limit (|v| == 65504: what an epilogue clamp `fmed3f(t, -65504, 65504)` leaves behind) into ctr[0] and
-// the non-finite ones (a kernel without a clamp overflowed) into ctr[1].  q8 != 0: e4m3 bytes of a [N][cbt][P][32] tensor
-// (|v| == 448 / NaN).  One atomic per wave that found something.
-void launch_sat_scan(const f16* x, int N, int cbt, int cb0, int CB, long long P, int q8, unsigned long long* ctr, hipStream_t s);
-
-// Headroom scan (ltk_health_watch, ltk_health_scan): ONE op's record, accumulated over the same tensor view launch_sat_scan takes.
+// Headroom scan (ltk_health_watch, ltk_health_scan): ONE op's record, accumulated over the channel-blocked tensor view
+// [N][cbt][P][16] halfs, blocks [cb0, cb0 + CB); q8 != 0: e4m3 bytes of a [N][cbt][P][32] tensor.
 // Magnitude codes (the value's bits with the sign dropped) order like the values, so the largest finite code is the largest |v|.
 //   fp16: at_limit code 0x7bff (65504), near_limit 0x7800 <= code < 0x7c00 (the top binade, 32768 ..), nonfinite code >= 0x7c00
 //   e4m3: at_limit code 0x7e (448),     near_limit 0x78 <= code < 0x7f (256 ..),                        nonfinite code 0x7f
+// at_limit is what an epilogue clamp `fmed3f(t, -65504, 65504)` leaves behind, nonfinite what a kernel without a clamp overflowed to.
 // elements counts every value of the view; max_code is the largest finite code.  The kernel is the record's only writer; the host
 // zeroes it when a watch is armed.
 struct HealthRec {
@@ -83,6 +78,7 @@ struct HealthRec {
 };
 void launch_health_scan(const void* x, int N, int cbt, int cb0, int CB, long long P, int q8, HealthRec* rec, hipStream_t s);
 
+// fp16 CB16 (or [N][H][W][8] when ld <= 8) channel range (ld, coff, C) -> float32 NCHW (debug capture).
 void launch_nhwc_to_nchw_f32(const f16* x, int N, int H, int W, int ld, int coff, int C, float* out, hipStream_t s);
 
 // audio.py:45-51 melspectrogram columns + mel.py:56-63 window gather.

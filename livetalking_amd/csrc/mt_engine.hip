@@ -29,7 +29,6 @@ int ltk_musetalk_load(ltk_engine* e, const ltk_named_tensor* unet_sd, int n_unet
     if (e->mt) return fail(LTK_E_STATE, "a MuseTalk model is already loaded in this engine");
     CHK(enter_device(e->device));
     MtGraph* mg = mt_graph_new();
-    mt_set_sat_counter(mg, e->d_sat);
     mt_set_fp8(mg, e->mt_fp8, e->mt_fp8_ascale);
     const int rc = mt_build(mg, unet_sd, n_unet, vae_sd, n_vae, max_frames);
     if (rc) {
@@ -257,7 +256,6 @@ int whisper_step_locked(ltk_engine* e, const float* pcm, int n_samples, int batc
 int whisper_batch_build(ltk_engine* e) {
     if (e->whisper_b) return LTK_OK;
     MtGraph* g = mt_graph_new();
-    mt_set_sat_counter(g, e->d_sat);
     const int brc = mt_build_whisper_batch_graph(g, e->whisper, kWhisperBatchClips);
     float *pcm = nullptr, *logspec = nullptr;
     int* gmax = nullptr;
@@ -393,7 +391,6 @@ MtGraph* hubert_cached_program(ltk_engine* e, std::vector<ltk_engine::HubertProg
         cache.erase(cache.begin() + v);
     }
     MtGraph* g = mt_graph_new();
-    mt_set_sat_counter(g, e->d_sat);
     const int brc = mt_build_hubert_program(g, e->hubert_w, n_samples, frames);
     if (brc) {
         *rc = fail(brc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, std::string("hubert: ") + mt_graph_error(g));

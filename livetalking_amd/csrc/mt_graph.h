@@ -78,7 +78,6 @@ struct MtGraph {
     double macs = 0;                          // conv / linear MACs per frame (attention excluded)
     double macs_fp8 = 0;                      // ... of which on fp8 operands
     std::string err;
-    unsigned long long* sat_ctr = nullptr;    // debug (knob SAT_CHECK): saturation counters every op's output is scanned into
     HealthRec* health = nullptr;              // a watched call's run (mt_set_health): op i's output is scanned into health[i]
     unsigned char* health_obs = nullptr;      // ... and health_obs[i] set
     MtTensor *t_latent = nullptr, *t_ctx = nullptr, *t_unet_out = nullptr, *t_vae_out = nullptr;

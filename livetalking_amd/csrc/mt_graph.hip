@@ -371,10 +371,6 @@ static int mt_run_op(MtGraph& g, const MtOp& op, int nf, float* partial, size_t 
         launch_health_scan(g.bufs[op.y.buf], nf, op.y.ld / gran, op.y.coff / gran, op.y.C / gran, op.y.P(), op.y.q8 ? 1 : 0, g.health + oi, s);
         if (g.health_obs) g.health_obs[oi] = 1;
     }
-    if (!rc && g.sat_ctr && op.y.buf >= 0 && knob(K_SAT_CHECK)) {      // debug: what this op clamped to (or pushed past) the limit of its output type
-        const int gran = op.y.q8 ? 32 : 16;
-        launch_sat_scan(g.bufs[op.y.buf], nf, op.y.ld / gran, op.y.coff / gran, op.y.C / gran, op.y.P(), op.y.q8 ? 1 : 0, g.sat_ctr, s);
-    }
     return rc;
 }
 
@@ -431,7 +427,6 @@ int mt_gn_error(MtGraph* g) {
     return 1;
 }
 
-void mt_set_sat_counter(MtGraph* g, unsigned long long* d_ctr) { g->sat_ctr = d_ctr; }
 void mt_set_health(MtGraph* g, HealthRec* recs, unsigned char* observed) { g->health = recs; g->health_obs = observed; }
 bool mt_health_on(const MtGraph* g) { return g->health != nullptr; }
 const void* mt_op_out(MtGraph* g, const char* name, int* C, int* ld, int* coff, int* P, int* q8) {

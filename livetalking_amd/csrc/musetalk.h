@@ -23,8 +23,6 @@ int mt_gn_error(MtGraph* g);
 // multiplied by before the saturating conversion (<= 0 keeps the default 8)
 void mt_set_fp8(MtGraph* g, int on, float act_scale);
 double mt_macs_fp8_per_frame(const MtGraph* g);
-// debug (knob SAT_CHECK): device counters [2] (halfs at the fp16 / e4m3 limit, non-finite ones) that every op's output is scanned into
-void mt_set_sat_counter(MtGraph* g, unsigned long long* d_ctr);
 // ltk_health_watch: while `recs` is set (one record per op, misc_kernels.h HealthRec), every run scans each op's output into its
 // record, one launch behind the op on its stream, and marks it in observed[op]; null (the default) launches nothing.  The engine sets
 // it for a watched call's runs only and runs those outside the graph cache (run_program).

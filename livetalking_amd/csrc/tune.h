@@ -28,7 +28,6 @@ namespace ltk {
     X(PREFETCH, 1)             /* 1: a session's consecutive single-request calls are software-pipelined across calls; 0: every call runs the whole pass */ \
     X(MT_FUSE, 7)              /* MuseTalk program, read at BUILD: bit 0 GEGLU epilogue, bit 1 stacked cross-attention k | v, bit 2 LayerNorm fold (needs bit 1); 0 = rounds 2-5 */ \
     X(MT_GN1, 1)               /* 1: GroupNorm of maps whose (image, group) fits one block's registers as ONE launch (gn_group_kernel) instead of gn_stats + gn_apply */ \
-    X(SAT_CHECK, 0)            /* debug: scan every layer / op output for values at the limit of its type and non-finite values (ltk_debug_saturation) */ \
     X(FACE_CACHE_MAX_MB, 16384) /* largest face cache ONE avatar may take under FACE_CACHE (16384 MB = a 3 900-frame bank); longer avatars fail with LTK_E_NOMEM */ \
     X(LIN_FK, 1)               /* 1: 1x1 / linear layers with K = 320 / 384 / 512 / 640 / 1280 on >= kLinFkMinRows rows run on lin_fk_kernel; 0: conv3 1x1 */ \
     X(ATTN_LDS, 1)             /* 1: self-attention with head dims 40 / 80 over >= 128 keys shares its K / V^T tiles through LDS (attn_lds_kernel); 0: attn_kernel */ \
@@ -54,8 +53,6 @@ namespace ltk {
 //             ONE value-transpose launch at the head of the pass; bit 2: the transformer blocks' LayerNorms folded into the linear
 //             layers around them.
 // MT_GN1      the U-Net levels and the VAE's 32^2 maps (nn_kernels.hip).
-// SAT_CHECK   what an epilogue's clamp to +-65504 leaves behind (+-448 for e4m3).  The fused Wav2Lip head (which writes bytes) runs
-//             unfused under it.
 // LIN_FK      conv3_mfma.hip: a wave's A rows in registers, full-K 32-cout weight slabs through LDS.
 // ATTN_LDS    the four query tiles of a block share whole 64-key tiles (nn_kernels.hip); under 0 every wave reads them from L2.
 // LIN_MP      conv3_mfma.hip: passes of 1280 channels, the accumulators of 2 or 3 weight slabs per block in registers
@@ -70,9 +67,8 @@ namespace ltk {
 //             the knob says, so it can change at run time (captured passes are keyed by knob_epoch()).  The grouped path (UL_GROUPED,
 //             mode 2) ignores it.  The fused op has one summation order at every frame count: one launch over all frames of a merged pass.
 //             ltk_ultralight_op_name lists a fused block once (type 15) under its project conv's name, and ltk_debug_capture taps only that
-//             output: the .conv.0 / .conv.3 tensors do not exist in a fused pass.  SAT_CHECK: the Ultralight program has no saturation
-//             scan; one added to it would see the fused op's output only, never the hidden tensors.  Default 0 until a follow-up meets
-//             the rule in profiles/ultralight_fuse_ir.txt.
+//             output: the .conv.0 / .conv.3 tensors do not exist in a fused pass.  Default 0 until a follow-up meets the rule in
+//             profiles/ultralight_fuse_ir.txt.
 // DEFER       engine_internal.h infer_call / defer_window.h: a lone session's host turn-around (completion wake-up, Python, the next
 //             call's launches: 40-55 us of a 1.2-ms step) then runs under the pass in flight instead of between two passes.
 

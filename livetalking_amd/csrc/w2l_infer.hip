@@ -58,7 +58,7 @@ static int pass_graph_key(int nf, bool cached, bool have_feats, bool prefetch, i
 int ltk::launch_pass(ltk_engine* e, int nf, hipStream_t s, bool bank_faces, const float* d_face6, bool have_outs, float* d_pred_f32, bool cached, int par,
                      bool have_feats) {
     // the float32 NCHW output (test hook) and layer capture need the 32-channel map in memory: unfused
-    const bool fused = have_outs && !d_pred_f32 && !e->capture && knob(K_HEAD_FUSED) && !knob(K_SAT_CHECK);
+    const bool fused = have_outs && !d_pred_f32 && !e->capture && knob(K_HEAD_FUSED);
     // knob GRAPH: 0 never, non-zero (default 1) every eligible pass.  Measured (profiles/r04_vs_r03_same_job.txt, r04_graph_auto_ab.txt): the replay of a
     // 16-frame pass is ~5-15 us (0.5-1 %) slower on the device than the same launches issued one by one (equal from 64 frames on), the host side is
     // one launch instead of ~70: a single session's step is 0..1.8 % faster end to end depending on the box's host (three interleaved pairs on the

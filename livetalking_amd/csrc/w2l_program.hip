@@ -565,9 +565,6 @@ int run_convs(ltk_engine* e, int nf, hipStream_t s, const OutPtrs* head_outs, st
         else
             rc = conv_launch(L.plan, io, on_aux ? e->aux : s, &err);
         if (rc) return conv_status(rc, L.name + ": " + err);
-        // debug (knob SAT_CHECK): count what this layer's epilogue clamped to the fp16 limit (a fused head writes bytes: run it unfused)
-        if (knob(K_SAT_CHECK) && !(io.head_w && io.head_outs))
-            launch_sat_scan(io.y, n, L.out_ld / 16, L.out_coff / 16, (L.plan.Cout + 15) / 16, (long long)L.Ho * L.Wo, 0, e->d_sat, on_aux ? e->aux : s);
         // a watched call (ltk_health_watch): this layer's record, on the layer's stream.  The fused head's 32-channel map never reaches
         // memory: that layer stays unobserved
         if (e->w2l_scan && !(io.head_w && io.head_outs))

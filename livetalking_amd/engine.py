@@ -786,13 +786,6 @@ class Engine:
         lib = _lib.load()
         _lib.check(lib.ltk_debug_set_knob(name.encode(), int(value)))
 
-    def saturation(self, reset: bool = True):
-        """(values at the fp16 / e4m3 limit, non-finite values) seen in layer / op outputs since the last reset; counted only while
-        knob SAT_CHECK is on (include/ltk.h: ltk_debug_saturation)."""
-        a, b = C.c_ulonglong(), C.c_ulonglong()
-        _lib.check(self._lib.ltk_debug_saturation(self._h, 1 if reset else 0, C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
-
     def debug_capture(self, enable: bool):
         _lib.check(self._lib.ltk_debug_capture(self._h, 1 if enable else 0))
 

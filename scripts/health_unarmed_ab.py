@@ -81,7 +81,7 @@ def main():
     print("# kernels whose launch count differs from the parent's:", diff if diff else "none")
     print("# health_scan_kernel launches:", sum(v for k, v in th.items() if "health_scan" in k))
     if diff == ["__amd_rocclr_fillBufferAligned"]:
-        print("# (a load-time difference: ltk_wav2lip_load zeroes the watch's table of 54 records with one hipMemset; no launch of a pass differs)")
+        print("# (the runtime's fill kernel only: the two builds issue another number of hipMemset calls at engine creation / model load; no launch of a pass differs)")
     bad = any("ltk" in k for k in diff)
     print(f"\n# 2b. python bench.py --gpus 1 --steps 200 --warmup 20, legs interleaved (parent, this) x {a.pairs}: the timed line")
     ms = {"parent": [], "this": []}

@@ -11,10 +11,11 @@ before setting LTK_HUBERT_ENGINE=1:
 1. loads HubertModel.from_pretrained(model) and hands its state dict to Engine.load_hubert (a missing tensor or a wrong shape
    ends here with the engine's message);
 2. runs `--seconds` of audio (16 kHz mono from --wav, else a seeded speech-like signal) through get_hubert_from_16k_speech on the
-   engine with knob SAT_CHECK on, and through the same model in torch fp32 on the CPU;
-3. reports rel L2 of the (T, 1024) features, the largest |feature| of both, and the SAT_CHECK counters (values the engine's ops
-   clamped at the fp16 limit / non-finite values).
-Exit code 0 only if rel L2 <= 2e-2 and both counters are 0.  The fp16 rounding model of tests/hubert_ref.py sits at 1.5e-3 on seeded
+   engine as ONE call under the fp16 headroom watch (Engine.health_watch("hubert", 1): all its clips count into the model's
+   table), and through the same model in torch fp32 on the CPU;
+3. reports rel L2 of the (T, 1024) features, the largest |feature| of both, and the watch's line (livetalking_amd/health.py): the op
+   with the least headroom, or every op with values clamped at the fp16 limit / non-finite values.
+Exit code 0 only if rel L2 <= 2e-2 and both totals over the ops (at the limit, non-finite) are 0.  The fp16 rounding model of tests/hubert_ref.py sits at 1.5e-3 on seeded
 24-layer weights; 2e-2 leaves an order of magnitude over that for weights nobody has run here.  It is a first-run gate, not a parity
 bound: report the figure it prints.
 """
@@ -44,6 +45,7 @@ def main():
     os.environ.setdefault("LTK_ALLOW_STANDIN", "1")
     import torch
     from transformers import HubertModel
+    from livetalking_amd import health
     from livetalking_amd.engine import Engine
     if not torch.cuda.is_available():
         sys.exit("needs a GPU")
@@ -61,16 +63,15 @@ def main():
     layers = len({k.split(".")[2] for k in sd if k.startswith("encoder.layers.")})
     print(f"[hubert] {args.model}: {len(sd)} tensors, {layers} encoder layers, {len(pcm)} samples")
 
-    Engine.set_knob("SAT_CHECK", 1)
     eng = Engine(0)
     try:
         eng.load_hubert(sd)
-        eng.saturation(reset=True)
+        eng.health_watch("hubert", 1)
         got = eng.hubert_features(pcm)
-        at_limit, non_finite = eng.saturation()
+        ops, seen, _ = eng.health_report("hubert")
     finally:
         eng.close()
-        Engine.set_knob("SAT_CHECK", 0)
+    at_limit, non_finite = sum(o["at_limit"] for o in ops), sum(o["nonfinite"] for o in ops)
 
     x = pcm.astype(np.float64)
     x = ((x - x.mean()) / np.sqrt(x.var() + 1e-7)).astype(np.float32)
@@ -79,7 +80,7 @@ def main():
     ref = ref[: got.shape[0]]
     rel = float(np.linalg.norm(got[: ref.shape[0]].astype(np.float64) - ref) / np.linalg.norm(ref))
     print(f"[hubert] {got.shape[0]} rows: rel L2 engine vs torch fp32 {rel:.3e}; max |feature| engine {np.abs(got).max():.2f}, torch {np.abs(ref).max():.2f}")
-    print(f"[hubert] SAT_CHECK: {at_limit} values at the fp16 limit, {non_finite} non-finite")
+    print("[hubert] " + health.format_line("hubert", ops, seen)[1])
     ok = rel <= 2e-2 and at_limit == 0 and non_finite == 0
     print("[hubert] OK" if ok else "[hubert] FAILED: keep LTK_HUBERT_ENGINE unset")
     sys.exit(0 if ok else 1)

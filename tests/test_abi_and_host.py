@@ -510,6 +510,37 @@ def test_abi_argument_validation_without_gpu():
             Engine(0)
 
 
+def test_a_retired_knob_is_refused_by_name():
+    """SAT_CHECK went with its scan (the headroom watch, ltk_health_watch, answers its question): setting it must fail loudly, with
+    the unknown-knob text and no alias, while a knob of the list is still taken."""
+    from livetalking_amd._lib import LtkError
+    from livetalking_amd.engine import Engine
+    for name in ("SAT_CHECK", "LTK_SAT_CHECK"):
+        with pytest.raises(LtkError) as ei:
+            Engine.set_knob(name, 1)
+        assert ei.value.code == -1 and f"unknown knob {name}" in str(ei.value), str(ei.value)
+    Engine.set_knob("HEAD_FUSED", 1)             # its default
+
+
+def test_a_stale_sat_check_environment_is_named_once_per_process():
+    """A deployment that still exports LTK_SAT_CHECK gets one stderr line at engine creation that names the replacement (the
+    environment is read once per process, so the process is a child); without the variable nothing is printed."""
+    import subprocess
+    import sys
+    code = ("import ctypes as C\nfrom livetalking_amd import _lib\nlib = _lib.load()\nh = C.c_void_p()\n"
+            "assert lib.ltk_engine_create(-1, C.byref(h)) < 0 and lib.ltk_engine_create(-1, C.byref(h)) < 0\n")      # no device -1: no engine, no GPU work
+    for value, lines in (("1", 1), (None, 0)):
+        env = {k: v for k, v in os.environ.items() if k != "LTK_SAT_CHECK"}
+        if value is not None:
+            env["LTK_SAT_CHECK"] = value
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        said = [l for l in r.stderr.splitlines() if "LTK_SAT_CHECK" in l]
+        assert len(said) == lines, r.stderr
+        if lines:
+            assert "removed" in said[0] and "LTK_HEALTH_WATCH" in said[0] and "scripts/checkpoint_health.py" in said[0]
+
+
 def test_tile_table_entries_name_existing_layers_and_legal_tiles():
     """csrc/w2l_program.hip kTileTable is keyed by layer-name strings and was tuned on single boxes: every entry must name a layer
     of the network description, a frame-count bucket and a tile / split conv3 has an instantiation for (device-free check

@@ -3,7 +3,8 @@
 1. the scan kernel alone against the numpy model of tests/health_cases.py: integers equal, max_abs bit-equal;
 2. Wav2Lip: one layer's BatchNorm affine scaled past the fp16 range (asserted on the oracle first), two watched calls of five: the
    planted layer is named, the layers before it are clean, max_abs is the tap's, the frames are byte-identical to an unwatched
-   engine's, and the graph / prefetch counters behind the window move as a fresh session's do;
+   engine's, and the graph / prefetch counters behind the window move as a fresh session's do; output_block.0 is observed with the
+   head unfused (HEAD_FUSED = 0) and only then;
 3. MuseTalk (B = 1), fp16 and fp8; 4. Ultralight with UL_FUSE_IR off and on, two avatars; 5. Whisper and HuBERT, single and batched;
 6. refusals and lifetime.
 """
@@ -153,6 +154,39 @@ def test_wav2lip_watch_names_the_planted_layer_and_leaves_the_frames_alone():
     for k in range(CALLS - WATCHED):
         assert ctr_w[WATCHED + k] == ctr_u[k], (k, ctr_w[WATCHED + k], ctr_u[k])
     assert ctr_u[CALLS - WATCHED - 1][0] >= 1 and dict(ctr_u[CALLS - WATCHED - 1][1])["hits"] >= 1      # ... and that is a session that captures and hits
+
+
+def test_wav2lip_watch_sees_output_block_0_only_with_the_head_unfused():
+    """The one layer whose coverage depends on a knob: under HEAD_FUSED = 0 the 32-channel map of output_block.0 is in memory and
+    scanned (B x 32 x 256 x 256 values); in the fused head it never is, and the report says so.  Every other layer is observed on
+    both routes.  tests/test_parity_stress_gpu.py relies on the first to scan every layer."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from livetalking_amd.engine import Engine
+    frames, faces, coords, mel = _w2l_inputs(1, 1)
+    e = Engine(0)
+    try:
+        e.load_wav2lip(synth.wav2lip_state_dict(1234), max_frames=2)
+        aid = e.register_avatar(faces, frames, coords)
+        d_mel = torch.from_numpy(mel[0]).cuda()
+        d_pred = torch.zeros(1, 256, 256, 3, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        for fused in (0, 1):
+            e.health_watch("wav2lip", 1)
+            Engine.set_knob("HEAD_FUSED", fused)
+            try:
+                e.wav2lip_infer([(aid, 0, 1, d_mel.data_ptr(), d_pred.data_ptr())])
+            finally:
+                Engine.set_knob("HEAD_FUSED", 1)
+            ops, seen, left = e.health_report("wav2lip")
+            assert (seen, left) == (1, 0) and ops[-1]["name"] == "output_block.0"
+            assert all(o["observed"] == 1 and o["elements"] > 0 for o in ops[:-1]), [o["name"] for o in ops[:-1] if o["observed"] != 1]
+            if fused:
+                assert ops[-1]["observed"] == 0 and ops[-1]["elements"] == 0
+            else:
+                assert ops[-1]["observed"] == 1 and ops[-1]["elements"] == 32 * 65536
+    finally:
+        e.close()
 
 
 # ------------------------------------------------------------------ 6. refusals and lifetime

@@ -7,9 +7,12 @@ whose activations nobody here has seen.  These tests walk a family of draws - th
 multipliers that push the fp32 peak activation through 1e3 and 1e4 to past the fp16 limit (synth_inputs.wav2lip_state_dict(gain=),
 musetalk_unet_state_dict(gn_gain=), vae_decoder_state_dict(gn_gain=)) - and at every point:
 
-  * run the device with knob SAT_CHECK on and read the saturation counters (ltk_debug_saturation: values an epilogue clamped to
-    the fp16 / e4m3 limit, non-finite values);
-  * where both counters are 0, hold the product frames (knob off) to the stated tolerance against the fp32 oracle:
+  * run one call under the headroom watch (Engine.health_watch / health_report, include/ltk.h: ltk_health_watch) and read the
+    saturation counters off its report: at_limit (values an epilogue clamped to the fp16 / e4m3 limit) and nonfinite, each summed
+    over the program's layers / ops.  The Wav2Lip call runs with the head unfused (knob HEAD_FUSED = 0), so that the 32-channel map
+    of output_block.0 is in memory and scanned like every other layer; the MuseTalk call is a musetalk_infer call on an avatar
+    whose latent bank is the point's latents (the debug hook musetalk_forward_host is not a call of the watch);
+  * where both counters are 0, hold the product frames (an unwatched call, fused head) to the stated tolerance against the fp32 oracle:
     PSNR >= 40 dB and max-abs <= 6 LSB (fp16 paths); fp8 conv path: worst frame >= 36.5 dB - what the three draws support
     (measured 37.0 / 37.7 dB here on seeds 23 / 11 and 39.2 dB on the draw tests/test_fp8_gpu.py gates at 38 dB pooled / 37 dB
     worst frame: round 6 found that gate to be a property of that one draw and narrowed the claim, DESIGN.md section 4);
@@ -24,6 +27,11 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import synth_inputs as synth  # noqa: E402
+
+
+def _totals(ops):
+    """(at_limit, nonfinite) over the ops of a health report."""
+    return sum(o["at_limit"] for o in ops), sum(o["nonfinite"] for o in ops)
 
 
 def _psnr_lsb(got, ref):
@@ -69,13 +77,15 @@ def test_wav2lip_frames_vs_oracle_over_seeds_and_gains():
             aid = eng.register_avatar(faces, frames, coords)
             d_mel = torch.from_numpy(ref_mel.astype(np.float32)).cuda()
             d_pred = torch.zeros(B, 256, 256, 3, dtype=torch.uint8, device="cuda")
-            Engine.set_knob("SAT_CHECK", 1)
+            eng.health_watch("wav2lip", 1)
+            Engine.set_knob("HEAD_FUSED", 0)                # output_block.0's map reaches memory: every layer is scanned
             try:
-                eng.saturation(reset=True)
                 eng.wav2lip_infer([(aid, 1, B, d_mel.data_ptr(), d_pred.data_ptr())])
-                at_limit, nonfinite = eng.saturation(reset=True)
             finally:
-                Engine.set_knob("SAT_CHECK", 0)
+                Engine.set_knob("HEAD_FUSED", 1)
+            ops, seen, _ = eng.health_report("wav2lip")
+            assert seen == 1 and all(o["observed"] == 1 for o in ops), (seen, [o["name"] for o in ops if o["observed"] != 1])
+            at_limit, nonfinite = _totals(ops)
             d_pred.zero_()
             eng.wav2lip_infer([(aid, 1, B, d_mel.data_ptr(), d_pred.data_ptr())])      # the product path (fused head)
             psnr, lsb = _psnr_lsb(d_pred.cpu().numpy(), ref)
@@ -111,11 +121,16 @@ def test_musetalk_frames_vs_oracle_over_seeds_gains_and_batch_sizes():
         pytest.skip("no GPU")
     from livetalking_amd.engine import Engine
     from oracle import musetalk_oracle as M
+    # the bank entries beside the latents (full frame, face box, blend mask, crop box): the scanned call renders into d_pred only
+    frame = synth.wav2lip_avatar(n_frames=1, full_hw=(360, 640), box=160, seed=2)[0][0]
+    box, crop = (240, 100, 390, 270), (210, 60, 420, 305)
+    mask = np.full((crop[3] - crop[1], crop[2] - crop[0], 3), 255, np.uint8)
     rows = []
     for (useed, vseed), gain, Bf, fp8, expect in MT_POINTS:
         unet_sd = synth.musetalk_unet_state_dict(useed, gn_gain=float(gain))
         vae_sd = synth.vae_decoder_state_dict(vseed, gn_gain=float(gain))
-        lat = np.concatenate(synth.musetalk_latents(Bf, seed=5 + useed % 7))
+        lats = synth.musetalk_latents(Bf, seed=5 + useed % 7)
+        lat = np.concatenate(lats)
         feat = synth.musetalk_whisper_feats(Bf, seed=11 + useed % 5)
         usd = {k: torch.from_numpy(v) for k, v in unet_sd.items()}
         vsd = {k: torch.from_numpy(v) for k, v in vae_sd.items()}
@@ -128,13 +143,16 @@ def test_musetalk_frames_vs_oracle_over_seeds_gains_and_batch_sizes():
         eng = Engine(0)
         try:
             eng.load_musetalk(unet_sd, vae_sd, max_frames=Bf, fp8=fp8)
-            Engine.set_knob("SAT_CHECK", 1)
-            try:
-                eng.saturation(reset=True)
-                eng.musetalk_forward_host(lat, feat)
-                at_limit, nonfinite = eng.saturation(reset=True)
-            finally:
-                Engine.set_knob("SAT_CHECK", 0)
+            aid = eng.register_musetalk_avatar(lats, [frame] * Bf, [box] * Bf, [mask] * Bf, [crop] * Bf)
+            d_feat = torch.from_numpy(feat).cuda()
+            d_pred = torch.zeros(Bf, 256, 256, 3, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            eng.health_watch("musetalk", 1)
+            eng.musetalk_infer([(aid, 0, Bf, d_feat.data_ptr(), d_pred.data_ptr())])
+            ops, seen, _ = eng.health_report("musetalk")
+            # every op with an output tensor is scanned in a watched call, whatever its values: the observed set does not depend on the draw
+            assert seen == 1 and sum(o["observed"] for o in ops) > 0 and all(o["elements"] > 0 for o in ops if o["observed"]), seen
+            at_limit, nonfinite = _totals(ops)
             _, _, got = eng.musetalk_forward_host(lat, feat)
             psnr, lsb = _psnr_lsb(got, ref)
         finally:
