@@ -742,6 +742,42 @@ int ltk_ul_ir_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int Cin, 
                   const float* scale2, const float* shift2, const void* d_res, void* d_y, const ltk_conv_opts* opts, void* d_e1, void* d_e2,
                   ltk_ul_ir_report* rep);
 
+/* Standalone ops of the BiSeNet face parser (avatars/musetalk/utils/face_parsing/model.py, resnet.py; csrc/parse_kernels.h), used by
+ * kernel unit tests.  Tensors are device fp16 [N][C/16][H][W][16]; `opts` (may be NULL) carries channel views only - x_ld / x_coff,
+ * y_ld / y_coff, res_ld / res_coff in channels, multiples of 16, 0 = the op's own channel count - as for ltk_ul_gconv_f16.
+ * LTK_E_INVALID for what an op does not take (named in ltk_last_error), nothing launched.
+ *   ltk_parse_stem_f16     : cp.resnet.conv1 + bn1 + ReLU on the image itself: rgb device uint8 [N][H][W][3], H and W even; each tap is
+ *                            f16((v / 255 - mean_c) / std_c) with mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225) inside the image
+ *                            and 0 outside it (the padding of the NORMALISED tensor); weight host fp32 [64][3][7][7] (rounded to fp16),
+ *                            scale / shift host fp32 [64] (NULL = 1 / 0); y = relu(conv * scale + shift), 64 channels on H/2 x W/2.
+ *   ltk_maxpool3x3s2_f16   : nn.MaxPool2d(3, 2, 1), padding -inf; y on ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1).  Exact.
+ *   ltk_global_avgpool_f16 : mean over the P <= 4096 pixels of each channel, y [N][C/16][1][16]; fp32 sums in one fixed tree, so a
+ *                            channel's bytes depend on its own P values only.
+ *   ltk_chan_gate_f16      : y = x * (sigmoid(a) [+ 1 if plus1]) [+ b] [+ r]; a and b (may be NULL) dense device fp16 [N][C/16][1][16],
+ *                            r (may be NULL) a map like x (view: res_ld / res_coff); fp32, one rounding.
+ *   ltk_seg_argmax_f16     : x [N][2][h][w][16] logits, classes 0..18; labels device uint8 [N][8h][8w] = argmax over the 19 classes of
+ *                            the bilinear x8 upsample (align_corners=True), fp32 interpolation, the lowest class wins a tie. */
+int ltk_parse_stem_f16(ltk_engine* e, const void* d_rgb, int N, int H, int W, const float* weight, const float* scale, const float* shift,
+                       void* d_y, const ltk_conv_opts* opts);
+int ltk_maxpool3x3s2_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, void* d_y, const ltk_conv_opts* opts);
+int ltk_global_avgpool_f16(ltk_engine* e, const void* d_x, int N, int P, int C, void* d_y, const ltk_conv_opts* opts);
+int ltk_chan_gate_f16(ltk_engine* e, const void* d_x, int N, int P, int C, const void* d_a, const void* d_b, const void* d_r, int plus1,
+                      void* d_y, const ltk_conv_opts* opts);
+int ltk_seg_argmax_f16(ltk_engine* e, const void* d_x, int N, int h, int w, void* d_labels);
+
+/* The launch list of the face parser's main output (BiSeNet.forward()[0] + argmax) at one square image size, on the host alone (no
+ * engine, no GPU; no program runs it yet): per launch its name - the module's, a conv's output standing behind its BatchNorm, ReLU and
+ * residual add -, type (0 the library's conv, 10 stem, 11 max pool, 12 global average pool, 13 channel gate, 14 labels), real channels
+ * in and out, k / stride / pad, relu, ups (the conv reads its input through a nearest x2 upsample; H x W is then the upsampled map),
+ * has_res (a residual, or the gate's added map), plus1 (the gate's feat * atten + feat form), the map read H x W (the stem: the image)
+ * and written Ho x Wo (labels: the image).  41 launches.  LTK_E_INVALID: size not a multiple of 32 in [64, 512], or max_ops too small. */
+typedef struct ltk_fp_op_info {
+    char name[64];
+    int type, cin, cout, k, stride, pad, relu, ups, has_res, plus1;
+    int H, W, Ho, Wo;
+} ltk_fp_op_info;
+int ltk_debug_face_parse_program(int size, ltk_fp_op_info* ops, int max_ops, int* n_ops);
+
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */
 int ltk_debug_conv3_variants(char* buf, int cap);

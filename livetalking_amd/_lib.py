@@ -82,6 +82,11 @@ class UlOpInfo(C.Structure):
         "C", "Creal", "cin", "k", "stride", "pad", "relu")]
 
 
+class FpOpInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, C.c_int) for n in ("type", "cin", "cout", "k", "stride", "pad", "relu", "ups", "has_res", "plus1",
+                                                                     "H", "W", "Ho", "Wo")]
+
+
 class NormOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
 
@@ -151,6 +156,14 @@ SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_upsample2x_cat_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_int, C.c_void_p]),
+    "ltk_parse_stem_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(ConvOpts)]),
+    "ltk_maxpool3x3s2_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_global_avgpool_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_chan_gate_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.POINTER(ConvOpts)]),
+    "ltk_seg_argmax_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ltk_debug_face_parse_program": (C.c_int, [C.c_int, C.POINTER(FpOpInfo), C.c_int, C.POINTER(C.c_int)]),
     "ltk_egress_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ltk_egress_close": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ltk_egress_watermark": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -1,5 +1,7 @@
 // ------------------------------------------------------------------ test / measurement hooks of both models
 #include "debug_util.h"
+#include "faceparse.h"
+#include "parse_kernels.h"
 #include "ul_gconv.h"
 #include "ul_ir.h"
 
@@ -913,6 +915,114 @@ int ltk_upsample2x_cat_f16(ltk_engine* e, const void* d_x, int N, int h, int w, 
         le = hipMemcpy2DAsync((char*)d_y + (size_t)C_up * Hs * Ws * sizeof(f16), pitch, d_skip, row, row, (size_t)N, hipMemcpyDeviceToDevice, s);
     const hipError_t se = hipStreamSynchronize(s);
     if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string("upsample + concat: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
+namespace {
+
+// the channel views of a face-parser hook: channels -> channel blocks, LTK_OK or the refusal
+struct ParseViews { int x_cbt, x_cb0, y_cbt, y_cb0, r_cbt, r_cb0; };
+int parse_views(const ltk_conv_opts* o, int Cx, int Cy, ParseViews* v) {
+    if (o && (o->act || o->ups || o->force_pxw || o->force_nbt || o->force_ksplit || o->family))
+        return fail(LTK_E_INVALID, "face parser op: only the channel views of the options apply");
+    if (Cx <= 0 || Cx % 16) return fail(LTK_E_INVALID, "face parser op: C % 16 == 0");
+    const int x_ld = o && o->x_ld ? o->x_ld : Cx, y_ld = o && o->y_ld ? o->y_ld : Cy, r_ld = o && o->res_ld ? o->res_ld : Cy;
+    const int x_coff = o ? o->x_coff : 0, y_coff = o ? o->y_coff : 0, r_coff = o ? o->res_coff : 0;
+    if ((x_ld | x_coff | y_ld | y_coff | r_ld | r_coff) & 15) return fail(LTK_E_INVALID, "face parser op: channel views are multiples of 16 channels");
+    *v = ParseViews{x_ld / 16, x_coff / 16, y_ld / 16, y_coff / 16, r_ld / 16, r_coff / 16};
+    return LTK_OK;
+}
+
+// what every one of these hooks does behind its launch: the launcher's refusal, the launch error, the stream's
+int parse_finish(ltk_engine* e, int lrc, const std::string& err, const char* what) {
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(e->compute);          // before the operands go
+    if (lrc) return conv_status(lrc, err);
+    if (le != hipSuccess || se != hipSuccess) return fail(LTK_E_HIP, std::string(what) + ": " + hipGetErrorString(le != hipSuccess ? le : se));
+    return LTK_OK;
+}
+
+}  // namespace
+
+int ltk_parse_stem_f16(ltk_engine* e, const void* d_rgb, int N, int H, int W, const float* weight, const float* scale, const float* shift,
+                       void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_rgb || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, 16, kStemCout, &v); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::vector<f16> wq(kStemWHalfs);
+    parse_stem_pack(weight, wq.data());
+    std::vector<float> ss(2 * kStemCout);
+    for (int c = 0; c < kStemCout; ++c) { ss[c] = scale ? scale[c] : 1.f; ss[kStemCout + c] = shift ? shift[c] : 0.f; }
+    DevBuf d_w, d_ss;
+    int rc = upload(wq.data(), wq.size() * sizeof(f16), &d_w);
+    if (!rc) rc = upload(ss.data(), ss.size() * sizeof(float), &d_ss);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_parse_stem((const uint8_t*)d_rgb, N, H, W, (const f16*)d_w.p, (const float*)d_ss.p, (const float*)d_ss.p + kStemCout,
+                                      (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "parse stem kernel");
+}
+
+int ltk_maxpool3x3s2_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, C, C, &v); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_maxpool3x3s2((const f16*)d_x, N, v.x_cbt, v.x_cb0, C, H, W, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "maxpool kernel");
+}
+
+int ltk_global_avgpool_f16(ltk_engine* e, const void* d_x, int N, int P, int C, void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, C, C, &v); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_gap((const f16*)d_x, N, v.x_cbt, v.x_cb0, C, P, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "global average pool kernel");
+}
+
+int ltk_chan_gate_f16(ltk_engine* e, const void* d_x, int N, int P, int C, const void* d_a, const void* d_b, const void* d_r, int plus1,
+                      void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !d_a || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, C, C, &v); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_chan_gate((const f16*)d_x, N, v.x_cbt, v.x_cb0, C, P, (const f16*)d_a, (const f16*)d_b, (const f16*)d_r, v.r_cbt, v.r_cb0,
+                                     plus1, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "channel gate kernel");
+}
+
+int ltk_seg_argmax_f16(ltk_engine* e, const void* d_x, int N, int h, int w, void* d_labels) {
+    if (!e || !d_x || !d_labels) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_seg_argmax((const f16*)d_x, N, h, w, (uint8_t*)d_labels, e->compute, &err);
+    return parse_finish(e, lrc, err, "seg argmax kernel");
+}
+
+int ltk_debug_face_parse_program(int size, ltk_fp_op_info* ops, int max_ops, int* n_ops) {
+    if (!ops || !n_ops || max_ops <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::vector<FpOp> prog = fp_program(size);
+    if (prog.empty()) return fail(LTK_E_INVALID, "face parser: size must be a multiple of 32 in [64, 512]");
+    if ((int)prog.size() > max_ops) return fail(LTK_E_INVALID, "face parser: the program has " + std::to_string(prog.size()) + " ops");
+    for (size_t i = 0; i < prog.size(); ++i) {
+        const FpOp& p = prog[i];
+        ltk_fp_op_info& o = ops[i];
+        memset(&o, 0, sizeof(o));
+        snprintf(o.name, sizeof(o.name), "%s", p.name.c_str());
+        o.type = p.type; o.cin = p.cin; o.cout = p.cout; o.k = p.k; o.stride = p.stride; o.pad = p.pad; o.relu = p.relu; o.ups = p.ups;
+        o.has_res = p.has_res; o.plus1 = p.plus1; o.H = p.H; o.W = p.W; o.Ho = p.Ho; o.Wo = p.Wo;
+    }
+    *n_ops = (int)prog.size();
     return LTK_OK;
 }
 

@@ -447,6 +447,50 @@ class Engine:
         _lib.check(self._lib.ltk_upsample2x_cat_f16(self._h, C.c_void_p(d_x_ptr), N, h, w, C_up, C.c_void_p(d_skip_ptr), Hs, Ws, C_skip,
                                                     C.c_void_p(d_y_ptr)))
 
+    # ---- the face parser's own ops (include/ltk.h: "Standalone ops of the BiSeNet face parser"); views = {x_ld, x_coff, y_ld, y_coff,
+    # res_ld, res_coff} in channels
+    def parse_stem_f16(self, d_rgb_ptr: int, N, H, W, weight: np.ndarray, scale=None, shift=None, d_y_ptr: int = 0,
+                       views: Optional[dict] = None):
+        """7x7 stride-2 stem + BatchNorm + ReLU on device uint8 RGB [N][H][W][3], normalisation fused; weight (64,3,7,7)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        assert w.shape == (64, 3, 7, 7)
+        sc = np.ascontiguousarray(scale, dtype=np.float32) if scale is not None else None
+        sf = np.ascontiguousarray(shift, dtype=np.float32) if shift is not None else None
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_parse_stem_f16(self._h, C.c_void_p(d_rgb_ptr), int(N), int(H), int(W), w.ctypes.data,
+                                                sc.ctypes.data if sc is not None else None, sf.ctypes.data if sf is not None else None,
+                                                C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def maxpool3x3s2_f16(self, d_x_ptr: int, N, H, W, C_, d_y_ptr: int, views: Optional[dict] = None):
+        """nn.MaxPool2d(3, 2, 1) on a CB16 tensor (padding -inf)."""
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_maxpool3x3s2_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(H), int(W), int(C_), C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def global_avgpool_f16(self, d_x_ptr: int, N, P, C_, d_y_ptr: int, views: Optional[dict] = None):
+        """Mean over the P pixels of each channel of a CB16 tensor -> [N][C/16][1][16]."""
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_global_avgpool_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(P), int(C_), C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def chan_gate_f16(self, d_x_ptr: int, N, P, C_, d_a_ptr: int, d_y_ptr: int, d_b_ptr: int = 0, d_r_ptr: int = 0, plus1: bool = False,
+                      views: Optional[dict] = None):
+        """y = x * (sigmoid(a) [+ 1]) [+ b] [+ r] on CB16 tensors; a, b are [N][C/16][1][16]."""
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_chan_gate_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(P), int(C_), C.c_void_p(d_a_ptr),
+                                               C.c_void_p(d_b_ptr) if d_b_ptr else None, C.c_void_p(d_r_ptr) if d_r_ptr else None,
+                                               1 if plus1 else 0, C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def seg_argmax_f16(self, d_x_ptr: int, N, h, w, d_labels_ptr: int):
+        """uint8 labels [N][8h][8w]: argmax over classes 0..18 of the bilinear x8 (align_corners) upsample of [N][2][h][w][16] logits."""
+        _lib.check(self._lib.ltk_seg_argmax_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(h), int(w), C.c_void_p(d_labels_ptr)))
+
+    @staticmethod
+    def face_parse_program(size: int = 512):
+        """The face parser's launch list at `size`, on the host alone (include/ltk.h: ltk_debug_face_parse_program): a dict per launch."""
+        ops = (_lib.FpOpInfo * 64)()
+        n = C.c_int()
+        _lib.check(_lib.load().ltk_debug_face_parse_program(int(size), ops, 64, C.byref(n)))
+        return [dict(name=o.name.decode(), **{f: getattr(o, f) for f, _ in _lib.FpOpInfo._fields_[1:]}) for o in ops[:n.value]]
+
     # ---- frame egress (include/ltk.h: ltk_egress_*)
     def egress_open(self, H: int, W: int) -> int:
         h = C.c_void_p()

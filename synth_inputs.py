@@ -568,3 +568,72 @@ def ultralight_inputs(batch: int, seed: int = 1234):
         masked[5:150, 5:155] = 0                    # cv2.rectangle(img, (5, 5, 150, 145), 0, -1): x 5..154, y 5..149
         imgs.append(np.concatenate([real.transpose(2, 0, 1), masked.transpose(2, 0, 1)]).astype(np.float32) / np.float32(255.0))
     return np.stack(imgs), ultralight_feats(batch, seed + 78).reshape(batch, 16, 32, 32)
+
+
+# ---------------------------------------------------------------------------------------------- BiSeNet face parser
+def _fp_convs():
+    """(conv key, BatchNorm key or None, cin, cout, k, a ReLU follows, last BatchNorm of a residual block) of BiSeNet's main output path
+    (avatars/musetalk/utils/face_parsing/model.py, resnet.py), in state_dict order."""
+    out = [("cp.resnet.conv1", "cp.resnet.bn1", 3, 64, 7, True, False)]
+    cin = 64
+    for l, c in enumerate((64, 128, 256, 512)):
+        for b in range(2):
+            p = f"cp.resnet.layer{l + 1}.{b}"
+            out.append((p + ".conv1", p + ".bn1", cin if b == 0 else c, c, 3, True, False))
+            out.append((p + ".conv2", p + ".bn2", c, c, 3, False, True))
+            if b == 0 and l > 0:
+                out.append((p + ".downsample.0", p + ".downsample.1", cin, c, 1, False, False))
+        cin = c
+    for p, ci in (("cp.arm16", 256), ("cp.arm32", 512)):
+        out.append((p + ".conv.conv", p + ".conv.bn", ci, 128, 3, True, False))
+        out.append((p + ".conv_atten", p + ".bn_atten", 128, 128, 1, False, False))
+    out += [("cp.conv_head32.conv", "cp.conv_head32.bn", 128, 128, 3, True, False), ("cp.conv_head16.conv", "cp.conv_head16.bn", 128, 128, 3, True, False),
+            ("cp.conv_avg.conv", "cp.conv_avg.bn", 512, 128, 1, True, False), ("ffm.convblk.conv", "ffm.convblk.bn", 256, 256, 1, True, False),
+            ("ffm.conv1", None, 256, 64, 1, True, False), ("ffm.conv2", None, 64, 256, 1, False, False),
+            ("conv_out.conv.conv", "conv_out.conv.bn", 256, 256, 3, True, False), ("conv_out.conv_out", None, 256, 19, 1, False, False)]
+    return out
+
+
+FACEPARSE_CLASS_GAIN = (1.0, 1.0, 1.0, 1.5, 1.562, 1.562, 1.0, 1.562, 0.64, 1.562, 1.103, 1.562, 1.562, 0.809, 1.278, 1.562, 1.562, 1.562, 1.562)
+
+
+def faceparse_state_dict(seed: int = 83, shapes_only: bool = False, heads: bool = True) -> Dict[str, np.ndarray]:
+    """Reference-named fp32 state_dict of face_parsing's BiSeNet(n_classes=19) as numpy arrays: He-scaled convs (std sqrt(2 / fan_in) in
+    front of a ReLU, sqrt(1 / fan_in) otherwise), BatchNorm as ultralight_state_dict draws it (gamma damped on the last BatchNorm of a
+    residual block), conv_out.conv_out with zero-sum rows and per-class gains so that the classes the mask modes use win.  `heads`: also the conv_out16 / conv_out32
+    heads, which net(img)[0] does not use."""
+    rng = np.random.default_rng(seed)
+    sd: Dict[str, np.ndarray] = {}
+
+    def bn(p, c, damp):
+        lo, hi = (0.3, 0.7) if damp else (0.7, 1.3)
+        sd[p + ".weight"] = rng.uniform(lo, hi, c).astype(np.float32)
+        sd[p + ".bias"] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[p + ".running_mean"] = (rng.standard_normal(c) * 0.2).astype(np.float32)
+        sd[p + ".running_var"] = rng.uniform(0.6, 1.6, c).astype(np.float32)
+        sd[p + ".num_batches_tracked"] = np.asarray(1000, dtype=np.int64)
+
+    for conv, norm, cin, cout, k, relu, damp in _fp_convs():
+        sd[conv + ".weight"] = (rng.standard_normal((cout, cin, k, k)) * np.sqrt((2.0 if relu else 1.0) / (cin * k * k))).astype(np.float32)
+        if norm:
+            bn(norm, cout, damp)
+    # every class's weights sum to zero: the features behind a ReLU are all positive, and their common mean times a row's sum would
+    # decide the argmax for the whole image (one class won 98 % of the pixels).  Then the per-class gains FACEPARSE_CLASS_GAIN, fitted
+    # once on seed 83 / faceparse_image(512, 0) so that no row takes the image, and rows 1 <-> 4 and 12 <-> 8 change places: classes
+    # 1, 10, 11, 12 and 13 - the ones the mask modes keep - each win 10 % or more of that image (scripts/gen_golden_faceparse.py asserts 2 %).
+    w = sd["conv_out.conv_out.weight"]
+    w = (w - w.mean(1, keepdims=True)) * np.asarray(FACEPARSE_CLASS_GAIN, np.float32).reshape(19, 1, 1, 1)
+    w[[1, 4, 12, 8]] = w[[4, 1, 8, 12]]
+    sd["conv_out.conv_out.weight"] = np.ascontiguousarray(w, dtype=np.float32)
+    if heads:
+        for p in ("conv_out16", "conv_out32"):
+            sd[p + ".conv.conv.weight"] = (rng.standard_normal((64, 128, 3, 3)) * np.sqrt(2.0 / 1152)).astype(np.float32)
+            bn(p + ".conv.bn", 64, False)
+            sd[p + ".conv_out.weight"] = (rng.standard_normal((19, 64, 1, 1)) * np.sqrt(1.0 / 64)).astype(np.float32)
+    return _finish(sd, shapes_only)
+
+
+def faceparse_image(size: int = 512, seed: int = 0) -> np.ndarray:
+    """A smooth low-pass RGB uint8 image (size, size, 3)."""
+    rng = np.random.default_rng(9000 + seed)
+    return _smooth_image(rng, size, size)
