@@ -397,6 +397,22 @@ int ltk_hubert_step_batch(ltk_engine* e, const ltk_hubert_req* reqs, int nreq);
 int ltk_vae_encoder_load(ltk_engine* e, const ltk_named_tensor* vae_sd, int n, int max_faces);
 int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, const float* noise, float* latents_out);
 
+/* Avatar preparation, blend masks: the BiSeNet face parser (avatars/musetalk/utils/face_parsing/model.py BiSeNet.forward()[0],
+ * resnet.py; face_parsing/__init__.py:72-90: ToTensor + Normalize, the net, argmax) as one replayed device program over the 41 launches
+ * of ltk_debug_face_parse_program, wired as ltk_debug_face_parse_plan lists.
+ * ltk_face_parse_load: sd = BiSeNet(n_classes=19).state_dict() (fp32 host); read are the keys of the network's main output - the
+ * conv_out16.* / conv_out32.* heads and the num_batches_tracked counters are ignored when present; a missing key is LTK_E_INVALID and
+ * the message names it.  Eval-mode BatchNorm is folded into each conv's fp32 scale / shift.  size: the square image size, a multiple
+ * of 32 in [64, 512] (the reference uses 512); max_images in [1, 8]: images per run of the program.  LTK_E_STATE on a second load.
+ * ltk_face_parse: rgb_host uint8 [n][size][size][3] (RGB, as PIL hands it over) -> labels_host uint8 [n][size][size], classes 0..18.
+ * n may exceed max_images: the images go through in chunks of max_images (the last one short), each uploaded, run and copied back with
+ * one synchronisation.  LTK_E_STATE before a load; a refused call has launched nothing.
+ * ltk_face_parse_debug_get (test hook): the output of the launch named op_name as the last run left it, `images` <= the images of that
+ * run, as float32 [images][cout][Ho][Wo], real channels only; "labels" is refused (bytes: they come from ltk_face_parse). */
+int ltk_face_parse_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int size, int max_images);
+int ltk_face_parse(ltk_engine* e, const uint8_t* rgb_host, int n, uint8_t* labels_host);
+int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats);
+
 /* =========================== fp16 headroom watch: the first calls on a real checkpoint =========================== */
 
 /* The conv epilogues clamp to the fp16 range (fmed3f(t, -65504, 65504); +-448 on the e4m3 tensors of the fp8 path) and nothing reports
@@ -414,7 +430,9 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
  * LTK_HEALTH_MUSETALK ltk_musetalk_op_name (U-Net + VAE decoder); LTK_HEALTH_WHISPER the Whisper encoder's ops (types as
  * ltk_musetalk_op_name; the 16-clip program of ltk_whisper_step_batch counts into the same table); LTK_HEALTH_HUBERT
  * ltk_hubert_op_name (every clip length's program and the batched programs count into one table); LTK_HEALTH_ULTRALIGHT one
- * avatar's ltk_ultralight_op_name as knob UL_FUSE_IR stands when the report is read.
+ * avatar's ltk_ultralight_op_name as knob UL_FUSE_IR stands when the report is read; LTK_HEALTH_FACEPARSE the 41 launches of
+ * ltk_debug_face_parse_program with its types (a watched ltk_face_parse call counts once whatever its chunks; `labels` writes bytes and
+ * stays unobserved).
  * What a watch does not see (observed = 0, counters zero): an output that never reaches memory on the route the call took - the
  * 32-channel map inside the fused Wav2Lip head (output_block.0), the hidden tensors of a fused Ultralight inverted residual (the block
  * is listed once, with its project conv's output), the byte-writing heads; an op the call did not run (the face encoder under knob
@@ -422,7 +440,9 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
  * A watched ltk_wav2lip_infer call takes the whole-pass route (the prefetched encoder's frames are byte-identical), is not deferred -
  * its counters are complete when it returns - and leaves the prefetch slots and session records alone: the calls behind the window
  * find prefetching as the first calls of a session do. */
-enum { LTK_HEALTH_WAV2LIP = 0, LTK_HEALTH_MUSETALK = 1, LTK_HEALTH_ULTRALIGHT = 2, LTK_HEALTH_WHISPER = 3, LTK_HEALTH_HUBERT = 4 };
+enum { LTK_HEALTH_WAV2LIP = 0, LTK_HEALTH_MUSETALK = 1, LTK_HEALTH_ULTRALIGHT = 2, LTK_HEALTH_WHISPER = 3, LTK_HEALTH_HUBERT = 4,
+       /* 5 stays unassigned: callers written against the five codes above treat it as the first unknown program */
+       LTK_HEALTH_FACEPARSE = 6 };
 
 typedef struct ltk_health_op {
     char name[64];
@@ -766,7 +786,7 @@ int ltk_chan_gate_f16(ltk_engine* e, const void* d_x, int N, int P, int C, const
 int ltk_seg_argmax_f16(ltk_engine* e, const void* d_x, int N, int h, int w, void* d_labels);
 
 /* The launch list of the face parser's main output (BiSeNet.forward()[0] + argmax) at one square image size, on the host alone (no
- * engine, no GPU; no program runs it yet): per launch its name - the module's, a conv's output standing behind its BatchNorm, ReLU and
+ * engine, no GPU; the program of ltk_face_parse_load runs it): per launch its name - the module's, a conv's output standing behind its BatchNorm, ReLU and
  * residual add -, type (0 the library's conv, 10 stem, 11 max pool, 12 global average pool, 13 channel gate, 14 labels), real channels
  * in and out, k / stride / pad, relu, ups (the conv reads its input through a nearest x2 upsample; H x W is then the upsampled map),
  * has_res (a residual, or the gate's added map), plus1 (the gate's feat * atten + feat form), the map read H x W (the stem: the image)
@@ -777,6 +797,29 @@ typedef struct ltk_fp_op_info {
     int H, W, Ho, Wo;
 } ltk_fp_op_info;
 int ltk_debug_face_parse_program(int size, ltk_fp_op_info* ops, int max_ops, int* n_ops);
+
+/* Where every launch of that list reads and writes at (size, max_images), on the host alone: the binding table the device program of
+ * ltk_face_parse_load is built from (csrc/faceparse.h fp_plan).  A view = channels [coff, coff + C) of buffer `buf`, which holds `ld`
+ * channels, on an H x W map; buf = -1: the op has no such operand.  x, y: input and output (a conv behind a nearest x2 upsample: x is the
+ * stored map, half the op's H x W); r: a conv's residual or the map a gate adds; a, b: a gate's pre-sigmoid attention and the per-channel
+ * value it adds, dense 1 x 1 maps.  fp16 buffers are channel-blocked (C, ld, coff multiples of 16; conv_out.conv_out writes 32 layout
+ * channels, 19 real); *image_buf is uint8 [max_images][size][size][3] (C = ld = 3), *label_buf uint8 [max_images][size][size]
+ * (C = ld = 1).  buf_bytes[i]: bytes of buffer i at max_images; *n_bufs of them.  ffm.convblk reads ONE 256-channel buffer whose halves
+ * cp.resnet.layer2.1.conv2 and cp.conv_head16 write.  LTK_E_INVALID: size as above, max_images outside [1, 8], max_ops / max_bufs too
+ * small. */
+typedef struct ltk_fp_view { int buf, ld, coff, C, H, W; } ltk_fp_view;
+typedef struct ltk_fp_bind {
+    char name[64];
+    ltk_fp_view x, y, r, a, b;
+} ltk_fp_bind;
+int ltk_debug_face_parse_plan(int size, int max_images, ltk_fp_bind* ops, int max_ops, int* n_ops, unsigned long long* buf_bytes,
+                              int max_bufs, int* n_bufs, int* image_buf, int* label_buf);
+/* Measurement hook (scripts/face_parse_time.py; not on the production call path), the twin of ltk_musetalk_time / _time_ops for the
+ * program of ltk_face_parse_load: *ms_per_pass = milliseconds of one device pass of `images` <= max_images images, replayed as
+ * ltk_face_parse replays it, without upload or copy-back, over `iters` runs; ms_per_op (or NULL; n_ops = 41): per-launch times from
+ * events between eager launches.  Whatever the last ltk_face_parse left in the program's buffers is the input.  LTK_E_STATE before a
+ * load; a run the program refuses: its code and text as ltk_face_parse reports them. */
+int ltk_debug_face_parse_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops);
 
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */

@@ -87,6 +87,14 @@ class FpOpInfo(C.Structure):
                                                                      "H", "W", "Ho", "Wo")]
 
 
+class FpView(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("buf", "ld", "coff", "C", "H", "W")]
+
+
+class FpBind(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, FpView) for n in ("x", "y", "r", "a", "b")]
+
+
 class NormOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
 
@@ -103,8 +111,9 @@ class HealthOp(C.Structure):
 
 # include/ltk.h LTK_HEALTH_*: the programs a headroom watch can be armed for
 HEALTH_WAV2LIP, HEALTH_MUSETALK, HEALTH_ULTRALIGHT, HEALTH_WHISPER, HEALTH_HUBERT = range(5)
+HEALTH_FACEPARSE = 6         # (5 stays unassigned)
 HEALTH_PROGRAMS = {"wav2lip": HEALTH_WAV2LIP, "musetalk": HEALTH_MUSETALK, "ultralight": HEALTH_ULTRALIGHT, "whisper": HEALTH_WHISPER,
-                   "hubert": HEALTH_HUBERT}
+                   "hubert": HEALTH_HUBERT, "faceparse": HEALTH_FACEPARSE}
 
 DEFER_SYNC = 2      # flag of ltk_wav2lip_infer_deferred
 
@@ -164,6 +173,12 @@ SYMBOLS = {
                                     C.POINTER(ConvOpts)]),
     "ltk_seg_argmax_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ltk_debug_face_parse_program": (C.c_int, [C.c_int, C.POINTER(FpOpInfo), C.c_int, C.POINTER(C.c_int)]),
+    "ltk_debug_face_parse_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(FpBind), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ltk_face_parse_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int, C.c_int, C.c_int]),
+    "ltk_face_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "ltk_face_parse_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ltk_debug_face_parse_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     "ltk_egress_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ltk_egress_close": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ltk_egress_watermark": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

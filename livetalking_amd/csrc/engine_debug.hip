@@ -1026,6 +1026,78 @@ int ltk_debug_face_parse_program(int size, ltk_fp_op_info* ops, int max_ops, int
     return LTK_OK;
 }
 
+int ltk_debug_face_parse_plan(int size, int max_images, ltk_fp_bind* ops, int max_ops, int* n_ops, unsigned long long* buf_bytes,
+                              int max_bufs, int* n_bufs, int* image_buf, int* label_buf) {
+    if (!ops || !n_ops || !buf_bytes || !n_bufs || !image_buf || !label_buf || max_ops <= 0 || max_bufs <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    FpPlan pl;
+    std::string err;
+    if (fp_plan(size, max_images, &pl, &err)) return fail(LTK_E_INVALID, err);
+    if ((int)pl.ops.size() > max_ops) return fail(LTK_E_INVALID, "face parser: the program has " + std::to_string(pl.ops.size()) + " ops");
+    if ((int)pl.buf_bytes.size() > max_bufs) return fail(LTK_E_INVALID, "face parser: the program has " + std::to_string(pl.buf_bytes.size()) + " buffers");
+    auto view = [](const FpView& v) { return ltk_fp_view{v.buf, v.ld, v.coff, v.C, v.H, v.W}; };
+    for (size_t i = 0; i < pl.ops.size(); ++i) {
+        ltk_fp_bind& o = ops[i];
+        memset(&o, 0, sizeof(o));
+        snprintf(o.name, sizeof(o.name), "%s", pl.ops[i].name.c_str());
+        const FpBind& b = pl.bind[i];
+        o.x = view(b.x); o.y = view(b.y); o.r = view(b.r); o.a = view(b.a); o.b = view(b.b);
+    }
+    for (size_t i = 0; i < pl.buf_bytes.size(); ++i) buf_bytes[i] = (unsigned long long)pl.buf_bytes[i];
+    *n_ops = (int)pl.ops.size(); *n_bufs = (int)pl.buf_bytes.size();
+    *image_buf = pl.image_buf; *label_buf = pl.label_buf;
+    return LTK_OK;
+}
+
+int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats) {
+    if (!e || !op_name || !out_f32 || images <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->face_parse) return fail(LTK_E_STATE, "ltk_face_parse_load has not been called");
+    if (!strcmp(op_name, "labels")) return fail(LTK_E_INVALID, "face parser: labels are bytes, not an fp16 tensor: they come from ltk_face_parse");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (images > e->face_parse_last)
+        return fail(LTK_E_INVALID, "face parser: the last run held " + std::to_string(e->face_parse_last) + " images");
+    int cout = 0;
+    for (const FpOp& p : fp_program(e->face_parse_size)) if (p.name == op_name) cout = p.cout;
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->face_parse, op_name, &C, &ld, &coff, &H, &W);
+    if (!t || !cout) return fail(LTK_E_STATE, std::string("no face parser tensor named ") + op_name);
+    const size_t cnt = (size_t)images * cout * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats for these images");
+    return read_cb16(e, t, images, cout, ld, coff, H, W, out_f32);          // the real channels of the view
+}
+
+int ltk_debug_face_parse_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops) {
+    if (!e || images <= 0 || iters <= 0 || !ms_per_pass) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->face_parse) return fail(LTK_E_STATE, "ltk_face_parse_load has not been called");
+    if (images > e->face_parse_images) return fail(LTK_E_INVALID, "images exceeds max_images");
+    if (ms_per_op && n_ops != mt_op_count(e->face_parse)) return fail(LTK_E_INVALID, "n_ops != the program's launches");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    // as ltk_face_parse enqueues the program: eagerly the first time an image count is seen, then captured, then replayed
+    auto pass = [&]() -> int {
+        const int prc = run_program(e, e->face_parse, images);
+        return prc ? conv_status(prc, std::string("face parser: ") + mt_graph_error(e->face_parse)) : 0;
+    };
+    int rc = pass();
+    if (!rc) rc = pass();
+    float ms = 0.f;
+    if (!rc) rc = time_iters(e->compute, iters, pass, &ms);
+    if (rc) return rc;
+    e->face_parse_last = images;
+    *ms_per_pass = ms / iters;
+    if (ms_per_op) {
+        auto run = [&](std::vector<hipEvent_t>* evs) -> int {
+            const int prc = mt_run_timed(e->face_parse, images, e->d_partial, e->partial_cap, e->compute, evs);
+            return prc ? conv_status(prc, std::string("face parser: ") + mt_graph_error(e->face_parse)) : 0;
+        };
+        std::vector<float> per((size_t)n_ops);
+        rc = time_intervals(n_ops, iters, run, per.data());
+        if (rc) return rc;
+        memcpy(ms_per_op, per.data(), per.size() * sizeof(float));
+    }
+    return LTK_OK;
+}
+
 int ltk_f32_to_e4m3(const float* in, size_t n, uint8_t* out) {
     if (!in || !out) return fail(LTK_E_INVALID, "bad arguments");
     for (size_t i = 0; i < n; ++i) out[i] = f32_to_e4m3(in[i]);

@@ -253,10 +253,10 @@ struct ltk_engine {
     float* d_partial_aux = nullptr;       // ... of the aux stream
     float* d_partial_pf = nullptr;        // ... of the prefetch stream (aux2, knob PREFETCH)
     size_t partial_cap = 0, partial_aux_cap = 0, partial_pf_cap = 0;
-    // headroom watches (ltk_health_watch), allocated when their program is loaded: Wav2Lip by layer; the MuseTalk, Whisper and HuBERT
-    // programs by op (the batched Whisper program and every HuBERT program share their model's table).  w2l_scan: set while a watched
+    // headroom watches (ltk_health_watch), allocated when their program is loaded: Wav2Lip by layer; the MuseTalk, Whisper, HuBERT and
+    // face-parser programs by op (the batched Whisper program and every HuBERT program share their model's table).  w2l_scan: set while a watched
     // Wav2Lip call is being enqueued, run_convs scans every layer it launches into it.
-    HealthWatch hw_w2l, hw_mt, hw_whisper, hw_hubert;
+    HealthWatch hw_w2l, hw_mt, hw_whisper, hw_hubert, hw_faceparse;
     HealthWatch* w2l_scan = nullptr;
     // Lock rule.  `mu` owns the enqueue order on compute / aux / aux2 and everything a pass works with: the loaded programs (layers,
     // mt, whisper, vae_enc, their settings), the arena and pointer tables, the prefetch slots / solo_seq / pf_* counters, both graph
@@ -340,6 +340,9 @@ struct ltk_engine {
     float mt_fp8_ascale = 8.f;
     MtGraph* vae_enc = nullptr;           // AutoencoderKL encoder graph (avatar preparation), 2 images per face
     int vae_enc_faces = 0;
+    MtGraph* face_parse = nullptr;        // BiSeNet face parser (avatar preparation: blend masks), face_parse_size^2 images, face_parse_images per run
+    int face_parse_size = 0, face_parse_images = 0;
+    int face_parse_last = 0;              // images of the run that ran last (debug read-back)
     MtGraph* whisper = nullptr;           // Whisper-tiny encoder graph (Audio2Feature)
     float* d_wbasis = nullptr;            // slaney mel basis [80][201] (n_fft 400, 0..8000 Hz)
     float* d_wlogspec = nullptr;          // [80][3000]

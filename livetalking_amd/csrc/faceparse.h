@@ -1,7 +1,8 @@
 // The launch list of the BiSeNet face parser's main output (avatars/musetalk/utils/face_parsing/model.py BiSeNet.forward()[0], resnet.py)
 // at one square image size, as a table built on the host alone: what a program over parse_kernels.h and the conv library launches, in
-// order.  No program consumes it yet; ltk_debug_face_parse_program lists it and the CPU suite holds it to the
-// float64 restatement's op walk and every conv of it to the conv planner.
+// order - and fp_plan, where each of them reads and writes.  mt_build_face_parse_graph (musetalk.hip) builds the device program of
+// ltk_face_parse_load from the two; ltk_debug_face_parse_program / _plan list them and the CPU suite holds the list to the float64
+// restatement's op walk, every conv of it to the conv planner, and the bindings to a replay of the restatement through them.
 #pragma once
 #include <string>
 #include <vector>
@@ -20,5 +21,29 @@ struct FpOp {
 
 // size: a multiple of 32 in [64, 512]; an empty vector otherwise
 std::vector<FpOp> fp_program(int size);
+
+// Where every launch of the list reads and writes: the ONE statement of the network's wiring (tests/faceparse_ref.py walk).  The device
+// builder (mt_build_face_parse_graph) allocates these buffers under these ids and binds its ops to these views;
+// ltk_debug_face_parse_plan lists them and the CPU suite replays the float64 restatement through them.
+// A view = channels [coff, coff + C) of buffer `buf`, which holds `ld` channels, on an H x W map; buf = -1: the op has no such operand.
+// fp16 tensors are channel-blocked (C, ld, coff multiples of 16: conv_out.conv_out writes 32 layout channels, 19 real); the image
+// buffer (uint8 [n][S][S][3]: C = ld = 3) and the label buffer (uint8 [n][S][S]: C = ld = 1) are byte tensors.
+struct FpView { int buf = -1, ld = 0, coff = 0, C = 0, H = 1, W = 1; };
+struct FpBind {
+    FpView x, y;
+    FpView r;        // a conv's residual / the map a gate adds (cp.feat16_sum)
+    FpView a, b;     // a gate's pre-sigmoid attention and the per-channel value it adds (cp.feat32_sum), both dense 1 x 1
+};
+struct FpPlan {
+    std::vector<FpOp> ops;
+    std::vector<FpBind> bind;                  // one per op
+    std::vector<size_t> buf_elems;             // elements of ONE image per buffer (halfs, or bytes for the two byte buffers)
+    std::vector<size_t> buf_bytes;             // bytes at max_images
+    int image_buf = -1, label_buf = -1;
+    int size = 0, max_images = 0;
+};
+constexpr int kFpMaxImages = 8;
+// size as fp_program, max_images in [1, kFpMaxImages]: 0, or -1 with the refusal in *err.  Pure.
+int fp_plan(int size, int max_images, FpPlan* out, std::string* err);
 
 }  // namespace ltk

@@ -23,6 +23,8 @@ void fill_op(ltk_health_op* o, const char* name, int type, int observed, int q8,
     o->limit = q8 ? 448.f : 65504.f;
 }
 
+bool known_program(int program) { return (program >= LTK_HEALTH_WAV2LIP && program <= LTK_HEALTH_HUBERT) || program == LTK_HEALTH_FACEPARSE; }
+
 // one row of a program's listing: the op's name and type, whether it writes e4m3, and its record in the table
 struct Row { std::string name; int type, q8, rec; };
 
@@ -56,6 +58,10 @@ HealthWatch* find_watch(ltk_engine* e, int program, int avatar_id, std::shared_p
             if (!e->hubert_w) { *rc = fail(LTK_E_STATE, "ltk_hubert_load has not been called"); return nullptr; }
             mt_rows(e->hubert_w);
             return &e->hw_hubert;
+        case LTK_HEALTH_FACEPARSE:
+            if (!e->face_parse) { *rc = fail(LTK_E_STATE, "ltk_face_parse_load has not been called"); return nullptr; }
+            mt_rows(e->face_parse);
+            return &e->hw_faceparse;
         case LTK_HEALTH_ULTRALIGHT: {
             *hold = find_ul_avatar(e, avatar_id);
             if (!*hold || !(*hold)->health) { *rc = fail(LTK_E_STATE, "unknown Ultralight avatar id"); return nullptr; }
@@ -78,7 +84,7 @@ extern "C" {
 
 int ltk_health_watch(ltk_engine* e, int program, int avatar_id, int calls) {
     if (!e) return fail(LTK_E_INVALID, "engine is null");
-    if (program < LTK_HEALTH_WAV2LIP || program > LTK_HEALTH_HUBERT) return fail(LTK_E_INVALID, "unknown program");
+    if (!known_program(program)) return fail(LTK_E_INVALID, "unknown program");
     if (calls < 0) return fail(LTK_E_INVALID, "calls must not be negative");
     CHK(enter_device(e->device));
     // armed under the enqueue lock: a call sees the watch whole or not at all
@@ -100,7 +106,7 @@ int ltk_health_watch(ltk_engine* e, int program, int avatar_id, int calls) {
 
 int ltk_health_report(ltk_engine* e, int program, int avatar_id, ltk_health_op* ops, int cap, int* n_ops, int* calls_seen, int* calls_left) {
     if (!e || !ops || !n_ops || cap <= 0) return fail(LTK_E_INVALID, "bad arguments");
-    if (program < LTK_HEALTH_WAV2LIP || program > LTK_HEALTH_HUBERT) return fail(LTK_E_INVALID, "unknown program");
+    if (!known_program(program)) return fail(LTK_E_INVALID, "unknown program");
     CHK(enter_device(e->device));
     std::lock_guard<std::mutex> g(e->mu);
     std::shared_ptr<UlAvatar> hold;

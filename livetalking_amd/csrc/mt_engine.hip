@@ -1,5 +1,6 @@
 // MuseTalk (U-Net + VAE decoder), Whisper and HuBERT audio features and the VAE encoder: their entry points and run_program.
 #include "engine_internal.h"
+#include "faceparse.h"
 
 extern "C" {
 
@@ -672,6 +673,63 @@ int ltk_vae_encode_faces(ltk_engine* e, const uint8_t* faces_bgr, int nfaces, co
     (void)hipFree(d_faces); (void)hipFree(d_out);
     if (d_noise) (void)hipFree(d_noise);
     return rc;
+}
+
+// ================================================================================ face parser (avatar preparation: blend masks)
+int ltk_face_parse_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int size, int max_images) {
+    if (!e || !sd || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (size < 64 || size > 512 || size % 32) return fail(LTK_E_INVALID, "face parser: size must be a multiple of 32 in [64, 512]");
+    if (max_images < 1 || max_images > kFpMaxImages) return fail(LTK_E_INVALID, "face parser: max_images must be in [1, 8]");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->face_parse) return fail(LTK_E_STATE, "a face parser is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* fg = mt_graph_new();
+    const int rc = mt_build_face_parse_graph(fg, sd, n, size, max_images);
+    if (rc) {
+        const std::string msg = mt_graph_error(fg);
+        mt_graph_delete(fg);
+        (void)hipGetLastError();
+        return fail(rc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, "face parser: " + msg);
+    }
+    if (e->hw_faceparse.alloc(mt_op_count(fg))) {       // nothing half-loaded stays behind
+        mt_graph_delete(fg);
+        return fail(LTK_E_NOMEM, "face parser: health table allocation failed");
+    }
+    e->face_parse = fg;
+    e->face_parse_size = size;
+    e->face_parse_images = max_images;
+    e->face_parse_last = 0;
+    return LTK_OK;
+}
+
+int ltk_face_parse(ltk_engine* e, const uint8_t* rgb_host, int n, uint8_t* labels_host) {
+    if (!e || !rgb_host || !labels_host || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->face_parse) return fail(LTK_E_STATE, "ltk_face_parse_load has not been called");
+    hipStream_t s = e->compute;
+    const size_t S = (size_t)e->face_parse_size, img = S * S * 3, lab = S * S;
+    const int cap = e->face_parse_images;
+    const MtWatched watch(e->face_parse, e->hw_faceparse, e->hw_faceparse.begin());      // one engine call = one watched call, whatever its chunks
+    int rc = LTK_OK;
+    for (int i0 = 0; i0 < n && !rc; i0 += cap) {
+        const int nf = std::min(cap, n - i0);
+        hipError_t he = hipMemcpyAsync(mt_face_parse_image_in(e->face_parse), rgb_host + (size_t)i0 * img, (size_t)nf * img, hipMemcpyHostToDevice, s);
+        if (he != hipSuccess) { rc = fail(LTK_E_HIP, std::string("face parser: upload: ") + hipGetErrorString(he)); break; }
+        const int prc = run_program(e, e->face_parse, nf);
+        if (prc) { rc = conv_status(prc, std::string("face parser: ") + mt_graph_error(e->face_parse)); break; }
+        e->face_parse_last = nf;
+        he = hipMemcpyAsync(labels_host + (size_t)i0 * lab, mt_face_parse_labels(e->face_parse), (size_t)nf * lab, hipMemcpyDeviceToHost, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);       // the one wait of the chunk: the next one refills the image buffer
+        if (he != hipSuccess) rc = fail(LTK_E_HIP, std::string("face parser: ") + hipGetErrorString(he));
+    }
+    if (rc) {                                            // nothing of the call still reads rgb_host or writes labels_host when it returns
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return fail(rc, msg);
+    }
+    return LTK_OK;
 }
 
 }  // extern "C"

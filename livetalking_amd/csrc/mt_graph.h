@@ -23,7 +23,9 @@ struct MtTensor {
     int P() const { return H * W; }
 };
 
-enum MtOpType { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_ADDPOS, OP_VT, OP_HB_L0, OP_LNGELU, OP_POSCONV };
+// (OP_FP_*: the face parser's own ops, parse_kernels.h; their listing types are faceparse.h FpOp::type, MtOp::fp_type)
+enum MtOpType { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_ADDPOS, OP_VT, OP_HB_L0, OP_LNGELU, OP_POSCONV,
+                OP_FP_STEM, OP_FP_MAXPOOL, OP_FP_GAP, OP_FP_GATE, OP_FP_LABELS };
 
 struct MtOp {
     MtOpType type;
@@ -46,6 +48,11 @@ struct MtOp {
     int vt_buf = -1;            // OP_ATTN: the values are already transposed in this buffer (written by the pass's OP_VT), else the shared scratch
     long long gn_slot_off = -1; // OP_GN on a map gn_coop_kernel serves: first word of this op's exchange slots in MtGraph::gn_slots
     int wvec = -1, bvec = -1;   // OP_HB_L0 / OP_POSCONV (hubert_kernels.hip): the op's own weights and bias in MtGraph::vecs
+    // face parser (mt_build_face_parse_graph): OP_FP_GATE's pre-sigmoid attention `ga` and added per-channel value `gb` (dense 1 x 1 maps;
+    // the added map is `r`) and its feat * atten + feat form; OP_FP_STEM: wvec = the packed weight image, gamma / beta = scale / shift
+    MtTensor ga, gb;
+    int plus1 = 0;
+    int fp_type = -1;           // the listing type of a face-parser op (0 conv, 10 stem ... 14 labels); -1: not one
 };
 
 // one cross-attention's share of the hoisted k | v projection (MtGraph::kv_all): its value view and where the transposed values go
@@ -90,6 +97,11 @@ struct MtGraph {
     int hb_layers = 0, hb_samples = 0, hb_rows = 0;
     int hb_pcm_buf = -1;                      // fp32 [hb_samples]: the normalised waveform of the clip
     MtTensor* hb_out = nullptr;               // last_hidden_state
+    // face parser (mt_build_face_parse_graph): the two byte buffers of the program, typed side buffers as hb_pcm_buf is
+    int fp_img_buf = -1;                      // uint8 [frames][fp_size][fp_size][3]: the RGB images
+    int fp_label_buf = -1;                    // uint8 [frames][fp_size][fp_size]: the labels
+    int fp_size = 0;
+    bool no_rowgemm = false;                  // builder setting: add_conv plans no row-GEMM form beside conv3's (mt_build_face_parse_graph)
 
     MtTensor alloc(int C, int H, int W);
     MtTensor alloc_q8(int C, int H, int W);          // C % 32 == 0

@@ -10,6 +10,7 @@
 #include "nn_kernels.h"
 #include "misc_kernels.h"
 #include "hubert_kernels.h"
+#include "parse_kernels.h"
 
 namespace ltk {
 
@@ -110,7 +111,7 @@ int MtGraph::add_conv2(const std::string& name, const float* w, const float* bia
     // Only the 1x1 / linear layers with <= 2560 outputs: a row block re-gathers its rows for every 32-output slab and every weight slab is
     // re-read by every row group, so the 3x3 layers (K = 11 520..23 040: ~1.4 GB of L2 -> CU traffic per layer at 1024 rows) and the
     // 10 240-output GEGLU projection would lose to conv3.
-    if (!x.q8 && !ups && act == 0 && sh == 1 && sw == 1 && kh == 1 && kw == 1 && ph == 0 && pw == 0 && pad_br == 0 &&
+    if (!no_rowgemm && !x.q8 && !ups && act == 0 && sh == 1 && sw == 1 && kh == 1 && kw == 1 && ph == 0 && pw == 0 && pad_br == 0 &&
         Cin % 32 == 0 && Cin <= 5120 && CoutP % 256 == 0 && CoutP <= 2560 && x.P() <= 64 && x.P() == y.P()) {
         const size_t K = (size_t)kk * Cin;
         std::vector<float> we((size_t)CoutP * K);
@@ -359,6 +360,32 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
             launch_geglu(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.y.C, op.x.P(), g.bufs[op.y.buf], op.y.ld / 16,
                          op.y.coff / 16, s);
             break;
+        // the face parser's own ops (parse_kernels.h): every launcher checks its views and refuses with its text, nothing enqueued
+        case OP_FP_STEM:
+        case OP_FP_MAXPOOL:
+        case OP_FP_GAP:
+        case OP_FP_GATE:
+        case OP_FP_LABELS: {
+            std::string e;
+            int rc = -1;
+            if (op.type == OP_FP_STEM)
+                rc = launch_parse_stem(reinterpret_cast<const uint8_t*>(g.bufs[g.fp_img_buf]), nf, g.fp_size, g.fp_size,
+                                       reinterpret_cast<const f16*>(g.vecs[op.wvec]), g.vecs[op.gamma], g.vecs[op.beta], g.bufs[op.y.buf],
+                                       op.y.ld / 16, op.y.coff / 16, s, &e);
+            else if (op.type == OP_FP_MAXPOOL)
+                rc = launch_maxpool3x3s2(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.H, op.x.W, g.bufs[op.y.buf], op.y.ld / 16,
+                                         op.y.coff / 16, s, &e);
+            else if (op.type == OP_FP_GAP)
+                rc = launch_gap(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.P(), g.bufs[op.y.buf], op.y.ld / 16, op.y.coff / 16, s, &e);
+            else if (op.type == OP_FP_GATE)
+                rc = launch_chan_gate(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.P(), g.bufs[op.ga.buf],
+                                      op.gb.buf >= 0 ? g.bufs[op.gb.buf] : nullptr, op.r.buf >= 0 ? g.bufs[op.r.buf] : nullptr, op.r.ld / 16,
+                                      op.r.coff / 16, op.plus1, g.bufs[op.y.buf], op.y.ld / 16, op.y.coff / 16, s, &e);
+            else
+                rc = launch_seg_argmax(g.bufs[op.x.buf], nf, op.x.H, op.x.W, reinterpret_cast<uint8_t*>(g.bufs[g.fp_label_buf]), s, &e);
+            if (rc) { g.err = op.name + ": " + e; return rc; }
+            break;
+        }
     }
     return 0;
 }
@@ -404,7 +431,7 @@ int mt_graph_run(MtGraph& g, int nf, float* partial, size_t partial_cap, hipStre
 int mt_op_count(MtGraph* g) { return (int)g->ops.size(); }
 const char* mt_op_name(MtGraph* g, int i, int* type) {
     if (i < 0 || i >= (int)g->ops.size()) return nullptr;
-    if (type) *type = (int)g->ops[i].type;
+    if (type) *type = g->ops[i].fp_type >= 0 ? g->ops[i].fp_type : (int)g->ops[i].type;
     return g->ops[i].name.c_str();
 }
 int mt_run_timed(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s, std::vector<hipEvent_t>* evs) {

@@ -50,6 +50,13 @@ double mt_macs_per_frame(const MtGraph* g);
 // VAE encoder graph (avatar preparation): image input = mt_latent_in() ([N][1][65536][16], RGB in [-1,1]),
 // moments (mean | logvar, 8 channels at 32x32) = mt_unet_out()
 int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* vae_sd, int n, int frames);
+// BiSeNet face parser (avatar preparation: blend masks) at one square image size for up to max_images images per run: the launch list
+// of faceparse.h fp_program over the buffers and views of fp_plan.  sd: BiSeNet.state_dict(); the unused heads and counters are not
+// read.  Input: uint8 RGB [n][size][size][3] in mt_face_parse_image_in(); output: uint8 labels [n][size][size] in mt_face_parse_labels().
+// 0, -1 (refused: the text in mt_graph_error) or -4 (allocation).
+int mt_build_face_parse_graph(MtGraph* g, const ltk_named_tensor* sd, int n, int size, int max_images);
+uint8_t* mt_face_parse_image_in(MtGraph* g);
+const uint8_t* mt_face_parse_labels(MtGraph* g);
 // Whisper encoder graph (one 30-s window per run): input log-mel tensor = mt_latent_in(), 5 hidden states
 int mt_build_whisper_graph(MtGraph* g, const ltk_named_tensor* encoder_sd, int n);
 f16* mt_whisper_state(MtGraph* g, int i, int* cbt, int* cb0);

@@ -20,6 +20,8 @@
 #include "mt_graph.h"
 #include "tune.h"
 #include "nn_kernels.h"
+#include "faceparse.h"
+#include "parse_kernels.h"
 
 namespace ltk {
 
@@ -613,5 +615,118 @@ int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* sd, int n, in
     if (mt_build_vae_encoder(*g, sd, n, g->t_latent, g->t_unet_out)) return -1;
     return mt_graph_alloc(*g, frames);
 }
+
+// ------------------------------------------------------------------------------------------ face parser (avatar preparation: blend masks)
+// BiSeNet's main output (avatars/musetalk/utils/face_parsing/model.py BiSeNet.forward()[0], resnet.py) + argmax as the 41 launches of
+// fp_program, wired by fp_plan (faceparse.h) and by nothing else: the plan's buffers become the graph's under the same ids, its views
+// the ops' tensors.  Convs are the library's with eval-mode BatchNorm folded into the fp32 scale / shift of the epilogue
+// (state_dict.h fold_bn; ffm.conv1, ffm.conv2 and conv_out.conv_out have neither BatchNorm nor bias); the stem's weights are packed once.
+namespace {
+// the state-dict names behind a conv of the list: its weight is `w`.weight, its BatchNorm `bn`.* (empty: none)
+void fp_keys(const std::string& name, std::string* w, std::string* bn) {
+    auto swap_tail = [&](const char* tail, const char* with) {
+        const size_t n = strlen(tail);
+        if (name.size() < n || name.compare(name.size() - n, n, tail) != 0) return false;
+        *bn = name.substr(0, name.size() - n) + with;
+        return true;
+    };
+    *w = name; bn->clear();
+    if (name.rfind("cp.resnet.", 0) == 0) {                      // resnet.py: conv1 / bn1, conv2 / bn2, downsample.0 / downsample.1
+        if (!swap_tail("conv1", "bn1") && !swap_tail("conv2", "bn2")) (void)swap_tail("downsample.0", "downsample.1");
+    } else if (swap_tail("conv_atten", "bn_atten")) {            // AttentionRefinementModule (model.py:66-67)
+    } else if (name == "ffm.conv1" || name == "ffm.conv2" || name == "conv_out.conv_out") {
+    } else {                                                      // ConvBNReLU (model.py:14-24): .conv / .bn
+        *w = name + ".conv"; *bn = name + ".bn";
+    }
+}
+MtTensor fp_tensor(const FpView& v) {
+    MtTensor t;
+    t.buf = v.buf; t.C = v.C; t.ld = v.ld; t.coff = v.coff; t.H = v.H; t.W = v.W;
+    return t;
+}
+}  // namespace
+
+int mt_build_face_parse_graph(MtGraph* gp, const ltk_named_tensor* t, int n, int size, int max_images) {
+    MtGraph& g = *gp;
+    FpPlan pl;
+    if (fp_plan(size, max_images, &pl, &g.err)) return -1;
+    SD sd{t, n, ""};
+    g.fp_size = size; g.fp_img_buf = pl.image_buf; g.fp_label_buf = pl.label_buf;
+    g.no_rowgemm = true;
+    for (size_t i = 0; i < pl.buf_elems.size(); ++i) {
+        const bool bytes = (int)i == pl.image_buf || (int)i == pl.label_buf;
+        g.buf_halfs.push_back(bytes ? (pl.buf_elems[i] + 1) / 2 : pl.buf_elems[i]);
+    }
+    constexpr float kBnEps = 1e-5f;                                // nn.BatchNorm2d's default, which the reference keeps
+    for (size_t i = 0; i < pl.ops.size(); ++i) {
+        const FpOp& p = pl.ops[i];
+        const FpBind& b = pl.bind[i];
+        const MtTensor x = fp_tensor(b.x), y = fp_tensor(b.y);
+        if (p.type == 0 || p.type == 10) {
+            std::string wk, bk;
+            fp_keys(p.name, &wk, &bk);
+            const float* w = sd.get(wk + ".weight", (size_t)p.cout * p.cin * p.k * p.k);
+            if (!w) { g.err = sd.err; return -1; }
+            std::vector<float> scale((size_t)p.cout, 1.f), shift((size_t)p.cout, 0.f);
+            if (!bk.empty()) {
+                const float* ga = sd.get(bk + ".weight", p.cout);
+                const float* be = ga ? sd.get(bk + ".bias", p.cout) : nullptr;
+                const float* mu = be ? sd.get(bk + ".running_mean", p.cout) : nullptr;
+                const float* va = mu ? sd.get(bk + ".running_var", p.cout) : nullptr;
+                if (!va) { g.err = sd.err; return -1; }
+                fold_bn(ga, be, mu, va, nullptr, kBnEps, p.cout, scale.data(), shift.data());
+            }
+            if (p.type == 10) {
+                if (p.cout != kStemCout || p.cin != 3 || p.k != 7) { g.err = p.name + ": not the stem parse_stem_kernel serves"; return -1; }
+                std::vector<f16> wq(kStemWHalfs);
+                parse_stem_pack(w, wq.data());
+                MtOp op;
+                op.type = OP_FP_STEM; op.fp_type = p.type; op.name = p.name; op.y = y;
+                op.wvec = g.add_named_vec(p.name + ".wq", wq.data(), wq.size() * sizeof(f16));
+                op.gamma = g.add_vec(scale.data(), p.cout);
+                op.beta = g.add_vec(shift.data(), p.cout);
+                if (op.wvec < 0 || op.gamma < 0 || op.beta < 0) return -4;
+                g.ops.push_back(op);
+                g.named[p.name] = y;
+                g.macs += (double)p.cin * p.cout * p.k * p.k * y.P();
+                continue;
+            }
+            const MtTensor r = fp_tensor(b.r);
+            MtTensor xin = x;
+            if (p.ups) { xin.H *= 2; xin.W *= 2; }        // the logical (upsampled) size the conv runs on; the view is the stored map
+            if (xin.H != p.H || xin.W != p.W || y.H != p.Ho || y.W != p.Wo) { g.err = p.name + ": the bound maps are not the op's"; return -1; }
+            if (g.add_conv(p.name, w, shift.data(), p.cin, p.cout, p.k, p.stride, p.pad, xin, y, b.r.buf >= 0 ? &r : nullptr, p.relu ? 1 : 0, p.ups,
+                           scale.data()))
+                return -1;
+            g.ops.back().fp_type = 0;
+            // conv3 under its own rule, as the conv planner is held to for every conv of the list (tests/test_faceparse_host.py): not the
+            // U-Net's measured forced tiles (and no row-GEMM form for ffm.conv2's 64 -> 256 channels on one pixel: no_rowgemm above)
+            g.ops.back().unet3x3 = false;
+            continue;
+        }
+        MtOp op;
+        op.fp_type = p.type; op.name = p.name; op.x = x; op.y = y;
+        if (p.type == 11) op.type = OP_FP_MAXPOOL;
+        else if (p.type == 12) op.type = OP_FP_GAP;
+        else if (p.type == 13) {
+            op.type = OP_FP_GATE; op.plus1 = p.plus1;
+            op.ga = fp_tensor(b.a); op.gb = fp_tensor(b.b); op.r = fp_tensor(b.r);
+            // launch_chan_gate reads the attention and the added value as dense tensors
+            if (op.ga.buf < 0 || op.ga.coff || op.ga.ld != x.C || (op.gb.buf >= 0 && (op.gb.coff || op.gb.ld != x.C))) {
+                g.err = p.name + ": the gate's attention / broadcast operand is not a dense tensor of its channels";
+                return -1;
+            }
+        } else if (p.type == 14) {
+            op.type = OP_FP_LABELS;
+            op.y = MtTensor();                    // bytes in fp_label_buf: no fp16 output tensor (nothing to scan, nothing to read back)
+            if (x.ld != 32 || x.coff || x.C != 32) { g.err = p.name + ": the logits must be a dense 32-channel tensor"; return -1; }
+        } else { g.err = p.name + ": unknown op type"; return -1; }
+        g.ops.push_back(op);
+        if (p.type != 14) g.named[p.name] = y;
+    }
+    return mt_graph_alloc(g, max_images);
+}
+uint8_t* mt_face_parse_image_in(MtGraph* g) { return reinterpret_cast<uint8_t*>(g->bufs[g->fp_img_buf]); }
+const uint8_t* mt_face_parse_labels(MtGraph* g) { return reinterpret_cast<const uint8_t*>(g->bufs[g->fp_label_buf]); }
 
 }  // namespace ltk

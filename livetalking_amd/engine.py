@@ -40,6 +40,7 @@ class Engine:
         self._h = h
         self.device = int(device)
         self.max_frames = 0
+        self.face_parse_size = None     # the image size load_face_parser built the parser for
         self._closed = False
         self._lock = threading.Lock()
         self._egress_open = set()       # egress sessions still open: closed with the engine
@@ -491,6 +492,59 @@ class Engine:
         _lib.check(_lib.load().ltk_debug_face_parse_program(int(size), ops, 64, C.byref(n)))
         return [dict(name=o.name.decode(), **{f: getattr(o, f) for f, _ in _lib.FpOpInfo._fields_[1:]}) for o in ops[:n.value]]
 
+    @staticmethod
+    def face_parse_plan(size: int = 512, max_images: int = 1):
+        """Where every launch of face_parse_program(size) reads and writes (include/ltk.h: ltk_debug_face_parse_plan), on the host
+        alone: dict(ops=[dict(name, x, y, r, a, b)], buf_bytes=[...], image_buf, label_buf).  A view is dict(buf, ld, coff, C, H, W),
+        or None where the op has no such operand."""
+        ops = (_lib.FpBind * 64)()
+        bufs = (C.c_ulonglong * 64)()
+        n, nb, ib, lb = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.load().ltk_debug_face_parse_plan(int(size), int(max_images), ops, 64, C.byref(n), bufs, 64, C.byref(nb), C.byref(ib),
+                                                         C.byref(lb)))
+
+        def view(v):
+            return None if v.buf < 0 else {f: int(getattr(v, f)) for f, _ in _lib.FpView._fields_}
+        return dict(ops=[dict(name=o.name.decode(), **{k: view(getattr(o, k)) for k in ("x", "y", "r", "a", "b")}) for o in ops[:n.value]],
+                    buf_bytes=[int(b) for b in bufs[:nb.value]], image_buf=ib.value, label_buf=lb.value)
+
+    # ------------------------------------------------------------------ avatar preparation (face parser: blend-mask labels)
+    def load_face_parser(self, sd: Dict[str, object], size: int = 512, max_images: int = 1):
+        """face_parsing/__init__.py:44-56: `sd` = BiSeNet(n_classes=19).state_dict() (79999_iter.pth), tensors or arrays; the unused
+        conv_out16 / conv_out32 heads may be present.  size: the square image size (the reference parses at 512); max_images: images
+        per run of the program."""
+        arr, n, keep = self._named_tensors(sd)
+        _lib.check(self._lib.ltk_face_parse_load(self._h, arr, n, int(size), int(max_images)))
+        self.face_parse_size = int(size)
+        del keep
+
+    def face_parse(self, rgb: np.ndarray) -> np.ndarray:
+        """uint8 RGB (n, S, S, 3) at the loaded size -> uint8 labels (n, S, S), classes 0..18 (include/ltk.h: ltk_face_parse)."""
+        rgb = np.asarray(rgb)
+        if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[0] < 1 or rgb.shape[3] != 3 or rgb.shape[1] != rgb.shape[2]:
+            raise ValueError(f"face_parse: uint8 (n, S, S, 3) expected, got {rgb.dtype} {rgb.shape}")
+        size = self.face_parse_size
+        if size is not None and rgb.shape[1] != size:
+            raise ValueError(f"face_parse: the parser was loaded for {size} x {size} images, got {rgb.shape[1]} x {rgb.shape[2]}")
+        rgb = np.ascontiguousarray(rgb)
+        out = np.empty(rgb.shape[:3], dtype=np.uint8)
+        # (before a load the library refuses with LTK_E_STATE)
+        _lib.check(self._lib.ltk_face_parse(self._h, rgb.ctypes.data, int(rgb.shape[0]), out.ctypes.data))
+        return out
+
+    def face_parse_debug_get(self, name: str, shape) -> np.ndarray:
+        """The output of the launch `name` as the last run left it: float32 (images, cout, Ho, Wo), real channels only."""
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.ltk_face_parse_debug_get(self._h, name.encode(), int(shape[0]), out.ctypes.data, out.size))
+        return out
+
+    def face_parse_time(self, images: int, iters: int, per_op: bool = False):
+        """(ms per device pass of `images` images as ltk_face_parse replays it, per-launch ms or None)."""
+        ms = C.c_float()
+        ops = (C.c_float * 41)() if per_op else None
+        _lib.check(self._lib.ltk_debug_face_parse_time(self._h, int(images), int(iters), C.byref(ms), ops, 41 if per_op else 0))
+        return ms.value, (np.array(ops[:], dtype=np.float64) if per_op else None)
+
     # ---- frame egress (include/ltk.h: ltk_egress_*)
     def egress_open(self, H: int, W: int) -> int:
         h = C.c_void_p()
@@ -793,7 +847,7 @@ class Engine:
                 "limit": float(o.limit)}
 
     def health_watch(self, program, calls: int, avatar_id: int = -1):
-        """Arm the next `calls` inference calls of `program` ("wav2lip", "musetalk", "ultralight", "whisper", "hubert" or an
+        """Arm the next `calls` inference calls of `program` ("wav2lip", "musetalk", "ultralight", "whisper", "hubert", "faceparse" or an
         LTK_HEALTH_* code): each runs its usual launches with a scan behind every op.  0 disarms.  avatar_id: Ultralight only."""
         _lib.check(self._lib.ltk_health_watch(self._h, self._health_program(program), int(avatar_id), int(calls)))
 
