@@ -413,6 +413,31 @@ int ltk_face_parse_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int si
 int ltk_face_parse(ltk_engine* e, const uint8_t* rgb_host, int n, uint8_t* labels_host);
 int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats);
 
+/* Avatar preparation, face boxes: the S3FD face detector (avatars/wav2lip/face_detection/detection/sfd/net_s3fd.py s3fd.forward, then
+ * what detect.py batch_detect does per level: softmax, threshold, bbox.py batch_decode) as one replayed device program over the 39
+ * launches of ltk_debug_face_detect_program, wired as ltk_debug_face_detect_plan lists.  genavatar.py and MuseTalk's preprocessing.py
+ * take their face box from it (through api.py get_detections_for_batch; livetalking_amd/face_detect.py has the host side).
+ * ltk_face_detect_load: sd = s3fd().state_dict() (fp32 host); a missing key is LTK_E_INVALID and the message names it.  max_images in
+ * [1, 16] (the reference's face_det_batch_size): images per run of a program.  LTK_E_STATE on a second load.
+ * ltk_face_detect: bgr_host uint8 [n][H][W][3] as cv2.imread gives the frames (the channel reversal of api.py:65 and the mean
+ * subtraction of detect.py:59 happen on the device).  The program for (H, W) is built on first use over the loaded weights and captured
+ * once per image count; the engine keeps the 2 most recently used.  H, W >= 32 and the program's buffers below 8 GiB, else
+ * LTK_E_INVALID with the figure.  n may exceed max_images: the images go through in chunks of max_images (the last one short), each
+ * uploaded (one copy: the frames), run and copied back with one synchronisation.  thresh in [0, 1) (the reference: 0.05).  Output per image i: counts_out[i] =
+ * the positions whose score is above thresh, and in cand_out[i][cap][6] (32-bit words) the first min(counts_out[i], cap) of them in
+ * ascending key order, zeros behind: word 0 the key = level << 28 | h << 14 | w, words 1..5 the floats x1, y1, x2, y2, score.  The
+ * output does not depend on the order the device found them in.  counts_out[i] > cap is reported as it is (the list is then cut);
+ * cap in [1, 4096], the device's own list length: beyond 4096 candidates the kept ones are an arbitrary subset.  Every image gets its
+ * OWN positions (batch_detect decodes a position for every image of the batch when any image passes there; greedy NMS followed by the
+ * 0.5 filter makes those extra rows irrelevant, see face_detect.py).  LTK_E_STATE before a load; a refused call has launched nothing.
+ * ltk_face_detect_debug_get (test hook): the output of the launch named op_name as the last run left it, `images` <= the images of that
+ * run, as float32 [images][cout][Ho][Wo] (a merged head: 16 channels); the detect launches have no tensor.  The trunk's launches share
+ * two buffers, so for those the hook runs the program again up to the named launch, on the frames that run left on the device, and reads
+ * then; a tapped map, a norm and a head have buffers of their own and are read as the run left them. */
+int ltk_face_detect_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int max_images);
+int ltk_face_detect(ltk_engine* e, const uint8_t* bgr_host, int n, int H, int W, float thresh, uint32_t* cand_out, int cap, int* counts_out);
+int ltk_face_detect_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats);
+
 /* =========================== fp16 headroom watch: the first calls on a real checkpoint =========================== */
 
 /* The conv epilogues clamp to the fp16 range (fmed3f(t, -65504, 65504); +-448 on the e4m3 tensors of the fp8 path) and nothing reports
@@ -442,7 +467,10 @@ int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, flo
  * find prefetching as the first calls of a session do. */
 enum { LTK_HEALTH_WAV2LIP = 0, LTK_HEALTH_MUSETALK = 1, LTK_HEALTH_ULTRALIGHT = 2, LTK_HEALTH_WHISPER = 3, LTK_HEALTH_HUBERT = 4,
        /* 5 stays unassigned: callers written against the five codes above treat it as the first unknown program */
-       LTK_HEALTH_FACEPARSE = 6 };
+       LTK_HEALTH_FACEPARSE = 6,
+       /* the 39 launches of ltk_debug_face_detect_program with its types; every frame size's program counts into one table, a watched
+        * ltk_face_detect call counts once whatever its chunks, the detect launches write records and stay unobserved */
+       LTK_HEALTH_FACEDET = 7 };
 
 typedef struct ltk_health_op {
     char name[64];
@@ -820,6 +848,62 @@ int ltk_debug_face_parse_plan(int size, int max_images, ltk_fp_bind* ops, int ma
  * events between eager launches.  Whatever the last ltk_face_parse left in the program's buffers is the input.  LTK_E_STATE before a
  * load; a run the program refuses: its code and text as ltk_face_parse reports them. */
 int ltk_debug_face_parse_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops);
+
+/* Standalone ops of the S3FD face detector (avatars/wav2lip/face_detection/detection/sfd/net_s3fd.py, detect.py, bbox.py;
+ * csrc/s3fd_kernels.h), used by kernel unit tests.  Tensors are device fp16 [N][C/16][H][W][16]; `opts` (may be NULL) carries channel
+ * views only, as for the face parser's ops.  LTK_E_INVALID for what an op does not take (named in ltk_last_error), nothing launched.
+ *   ltk_s3fd_stem_f16    : conv1_1 + ReLU (net_s3fd.py:71) on the frame itself: bgr device uint8 [N][H][W][3] as cv2.imread gives it, any
+ *                          H, W >= 1.  The input transform of api.py:65 and detect.py:59 is fused: the network's channel c is byte 2 - c
+ *                          of the pixel minus (104, 117, 123)[c] (the means in the order the reference applies them to the REVERSED
+ *                          image); 0 outside the image (the padding of the mean-subtracted tensor).  weight host fp32 [64][3][3][3]
+ *                          (rounded to fp16), bias host fp32 [64] (NULL = 0); y = relu(conv + bias), 64 channels on H x W.
+ *   ltk_maxpool2x2s2_f16 : F.max_pool2d(x, 2, 2), floor mode: y on (H / 2) x (W / 2), an odd last row / column is dropped.  Exact.
+ *   ltk_l2norm_f16       : L2Norm (net_s3fd.py:16-19) over the C channels of each of P pixels: y = x / (sqrt(sum x^2) + 1e-10) * weight[c],
+ *                          the sum in fp32 in ascending channel order, one fp16 rounding; weight host fp32 [C].
+ *   ltk_s3fd_detect_f16  : detect.py:71-89 + bbox.py:111-129 for level `level` (stride 2^(level+2)) of a merged head map x [N][1][H][W][16]
+ *                          (conf at channels 0..1 - 0..3 with maxout: conf = [max(c0, c1, c2), c3] -, loc at 4..7): where the fp32
+ *                          two-way softmax score > thresh, one record {uint32 key = level << 28 | h << 14 | w, float x1, y1, x2, y2,
+ *                          score} is appended to d_recs [N][cap][6 words] through the counter d_counts[n] (uint32 [N], NOT reset by the
+ *                          call; it keeps counting past cap, records beyond cap are dropped).  Arrival order is arbitrary. */
+int ltk_s3fd_stem_f16(ltk_engine* e, const void* d_bgr, int N, int H, int W, const float* weight, const float* bias, void* d_y,
+                      const ltk_conv_opts* opts);
+int ltk_maxpool2x2s2_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, void* d_y, const ltk_conv_opts* opts);
+int ltk_l2norm_f16(ltk_engine* e, const void* d_x, int N, int P, int C, const float* weight, void* d_y, const ltk_conv_opts* opts);
+int ltk_s3fd_detect_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int maxout, int level, float thresh, void* d_recs, int cap,
+                        void* d_counts, const ltk_conv_opts* opts);
+
+/* The launch list of the S3FD face detector at one frame size, on the host alone (no engine, no GPU; csrc/facedet.h fd_program): per
+ * launch its name, type (0 the library's conv, 20 stem, 21 max pool 2x2, 22 L2Norm, 23 detect), channels in and out, k / stride / pad,
+ * relu, maxout and level (heads and detects; -1 elsewhere), the map read H x W (the stem: the frame) and written Ho x Wo.  A level's conf
+ * and loc convs are ONE conv "<source>_mbox" of 16 output channels (conf at 0..1 - 0..3 at level 0 -, loc at 4..7, the rest zero).
+ * 39 launches.  Level 3 is the fc7 map, (H/32 + 4) x (W/32 + 4), read with stride 32, as in the reference.
+ * LTK_E_INVALID: H or W outside [32, 16384], or max_ops too small. */
+typedef struct ltk_fd_op_info {
+    char name[64];
+    int type, cin, cout, k, stride, pad, relu, maxout, level;
+    int H, W, Ho, Wo;
+} ltk_fd_op_info;
+int ltk_debug_face_detect_program(int H, int W, ltk_fd_op_info* ops, int max_ops, int* n_ops);
+
+/* Where every launch of that list reads (x) and writes (y) at (H, W, max_images), on the host alone (csrc/facedet.h fd_plan); views as
+ * in ltk_debug_face_parse_plan.  The two trunk buffers are written in turn; tapped maps, norms and heads have buffers of their own; a
+ * detect op has no y: it appends to the record buffer, the last of the table (per image 4096 records of 24 bytes and a share of the
+ * 256-byte head).  *image_buf is uint8 [max_images][H][W][3].  buf_bytes[i]: bytes of buffer i at
+ * max_images, *total_bytes their sum.  LTK_E_INVALID: sizes as above, max_images outside [1, 16], total_bytes at or above 8 GiB (the
+ * text names the figure), max_ops / max_bufs too small. */
+typedef struct ltk_fd_bind {
+    char name[64];
+    ltk_fp_view x, y;
+} ltk_fd_bind;
+int ltk_debug_face_detect_plan(int H, int W, int max_images, ltk_fd_bind* ops, int max_ops, int* n_ops, unsigned long long* buf_bytes,
+                               int max_bufs, int* n_bufs, int* image_buf, unsigned long long* total_bytes);
+
+/* Measurement hook (scripts/face_detect_time.py; not on the production call path), the twin of ltk_debug_face_parse_time for the
+ * program of the frame size the last ltk_face_detect ran: *ms_per_pass = milliseconds of one device pass of `images` <= max_images
+ * images, replayed as ltk_face_detect replays it, without upload or copy-back, over `iters` runs; ms_per_op (or NULL; n_ops = 39):
+ * per-launch times from events between eager launches.  Whatever that call left in the program's buffers is the input (the counters
+ * are not reset: the lists fill up and the detect launches go on counting).  LTK_E_STATE before a load or a first call. */
+int ltk_debug_face_detect_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops);
 
 /* Names of every fp16 conv3 instantiation the launch path can pick, one per line, NUL-terminated, into buf[cap]; no GPU needed.
  * Returns LTK_E_INVALID when cap is too small. */

@@ -95,6 +95,15 @@ class FpBind(C.Structure):
     _fields_ = [("name", C.c_char * 64)] + [(n, FpView) for n in ("x", "y", "r", "a", "b")]
 
 
+class FdOpInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, C.c_int) for n in ("type", "cin", "cout", "k", "stride", "pad", "relu", "maxout", "level",
+                                                                     "H", "W", "Ho", "Wo")]
+
+
+class FdBind(C.Structure):
+    _fields_ = [("name", C.c_char * 64)] + [(n, FpView) for n in ("x", "y")]
+
+
 class NormOpts(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("x_ld", "x_coff", "y_ld", "y_coff")]
 
@@ -112,8 +121,9 @@ class HealthOp(C.Structure):
 # include/ltk.h LTK_HEALTH_*: the programs a headroom watch can be armed for
 HEALTH_WAV2LIP, HEALTH_MUSETALK, HEALTH_ULTRALIGHT, HEALTH_WHISPER, HEALTH_HUBERT = range(5)
 HEALTH_FACEPARSE = 6         # (5 stays unassigned)
+HEALTH_FACEDET = 7
 HEALTH_PROGRAMS = {"wav2lip": HEALTH_WAV2LIP, "musetalk": HEALTH_MUSETALK, "ultralight": HEALTH_ULTRALIGHT, "whisper": HEALTH_WHISPER,
-                   "hubert": HEALTH_HUBERT, "faceparse": HEALTH_FACEPARSE}
+                   "hubert": HEALTH_HUBERT, "faceparse": HEALTH_FACEPARSE, "facedet": HEALTH_FACEDET}
 
 DEFER_SYNC = 2      # flag of ltk_wav2lip_infer_deferred
 
@@ -179,6 +189,18 @@ SYMBOLS = {
     "ltk_face_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "ltk_face_parse_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
     "ltk_debug_face_parse_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    "ltk_s3fd_stem_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_maxpool2x2s2_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_l2norm_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_s3fd_detect_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.POINTER(ConvOpts)]),
+    "ltk_face_detect_load": (C.c_int, [C.c_void_p, C.POINTER(NamedTensor), C.c_int, C.c_int]),
+    "ltk_face_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "ltk_face_detect_debug_get": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "ltk_debug_face_detect_time": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    "ltk_debug_face_detect_program": (C.c_int, [C.c_int, C.c_int, C.POINTER(FdOpInfo), C.c_int, C.POINTER(C.c_int)]),
+    "ltk_debug_face_detect_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(FdBind), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong),
+                                             C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
     "ltk_egress_open": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "ltk_egress_close": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ltk_egress_watermark": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -227,7 +227,7 @@ def prepare_musetalk_avatar(frames_bgr: Sequence[np.ndarray], boxes, out_dir: st
                             extra_margin: int = 10, parsing_mode: str = "jaw", noise: Optional[np.ndarray] = None) -> str:
     """Writes full_imgs/%08d.png, mask/%08d.png, coords.pkl, mask_coords.pkl, latents.pt and avator_info.json into out_dir: the
     directory musetalk_avatar.load_avatar and bank.pack_avatar_dir read.  boxes: (x1, y1, x2, y2) per frame (no placeholder boxes:
-    every frame needs its face).  noise: as Engine.vae_encode_faces takes it (None: the distribution's mean)."""
+    every frame needs its face; face_detect.FaceDetector(engine, s3fd_sd).get_detections_for_batch gives the reference's fallback box).  noise: as Engine.vae_encode_faces takes it (None: the distribution's mean)."""
     import torch
     if len(frames_bgr) != len(boxes) or not len(frames_bgr):
         raise ValueError("prepare_musetalk_avatar: one box per frame, at least one frame")

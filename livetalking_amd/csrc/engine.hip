@@ -114,6 +114,7 @@ void ltk_engine_destroy(ltk_engine* e) {
     hubert_unload(e);
     if (e->vae_enc) mt_graph_delete(e->vae_enc);
     if (e->face_parse) mt_graph_delete(e->face_parse);
+    face_det_unload(e);
     if (e->d_wbasis) (void)hipFree(e->d_wbasis);
     if (e->d_wlogspec) (void)hipFree(e->d_wlogspec);
     if (e->d_wpcm) (void)hipFree(e->d_wpcm);

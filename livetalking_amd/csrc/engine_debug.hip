@@ -1,7 +1,9 @@
 // ------------------------------------------------------------------ test / measurement hooks of both models
 #include "debug_util.h"
+#include "facedet.h"
 #include "faceparse.h"
 #include "parse_kernels.h"
+#include "s3fd_kernels.h"
 #include "ul_gconv.h"
 #include "ul_ir.h"
 
@@ -922,13 +924,13 @@ namespace {
 
 // the channel views of a face-parser hook: channels -> channel blocks, LTK_OK or the refusal
 struct ParseViews { int x_cbt, x_cb0, y_cbt, y_cb0, r_cbt, r_cb0; };
-int parse_views(const ltk_conv_opts* o, int Cx, int Cy, ParseViews* v) {
+int parse_views(const ltk_conv_opts* o, int Cx, int Cy, ParseViews* v, const std::string& who = "face parser op") {
     if (o && (o->act || o->ups || o->force_pxw || o->force_nbt || o->force_ksplit || o->family))
-        return fail(LTK_E_INVALID, "face parser op: only the channel views of the options apply");
-    if (Cx <= 0 || Cx % 16) return fail(LTK_E_INVALID, "face parser op: C % 16 == 0");
+        return fail(LTK_E_INVALID, who + ": only the channel views of the options apply");
+    if (Cx <= 0 || Cx % 16) return fail(LTK_E_INVALID, who + ": C % 16 == 0");
     const int x_ld = o && o->x_ld ? o->x_ld : Cx, y_ld = o && o->y_ld ? o->y_ld : Cy, r_ld = o && o->res_ld ? o->res_ld : Cy;
     const int x_coff = o ? o->x_coff : 0, y_coff = o ? o->y_coff : 0, r_coff = o ? o->res_coff : 0;
-    if ((x_ld | x_coff | y_ld | y_coff | r_ld | r_coff) & 15) return fail(LTK_E_INVALID, "face parser op: channel views are multiples of 16 channels");
+    if ((x_ld | x_coff | y_ld | y_coff | r_ld | r_coff) & 15) return fail(LTK_E_INVALID, who + ": channel views are multiples of 16 channels");
     *v = ParseViews{x_ld / 16, x_coff / 16, y_ld / 16, y_coff / 16, r_ld / 16, r_coff / 16};
     return LTK_OK;
 }
@@ -1048,6 +1050,102 @@ int ltk_debug_face_parse_plan(int size, int max_images, ltk_fp_bind* ops, int ma
     return LTK_OK;
 }
 
+// ---- the face detector's own ops (s3fd_kernels.h) and its launch list (facedet.h)
+int ltk_s3fd_stem_f16(ltk_engine* e, const void* d_bgr, int N, int H, int W, const float* weight, const float* bias, void* d_y,
+                      const ltk_conv_opts* opts) {
+    if (!e || !d_bgr || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, 16, kFdStemCout, &v, "face detector op"); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::vector<f16> wq(kFdStemWHalfs);
+    s3fd_stem_pack(weight, wq.data());
+    std::vector<float> bs(kFdStemCout);
+    for (int c = 0; c < kFdStemCout; ++c) bs[c] = bias ? bias[c] : 0.f;
+    DevBuf d_w, d_b;
+    int rc = upload(wq.data(), wq.size() * sizeof(f16), &d_w);
+    if (!rc) rc = upload(bs.data(), bs.size() * sizeof(float), &d_b);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_s3fd_stem((const uint8_t*)d_bgr, N, H, W, (const f16*)d_w.p, (const float*)d_b.p, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "s3fd stem kernel");
+}
+
+int ltk_maxpool2x2s2_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int C, void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, C, C, &v, "face detector op"); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_maxpool2x2s2((const f16*)d_x, N, v.x_cbt, v.x_cb0, C, H, W, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "maxpool 2x2 kernel");
+}
+
+int ltk_l2norm_f16(ltk_engine* e, const void* d_x, int N, int P, int C, const float* weight, void* d_y, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !weight || !d_y) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, C, C, &v, "face detector op"); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    DevBuf d_w;
+    { const int rc = upload(weight, (size_t)C * sizeof(float), &d_w); if (rc) return rc; }
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_l2norm((const f16*)d_x, N, v.x_cbt, v.x_cb0, C, P, (const float*)d_w.p, (f16*)d_y, v.y_cbt, v.y_cb0, e->compute, &err);
+    return parse_finish(e, lrc, err, "l2norm kernel");
+}
+
+int ltk_s3fd_detect_f16(ltk_engine* e, const void* d_x, int N, int H, int W, int maxout, int level, float thresh, void* d_recs, int cap,
+                        void* d_counts, const ltk_conv_opts* opts) {
+    if (!e || !d_x || !d_recs || !d_counts) return fail(LTK_E_INVALID, "bad arguments");
+    ParseViews v;
+    { const int rc = parse_views(opts, 16, 16, &v, "face detector op"); if (rc) return rc; }
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    std::string err;
+    const int lrc = launch_s3fd_detect((const f16*)d_x, N, v.x_cbt, v.x_cb0, H, W, maxout, level, thresh, nullptr, (uint32_t*)d_recs, cap, (uint32_t*)d_counts,
+                                       e->compute, &err);
+    return parse_finish(e, lrc, err, "s3fd detect kernel");
+}
+
+int ltk_debug_face_detect_program(int H, int W, ltk_fd_op_info* ops, int max_ops, int* n_ops) {
+    if (!ops || !n_ops || max_ops <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    const std::vector<FdOp> prog = fd_program(H, W);
+    if (prog.empty()) return fail(LTK_E_INVALID, "face detector: H and W must be in [32, 16384]");
+    if ((int)prog.size() > max_ops) return fail(LTK_E_INVALID, "face detector: the program has " + std::to_string(prog.size()) + " ops");
+    for (size_t i = 0; i < prog.size(); ++i) {
+        const FdOp& p = prog[i];
+        ltk_fd_op_info& o = ops[i];
+        memset(&o, 0, sizeof(o));
+        snprintf(o.name, sizeof(o.name), "%s", p.name.c_str());
+        o.type = p.type; o.cin = p.cin; o.cout = p.cout; o.k = p.k; o.stride = p.stride; o.pad = p.pad; o.relu = p.relu; o.maxout = p.maxout;
+        o.level = p.level; o.H = p.H; o.W = p.W; o.Ho = p.Ho; o.Wo = p.Wo;
+    }
+    *n_ops = (int)prog.size();
+    return LTK_OK;
+}
+
+int ltk_debug_face_detect_plan(int H, int W, int max_images, ltk_fd_bind* ops, int max_ops, int* n_ops, unsigned long long* buf_bytes,
+                               int max_bufs, int* n_bufs, int* image_buf, unsigned long long* total_bytes) {
+    if (!ops || !n_ops || !buf_bytes || !n_bufs || !image_buf || !total_bytes || max_ops <= 0 || max_bufs <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    FdPlan pl;
+    std::string err;
+    if (fd_plan(H, W, max_images, &pl, &err)) return fail(LTK_E_INVALID, err);
+    if ((int)pl.ops.size() > max_ops) return fail(LTK_E_INVALID, "face detector: the program has " + std::to_string(pl.ops.size()) + " ops");
+    if ((int)pl.buf_bytes.size() > max_bufs) return fail(LTK_E_INVALID, "face detector: the program has " + std::to_string(pl.buf_bytes.size()) + " buffers");
+    auto view = [](const FdView& v) { return ltk_fp_view{v.buf, v.ld, v.coff, v.C, v.H, v.W}; };
+    for (size_t i = 0; i < pl.ops.size(); ++i) {
+        ltk_fd_bind& o = ops[i];
+        memset(&o, 0, sizeof(o));
+        snprintf(o.name, sizeof(o.name), "%s", pl.ops[i].name.c_str());
+        o.x = view(pl.bind[i].x); o.y = view(pl.bind[i].y);
+    }
+    for (size_t i = 0; i < pl.buf_bytes.size(); ++i) buf_bytes[i] = (unsigned long long)pl.buf_bytes[i];
+    *n_ops = (int)pl.ops.size(); *n_bufs = (int)pl.buf_bytes.size();
+    *image_buf = pl.image_buf; *total_bytes = (unsigned long long)pl.total_bytes;
+    return LTK_OK;
+}
+
 int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats) {
     if (!e || !op_name || !out_f32 || images <= 0) return fail(LTK_E_INVALID, "bad arguments");
     if (!e->face_parse) return fail(LTK_E_STATE, "ltk_face_parse_load has not been called");
@@ -1064,6 +1162,66 @@ int ltk_face_parse_debug_get(ltk_engine* e, const char* op_name, int images, flo
     const size_t cnt = (size_t)images * cout * H * W;
     if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats for these images");
     return read_cb16(e, t, images, cout, ld, coff, H, W, out_f32);          // the real channels of the view
+}
+
+int ltk_face_detect_debug_get(ltk_engine* e, const char* op_name, int images, float* out_f32, size_t n_floats) {
+    if (!e || !op_name || !out_f32 || images <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->face_det_w) return fail(LTK_E_STATE, "ltk_face_detect_load has not been called");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->face_det_last) return fail(LTK_E_STATE, "face detector: no program has run");
+    if (images > e->face_det_last_n)
+        return fail(LTK_E_INVALID, "face detector: the last run held " + std::to_string(e->face_det_last_n) + " images");
+    int C, ld, coff, H, W;
+    f16* t = mt_named(e->face_det_last, op_name, &C, &ld, &coff, &H, &W);
+    if (!t) return fail(LTK_E_STATE, std::string("no face detector tensor named ") + op_name);
+    const size_t cnt = (size_t)images * C * H * W;
+    if (cnt != n_floats) return fail(LTK_E_INVALID, "size mismatch: tensor has " + std::to_string(cnt) + " floats for these images");
+    // a tapped map, a norm and a head have buffers of their own: they are read as the (replayed) run left them.  The trunk's other
+    // ops write two buffers in turn (fd_plan), so what such a launch wrote is gone by the end of a run: the program runs again,
+    // eagerly, on the frames the last call left in its image buffer, up to and including this launch - the same kernels with the
+    // same arguments on the same bytes.  The detect launches stand behind every tensor: the records are not touched.
+    if (mt_named_writers(e->face_det_last, op_name) == 1) return read_cb16(e, t, images, C, ld, coff, H, W, out_f32);
+    int k = -1;
+    for (int i = 0; i < mt_op_count(e->face_det_last) && k < 0; ++i)
+        if (!strcmp(mt_op_name(e->face_det_last, i, nullptr), op_name)) k = i;
+    if (k < 0) return fail(LTK_E_STATE, std::string("no face detector launch named ") + op_name);
+    const int prc = mt_run_head(e->face_det_last, e->face_det_last_n, e->d_partial, e->partial_cap, e->compute, k + 1);
+    if (prc) return conv_status(prc, std::string("face detector: ") + mt_graph_error(e->face_det_last));
+    return read_cb16(e, t, images, C, ld, coff, H, W, out_f32);
+}
+
+int ltk_debug_face_detect_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops) {
+    if (!e || images <= 0 || iters <= 0 || !ms_per_pass) return fail(LTK_E_INVALID, "bad arguments");
+    if (!e->face_det_w) return fail(LTK_E_STATE, "ltk_face_detect_load has not been called");
+    if (images > e->face_det_images) return fail(LTK_E_INVALID, "images exceeds max_images");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    MtGraph* prog = e->face_det_last;
+    if (!prog) return fail(LTK_E_STATE, "face detector: no program has run");
+    if (ms_per_op && n_ops != mt_op_count(prog)) return fail(LTK_E_INVALID, "n_ops != the program's launches");
+    auto pass = [&]() -> int {
+        const int prc = run_program(e, prog, images);
+        return prc ? conv_status(prc, std::string("face detector: ") + mt_graph_error(prog)) : 0;
+    };
+    int rc = pass();
+    if (!rc) rc = pass();
+    float ms = 0.f;
+    if (!rc) rc = time_iters(e->compute, iters, pass, &ms);
+    if (rc) return rc;
+    e->face_det_last_n = images;
+    *ms_per_pass = ms / iters;
+    if (ms_per_op) {
+        auto run = [&](std::vector<hipEvent_t>* evs) -> int {
+            const int prc = mt_run_timed(prog, images, e->d_partial, e->partial_cap, e->compute, evs);
+            return prc ? conv_status(prc, std::string("face detector: ") + mt_graph_error(prog)) : 0;
+        };
+        std::vector<float> per((size_t)n_ops);
+        rc = time_intervals(n_ops, iters, run, per.data());
+        if (rc) return rc;
+        memcpy(ms_per_op, per.data(), per.size() * sizeof(float));
+    }
+    return LTK_OK;
 }
 
 int ltk_debug_face_parse_time(ltk_engine* e, int images, int iters, float* ms_per_pass, float* ms_per_op, int n_ops) {

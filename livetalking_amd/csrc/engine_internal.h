@@ -256,7 +256,7 @@ struct ltk_engine {
     // headroom watches (ltk_health_watch), allocated when their program is loaded: Wav2Lip by layer; the MuseTalk, Whisper, HuBERT and
     // face-parser programs by op (the batched Whisper program and every HuBERT program share their model's table).  w2l_scan: set while a watched
     // Wav2Lip call is being enqueued, run_convs scans every layer it launches into it.
-    HealthWatch hw_w2l, hw_mt, hw_whisper, hw_hubert, hw_faceparse;
+    HealthWatch hw_w2l, hw_mt, hw_whisper, hw_hubert, hw_faceparse, hw_facedet;
     HealthWatch* w2l_scan = nullptr;
     // Lock rule.  `mu` owns the enqueue order on compute / aux / aux2 and everything a pass works with: the loaded programs (layers,
     // mt, whisper, vae_enc, their settings), the arena and pointer tables, the prefetch slots / solo_seq / pf_* counters, both graph
@@ -343,6 +343,15 @@ struct ltk_engine {
     MtGraph* face_parse = nullptr;        // BiSeNet face parser (avatar preparation: blend masks), face_parse_size^2 images, face_parse_images per run
     int face_parse_size = 0, face_parse_images = 0;
     int face_parse_last = 0;              // images of the run that ran last (debug read-back)
+    // S3FD face detector (avatar preparation: face boxes): the packed weights once (face_det_w, never run), and one program per frame
+    // size over them (MtGraph::share), built on first use; at most kFaceDetPrograms are kept, the least recently used is dropped
+    MtGraph* face_det_w = nullptr;
+    struct FaceDetProg { MtGraph* g = nullptr; int H = 0, W = 0; unsigned long stamp = 0; };
+    std::vector<FaceDetProg> face_det_progs;
+    unsigned long face_det_clock = 0;
+    int face_det_images = 0;              // max_images of the load
+    MtGraph* face_det_last = nullptr;     // the program that ran last and the images of that run (debug read-back)
+    int face_det_last_n = 0;
     MtGraph* whisper = nullptr;           // Whisper-tiny encoder graph (Audio2Feature)
     float* d_wbasis = nullptr;            // slaney mel basis [80][201] (n_fft 400, 0..8000 Hz)
     float* d_wlogspec = nullptr;          // [80][3000]
@@ -705,6 +714,10 @@ constexpr size_t kHubertPrograms = 3;
 constexpr size_t kHubertBatchPrograms = 2;
 MtGraph* hubert_program(ltk_engine* e, int n_samples, int* rc);                                             // mt_engine.hip, under e->mu
 void hubert_unload(ltk_engine* e);
+void drop_program_graphs(ltk_engine* e, const MtGraph* old);                                                // mt_engine.hip, under e->mu
+constexpr size_t kFaceDetPrograms = 2;
+MtGraph* face_det_program(ltk_engine* e, int H, int W, int* rc);                                            // mt_engine.hip, under e->mu
+void face_det_unload(ltk_engine* e);
 int mt_run_locked(ltk_engine* e, const float* d_feat, const PtrList64* feat_ptrs, int nf, const OutList64* outs, float* d_image_f32);
 
 }  // namespace ltk

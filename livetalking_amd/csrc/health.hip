@@ -23,7 +23,7 @@ void fill_op(ltk_health_op* o, const char* name, int type, int observed, int q8,
     o->limit = q8 ? 448.f : 65504.f;
 }
 
-bool known_program(int program) { return (program >= LTK_HEALTH_WAV2LIP && program <= LTK_HEALTH_HUBERT) || program == LTK_HEALTH_FACEPARSE; }
+bool known_program(int program) { return (program >= LTK_HEALTH_WAV2LIP && program <= LTK_HEALTH_HUBERT) || program == LTK_HEALTH_FACEPARSE || program == LTK_HEALTH_FACEDET; }
 
 // one row of a program's listing: the op's name and type, whether it writes e4m3, and its record in the table
 struct Row { std::string name; int type, q8, rec; };
@@ -62,6 +62,10 @@ HealthWatch* find_watch(ltk_engine* e, int program, int avatar_id, std::shared_p
             if (!e->face_parse) { *rc = fail(LTK_E_STATE, "ltk_face_parse_load has not been called"); return nullptr; }
             mt_rows(e->face_parse);
             return &e->hw_faceparse;
+        case LTK_HEALTH_FACEDET:
+            if (!e->face_det_w) { *rc = fail(LTK_E_STATE, "ltk_face_detect_load has not been called"); return nullptr; }
+            mt_rows(e->face_det_w);
+            return &e->hw_facedet;
         case LTK_HEALTH_ULTRALIGHT: {
             *hold = find_ul_avatar(e, avatar_id);
             if (!*hold || !(*hold)->health) { *rc = fail(LTK_E_STATE, "unknown Ultralight avatar id"); return nullptr; }

@@ -1,6 +1,10 @@
 // MuseTalk (U-Net + VAE decoder), Whisper and HuBERT audio features and the VAE encoder: their entry points and run_program.
 #include "engine_internal.h"
+#include "facedet.h"
 #include "faceparse.h"
+#include "s3fd_kernels.h"
+
+#include <algorithm>
 
 extern "C" {
 
@@ -367,6 +371,17 @@ int ltk_whisper_step_batch(ltk_engine* e, const ltk_whisper_req* reqs, int nreq)
 }  // extern "C"
 
 // ================================================================================ HuBERT-large audio features (Ultralight)
+// under e->mu: a program that leaves a cache takes its captured graphs with it (a graph holds its buffers' addresses, and the next
+// program may land on the same ones); the stream is drained first.  The HuBERT and the face detector caches drop through here.
+void ltk::drop_program_graphs(ltk_engine* e, const MtGraph* old) {
+    (void)hipStreamSynchronize(e->compute);
+    for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
+        if (it->first.first != (const void*)old) { ++it; continue; }
+        if (it->second.exec) (void)hipGraphExecDestroy(it->second.exec);
+        it = e->prog_graphs.graphs.erase(it);
+    }
+}
+
 // The program for clips of n_samples, built on first use over the engine's packed weights; at most kHubertPrograms are kept.  A dropped
 // program takes its captured graph with it (the graph holds its buffers' addresses, and the next program may land on the same one).
 namespace {
@@ -380,12 +395,7 @@ MtGraph* hubert_cached_program(ltk_engine* e, std::vector<ltk_engine::HubertProg
         for (size_t i = 1; i < cache.size(); ++i)
             if (cache[i].stamp < cache[v].stamp) v = i;
         MtGraph* old = cache[v].g;
-        (void)hipStreamSynchronize(e->compute);
-        for (auto it = e->prog_graphs.graphs.begin(); it != e->prog_graphs.graphs.end();) {
-            if (it->first.first != (const void*)old) { ++it; continue; }
-            if (it->second.exec) (void)hipGraphExecDestroy(it->second.exec);
-            it = e->prog_graphs.graphs.erase(it);
-        }
+        drop_program_graphs(e, old);
         if (e->hubert_last == old) e->hubert_last = nullptr;
         if (e->hubert_blast == old) { e->hubert_blast = nullptr; e->hubert_blast_nf = 0; }
         mt_graph_delete(old);
@@ -407,6 +417,53 @@ MtGraph* hubert_cached_program(ltk_engine* e, std::vector<ltk_engine::HubertProg
 
 MtGraph* ltk::hubert_program(ltk_engine* e, int n_samples, int* rc) {
     return hubert_cached_program(e, e->hubert_progs, kHubertPrograms, n_samples, 1, rc);
+}
+
+// The face detector's program for H x W frames, built on first use over the engine's packed weights; at most kFaceDetPrograms are kept.
+// A dropped program takes its captured graphs with it, as a HuBERT program does.
+MtGraph* ltk::face_det_program(ltk_engine* e, int H, int W, int* rc) {
+    *rc = LTK_OK;
+    auto& cache = e->face_det_progs;
+    for (auto& p : cache)
+        if (p.H == H && p.W == W) { p.stamp = ++e->face_det_clock; return p.g; }
+    {   // a size the plan refuses must not cost a cached program
+        FdPlan pl;
+        std::string err;
+        if (fd_plan(H, W, e->face_det_images, &pl, &err)) { *rc = fail(LTK_E_INVALID, err); return nullptr; }
+    }
+    if (cache.size() >= kFaceDetPrograms) {
+        size_t v = 0;
+        for (size_t i = 1; i < cache.size(); ++i)
+            if (cache[i].stamp < cache[v].stamp) v = i;
+        MtGraph* old = cache[v].g;
+        drop_program_graphs(e, old);
+        if (e->face_det_last == old) { e->face_det_last = nullptr; e->face_det_last_n = 0; }
+        mt_graph_delete(old);
+        cache.erase(cache.begin() + v);
+    }
+    MtGraph* g = mt_graph_new();
+    const int brc = mt_build_face_detect_graph(g, e->face_det_w, nullptr, 0, H, W, e->face_det_images, true);
+    if (brc) {
+        *rc = fail(brc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, std::string("face detector: ") + mt_graph_error(g));
+        mt_graph_delete(g);
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    // mt_graph_alloc clears the new buffers with fills on the null stream, which the compute stream does not wait for: a large
+    // program's fill could still be running when the first call writes the threshold word and the frames
+    (void)hipDeviceSynchronize();
+    ltk_engine::FaceDetProg p;
+    p.g = g; p.H = H; p.W = W; p.stamp = ++e->face_det_clock;
+    cache.push_back(p);
+    return g;
+}
+
+void ltk::face_det_unload(ltk_engine* e) {
+    for (auto& p : e->face_det_progs) mt_graph_delete(p.g);
+    e->face_det_progs.clear();
+    e->face_det_last = nullptr; e->face_det_last_n = 0;
+    if (e->face_det_w) { mt_graph_delete(e->face_det_w); e->face_det_w = nullptr; }
+    e->hw_facedet.release();
 }
 
 void ltk::hubert_unload(ltk_engine* e) {
@@ -724,6 +781,88 @@ int ltk_face_parse(ltk_engine* e, const uint8_t* rgb_host, int n, uint8_t* label
         if (he != hipSuccess) rc = fail(LTK_E_HIP, std::string("face parser: ") + hipGetErrorString(he));
     }
     if (rc) {                                            // nothing of the call still reads rgb_host or writes labels_host when it returns
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        return fail(rc, msg);
+    }
+    return LTK_OK;
+}
+
+// ================================================================================ face detector (avatar preparation: face boxes)
+int ltk_face_detect_load(ltk_engine* e, const ltk_named_tensor* sd, int n, int max_images) {
+    if (!e || !sd || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (max_images < 1 || max_images > kFdMaxImages) return fail(LTK_E_INVALID, "face detector: max_images must be in [1, 16]");
+    std::lock_guard<std::mutex> g(e->mu);
+    if (e->face_det_w) return fail(LTK_E_STATE, "a face detector is already loaded in this engine");
+    CHK(enter_device(e->device));
+    MtGraph* wg = mt_graph_new();
+    const int rc = mt_build_face_detect_graph(wg, nullptr, sd, n, 32, 32, 1, false);
+    if (rc) {
+        const std::string msg = mt_graph_error(wg);
+        mt_graph_delete(wg);
+        (void)hipGetLastError();
+        return fail(rc == -4 ? LTK_E_NOMEM : LTK_E_INVALID, "face detector: " + msg);
+    }
+    if (e->hw_facedet.alloc(mt_op_count(wg))) {        // nothing half-loaded stays behind
+        mt_graph_delete(wg);
+        return fail(LTK_E_NOMEM, "face detector: health table allocation failed");
+    }
+    e->face_det_w = wg;
+    e->face_det_images = max_images;
+    return LTK_OK;
+}
+
+int ltk_face_detect(ltk_engine* e, const uint8_t* bgr_host, int n, int H, int W, float thresh, uint32_t* cand_out, int cap, int* counts_out) {
+    if (!e || !bgr_host || !cand_out || !counts_out || n <= 0) return fail(LTK_E_INVALID, "bad arguments");
+    if (!(thresh >= 0.f && thresh < 1.f)) return fail(LTK_E_INVALID, "face detector: thresh must be in [0, 1)");
+    if (cap < 1 || cap > kFdDevCap) return fail(LTK_E_INVALID, "face detector: cap must be in [1, " + std::to_string(kFdDevCap) + "]");
+    CHK(enter_device(e->device));
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->face_det_w) return fail(LTK_E_STATE, "ltk_face_detect_load has not been called");
+    int rc = LTK_OK;
+    MtGraph* prog = face_det_program(e, H, W, &rc);
+    if (!prog) return rc;
+    hipStream_t s = e->compute;
+    const size_t img = (size_t)H * W * 3, rec = (size_t)kFdDevCap * kFdRecWords;
+    const int chunk = e->face_det_images;
+    const MtWatched watch(prog, e->hw_facedet, e->hw_facedet.begin());           // one engine call = one watched call, whatever its chunks
+    // the threshold lives on the device (a captured detect launch reads it there): it is written when a program first runs and when a
+    // call brings another value, not per chunk
+    if (!mt_face_detect_thresh_is(prog, thresh)) {
+        const hipError_t te = hipMemcpyAsync(mt_face_detect_records(prog) + kFdThreshAt, &thresh, sizeof(float), hipMemcpyHostToDevice, s);
+        const hipError_t ts = te == hipSuccess ? hipStreamSynchronize(s) : te;       // `thresh` is this call's argument
+        if (ts != hipSuccess) return fail(LTK_E_HIP, std::string("face detector: threshold: ") + hipGetErrorString(ts));
+        mt_face_detect_set_thresh(prog, thresh);
+    }
+    std::vector<uint32_t> back(kFdHeadBytes / 4 + (size_t)chunk * rec);
+    struct Rec { uint32_t w[kFdRecWords]; };
+    for (int i0 = 0; i0 < n && !rc; i0 += chunk) {
+        const int nf = std::min(chunk, n - i0);
+        // one upload (the frames); the images' counters go back to zero by a fill on the device
+        hipError_t he = hipMemsetAsync(mt_face_detect_records(prog), 0, kFdThreshAt, s);
+        if (he == hipSuccess) he = hipMemcpyAsync(mt_face_detect_image_in(prog), bgr_host + (size_t)i0 * img, (size_t)nf * img, hipMemcpyHostToDevice, s);
+        if (he != hipSuccess) { rc = fail(LTK_E_HIP, std::string("face detector: upload: ") + hipGetErrorString(he)); break; }
+        const int prc = run_program(e, prog, nf);
+        if (prc) { rc = conv_status(prc, std::string("face detector: ") + mt_graph_error(prog)); break; }
+        e->face_det_last = prog; e->face_det_last_n = nf;
+        he = hipMemcpyAsync(back.data(), mt_face_detect_records(prog), kFdHeadBytes + (size_t)nf * rec * 4, hipMemcpyDeviceToHost, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);       // the one wait of the chunk: the next one refills the buffers
+        if (he != hipSuccess) { rc = fail(LTK_E_HIP, std::string("face detector: ") + hipGetErrorString(he)); break; }
+        for (int i = 0; i < nf; ++i) {
+            // arrival order is the atomics': the records of an image leave sorted by key, so the output does not depend on it
+            const uint32_t count = back[i];
+            const size_t held = std::min<size_t>(count, kFdDevCap);
+            Rec* r = reinterpret_cast<Rec*>(back.data() + kFdHeadBytes / 4 + (size_t)i * rec);
+            std::sort(r, r + held, [](const Rec& a, const Rec& b) { return a.w[0] < b.w[0]; });
+            uint32_t* out = cand_out + (size_t)(i0 + i) * cap * kFdRecWords;
+            const size_t keep = std::min<size_t>(held, (size_t)cap);
+            memcpy(out, r, keep * sizeof(Rec));
+            memset(out + keep * kFdRecWords, 0, ((size_t)cap - keep) * sizeof(Rec));
+            counts_out[i0 + i] = (int)std::min<uint32_t>(count, 0x7fffffffu);      // above cap: reported as it is
+        }
+    }
+    if (rc) {                                            // nothing of the call still reads bgr_host when it returns
         const std::string msg = g_err;
         (void)hipStreamSynchronize(s);
         (void)hipGetLastError();

@@ -25,7 +25,9 @@ struct MtTensor {
 
 // (OP_FP_*: the face parser's own ops, parse_kernels.h; their listing types are faceparse.h FpOp::type, MtOp::fp_type)
 enum MtOpType { OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_ADDPOS, OP_VT, OP_HB_L0, OP_LNGELU, OP_POSCONV,
-                OP_FP_STEM, OP_FP_MAXPOOL, OP_FP_GAP, OP_FP_GATE, OP_FP_LABELS };
+                OP_FP_STEM, OP_FP_MAXPOOL, OP_FP_GAP, OP_FP_GATE, OP_FP_LABELS,
+                // the face detector's own ops (s3fd_kernels.h; listing types: facedet.h FdOp::type, carried in MtOp::fp_type)
+                OP_FD_STEM, OP_FD_POOL, OP_FD_L2NORM, OP_FD_DETECT };
 
 struct MtOp {
     MtOpType type;
@@ -52,7 +54,13 @@ struct MtOp {
     // the added map is `r`) and its feat * atten + feat form; OP_FP_STEM: wvec = the packed weight image, gamma / beta = scale / shift
     MtTensor ga, gb;
     int plus1 = 0;
-    int fp_type = -1;           // the listing type of a face-parser op (0 conv, 10 stem ... 14 labels); -1: not one
+    int fp_type = -1;           // the listing type of a face-parser op (0 conv, 10 stem ... 14 labels) or face-detector op (0, 20 ... 23); -1: neither
+    // face detector (mt_build_face_detect_graph): OP_FD_STEM: wvec = the packed weight image, beta = the bias; OP_FD_L2NORM: gamma = the
+    // weight; OP_FD_DETECT: the level and its max-out
+    int fd_level = -1, fd_maxout = 0;
+    // OP_CONV, set by a builder whose outputs must not depend on the images beside an image (mt_build_face_detect_graph): every image
+    // takes the split-K factor of its own one-image launch (mt_run_op_body)
+    bool own_split = false;
 };
 
 // one cross-attention's share of the hoisted k | v projection (MtGraph::kv_all): its value view and where the transposed values go
@@ -101,6 +109,12 @@ struct MtGraph {
     int fp_img_buf = -1;                      // uint8 [frames][fp_size][fp_size][3]: the RGB images
     int fp_label_buf = -1;                    // uint8 [frames][fp_size][fp_size]: the labels
     int fp_size = 0;
+    // face detector (mt_build_face_detect_graph): the byte buffer of the frames, and the candidate buffer all six detect ops append to:
+    // [256-byte head: uint32 counters [frames] at 0, the threshold (float) at kFdThreshAt][frames][fd_cap][6 words]
+    int fd_img_buf = -1;                      // uint8 [frames][fd_H][fd_W][3]: the BGR frames
+    int fd_rec_buf = -1;
+    int fd_H = 0, fd_W = 0, fd_cap = 0;
+    float fd_thresh = __builtin_nanf("");     // what the device's threshold word holds (NaN: never written)
     bool no_rowgemm = false;                  // builder setting: add_conv plans no row-GEMM form beside conv3's (mt_build_face_parse_graph)
 
     MtTensor alloc(int C, int H, int W);

@@ -11,6 +11,7 @@
 #include "misc_kernels.h"
 #include "hubert_kernels.h"
 #include "parse_kernels.h"
+#include "s3fd_kernels.h"
 
 namespace ltk {
 
@@ -285,6 +286,30 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
                 rio.N = nf; rio.KW = op.ksz; rio.stride = 1; rio.pad = op.ksz / 2; rio.relu = 0;
                 rio.ln_out = io.ln_out; rio.ln_out_tiles = io.ln_out_tiles; rio.ln_in = io.ln_in; rio.ln_in_tiles = io.ln_in_tiles; rio.ln_eps = io.ln_eps;
                 rc = rowconv_launch(g.rplans[op.rplan], rio, s, &e);
+            } else if (op.own_split && nf > 1) {
+                // The face detector's records must not depend on the images beside an image.  conv3 splits the channel loop of an
+                // under-filled launch by a factor that follows the launch's frame count, and another factor (or another kernel family)
+                // is another fp32 summation order: every image takes the order of its OWN one-image launch - in one launch over all
+                // nf where the planner grants that factor to the same family at nf, else image by image.
+                ConvReport r1, rn;
+                memset(&r1, 0, sizeof(r1)); memset(&rn, 0, sizeof(rn));
+                ConvIO d = io;
+                d.N = 1; d.report = &r1;
+                rc = conv_launch_dry(g.plans[op.plan], d, &e);
+                const int ks1 = std::max(1, r1.ksplit);
+                if (!rc) { d.N = nf; d.force_ksplit = ks1; d.report = &rn; rc = conv_launch_dry(g.plans[op.plan], d, &e); }
+                auto family = [](const ConvReport& r) { return std::string(r.kernel, strcspn(r.kernel, "<")); };
+                if (!rc && family(rn) == family(r1) && std::max(1, rn.ksplit) == ks1) {
+                    io.force_ksplit = ks1;
+                    rc = conv_launch(g.plans[op.plan], io, s, &e);
+                } else if (!rc) {
+                    const size_t xs = (size_t)op.x.P() * op.x.ld, ys = (size_t)op.y.P() * op.y.ld;
+                    for (int f = 0; f < nf && !rc; ++f) {
+                        ConvIO one = io;
+                        one.N = 1; one.x = io.x + f * xs; one.y = io.y + f * ys;
+                        rc = conv_launch(g.plans[op.plan], one, s, &e);
+                    }
+                }
             } else {
                 rc = conv_launch(g.plans[op.plan], io, s, &e);
             }
@@ -386,6 +411,31 @@ static int mt_run_op_body(MtGraph& g, const MtOp& op, int nf, float* partial, si
             if (rc) { g.err = op.name + ": " + e; return rc; }
             break;
         }
+        // the face detector's own ops (s3fd_kernels.h), refusing as the parser's do
+        case OP_FD_STEM:
+        case OP_FD_POOL:
+        case OP_FD_L2NORM:
+        case OP_FD_DETECT: {
+            std::string e;
+            int rc = -1;
+            if (op.type == OP_FD_STEM)
+                rc = launch_s3fd_stem(reinterpret_cast<const uint8_t*>(g.bufs[g.fd_img_buf]), nf, g.fd_H, g.fd_W, reinterpret_cast<const f16*>(g.vecs[op.wvec]),
+                                      g.vecs[op.beta], g.bufs[op.y.buf], op.y.ld / 16, op.y.coff / 16, s, &e);
+            else if (op.type == OP_FD_POOL)
+                rc = launch_maxpool2x2s2(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.H, op.x.W, g.bufs[op.y.buf], op.y.ld / 16,
+                                         op.y.coff / 16, s, &e);
+            else if (op.type == OP_FD_L2NORM)
+                rc = launch_l2norm(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.C, op.x.P(), g.vecs[op.gamma], g.bufs[op.y.buf], op.y.ld / 16,
+                                   op.y.coff / 16, s, &e);
+            else {
+                char* base = reinterpret_cast<char*>(g.bufs[g.fd_rec_buf]);
+                rc = launch_s3fd_detect(g.bufs[op.x.buf], nf, op.x.ld / 16, op.x.coff / 16, op.x.H, op.x.W, op.fd_maxout, op.fd_level, 0.f,
+                                        reinterpret_cast<const float*>(base + kFdThreshAt), reinterpret_cast<uint32_t*>(base + kFdHeadBytes), g.fd_cap,
+                                        reinterpret_cast<uint32_t*>(base), s, &e);
+            }
+            if (rc) { g.err = op.name + ": " + e; return rc; }
+            break;
+        }
     }
     return 0;
 }
@@ -433,6 +483,9 @@ const char* mt_op_name(MtGraph* g, int i, int* type) {
     if (i < 0 || i >= (int)g->ops.size()) return nullptr;
     if (type) *type = g->ops[i].fp_type >= 0 ? g->ops[i].fp_type : (int)g->ops[i].type;
     return g->ops[i].name.c_str();
+}
+int mt_run_head(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s, int op_end) {
+    return mt_graph_run(*g, nf, partial, partial_cap, s, 0, op_end);
 }
 int mt_run_timed(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s, std::vector<hipEvent_t>* evs) {
     return mt_graph_run(*g, nf, partial, partial_cap, s, 0, -1, evs);

@@ -43,6 +43,8 @@ int mt_run(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s
 // per-op view (profiling): ops in execution order; type 0 conv/linear, 1 GroupNorm, 2 LayerNorm, 3 attention, 4 GEGLU, 5 add-pos, 6 value transpose (hoisted cross-attention values)
 int mt_op_count(MtGraph* g);
 const char* mt_op_name(MtGraph* g, int i, int* type);
+// ops [0, op_end) only, eagerly (ltk_face_detect_debug_get: a program whose ops share buffers is run again up to the op that is read)
+int mt_run_head(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s, int op_end);
 int mt_run_timed(MtGraph* g, int nf, float* partial, size_t partial_cap, hipStream_t s, std::vector<hipEvent_t>* evs);
 // named intermediate (debug / parity): returns device pointer + geometry, or null
 f16* mt_named(MtGraph* g, const char* name, int* C, int* ld, int* coff, int* H, int* W);
@@ -57,6 +59,20 @@ int mt_build_vae_encoder_graph(MtGraph* g, const ltk_named_tensor* vae_sd, int n
 int mt_build_face_parse_graph(MtGraph* g, const ltk_named_tensor* sd, int n, int size, int max_images);
 uint8_t* mt_face_parse_image_in(MtGraph* g);
 const uint8_t* mt_face_parse_labels(MtGraph* g);
+// S3FD face detector (avatar preparation: face boxes): the launch list of facedet.h fd_program over the buffers and views of fd_plan.
+// The packed weights live in ONE graph that is never run (share = null, sd = s3fd().state_dict(): built at 32 x 32 with no activations
+// when `allocate` is false); a program for H x W frames, up to max_images per run, is built over it (share = that graph, sd unused) and
+// owns its activations and op list only - the same ops in the same order, so every program scans into the model's one health table.
+// Input: uint8 BGR [n][H][W][3] in mt_face_detect_image_in(); output: mt_face_detect_records(), the candidate buffer of
+// s3fd_kernels.h (head with counters and threshold, kFdDevCap records per image).  0, -1 (refused: mt_graph_error) or -4 (allocation).
+int mt_build_face_detect_graph(MtGraph* g, const MtGraph* share, const ltk_named_tensor* sd, int n, int H, int W, int max_images, bool allocate);
+uint8_t* mt_face_detect_image_in(MtGraph* g);
+uint8_t* mt_face_detect_records(MtGraph* g);
+// the threshold the program's device word holds (NaN before the first write): ltk_face_detect uploads it only when a call brings another
+bool mt_face_detect_thresh_is(const MtGraph* g, float thresh);
+void mt_face_detect_set_thresh(MtGraph* g, float thresh);
+// launches of `g` that write the buffer of the tensor named `name` (0: no such tensor); 1 = nothing else overwrites it in a run
+int mt_named_writers(MtGraph* g, const char* name);
 // Whisper encoder graph (one 30-s window per run): input log-mel tensor = mt_latent_in(), 5 hidden states
 int mt_build_whisper_graph(MtGraph* g, const ltk_named_tensor* encoder_sd, int n);
 f16* mt_whisper_state(MtGraph* g, int i, int* cbt, int* cb0);

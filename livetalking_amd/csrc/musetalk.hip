@@ -20,8 +20,10 @@
 #include "mt_graph.h"
 #include "tune.h"
 #include "nn_kernels.h"
+#include "facedet.h"
 #include "faceparse.h"
 #include "parse_kernels.h"
+#include "s3fd_kernels.h"
 
 namespace ltk {
 
@@ -728,5 +730,104 @@ int mt_build_face_parse_graph(MtGraph* gp, const ltk_named_tensor* t, int n, int
 }
 uint8_t* mt_face_parse_image_in(MtGraph* g) { return reinterpret_cast<uint8_t*>(g->bufs[g->fp_img_buf]); }
 const uint8_t* mt_face_parse_labels(MtGraph* g) { return reinterpret_cast<const uint8_t*>(g->bufs[g->fp_label_buf]); }
+
+// ------------------------------------------------------------------------------------------ face detector (avatar preparation: face boxes)
+// S3FD (avatars/wav2lip/face_detection/detection/sfd/net_s3fd.py) + batch_detect's per-level work (detect.py:71-89) as the 39 launches
+// of fd_program, wired by fd_plan (facedet.h) and by nothing else.  Convs are the library's with the conv bias as the epilogue's fp32
+// shift and the ReLU folded; a level's conf and loc convs are stacked into ONE conv of 16 outputs (conf rows at 0.., loc rows at 4..7,
+// zero rows and zero biases elsewhere), 6 launches instead of 12.
+int mt_build_face_detect_graph(MtGraph* gp, const MtGraph* share, const ltk_named_tensor* t, int n, int H, int W, int max_images, bool allocate) {
+    MtGraph& g = *gp;
+    FdPlan pl;
+    if (fd_plan(H, W, max_images, &pl, &g.err)) return -1;
+    SD sd{t, n, ""};
+    g.share = share;
+    g.fd_H = H; g.fd_W = W; g.fd_img_buf = pl.image_buf; g.fd_cap = kFdDevCap;
+    g.no_rowgemm = true;
+    for (size_t i = 0; i < pl.buf_elems.size(); ++i) g.buf_halfs.push_back((int)i == pl.image_buf ? (pl.buf_elems[i] + 1) / 2 : pl.buf_elems[i]);
+    g.fd_rec_buf = pl.rec_buf;
+    auto tensor = [](const FdView& v) {
+        MtTensor x;
+        x.buf = v.buf; x.C = v.C; x.ld = v.ld; x.coff = v.coff; x.H = v.H; x.W = v.W;
+        return x;
+    };
+    for (size_t i = 0; i < pl.ops.size(); ++i) {
+        const FdOp& p = pl.ops[i];
+        const MtTensor x = tensor(pl.bind[i].x), y = tensor(pl.bind[i].y);
+        if (p.type == 20) {
+            if (p.cout != kFdStemCout || p.cin != 3 || p.k != 3) { g.err = p.name + ": not the stem s3fd_stem_kernel serves"; return -1; }
+            std::vector<f16> wq(kFdStemWHalfs);
+            const float* b = nullptr;
+            if (!share) {
+                const float* w = sd.get(p.name + ".weight", (size_t)p.cout * p.cin * 9);
+                b = w ? sd.get(p.name + ".bias", p.cout) : nullptr;
+                if (!b) { g.err = sd.err; return -1; }
+                s3fd_stem_pack(w, wq.data());
+            }
+            MtOp op;
+            op.type = OP_FD_STEM; op.fp_type = p.type; op.name = p.name; op.y = y;
+            op.wvec = g.add_named_vec(p.name + ".wq", wq.data(), wq.size() * sizeof(f16));
+            op.beta = g.add_named_vec(p.name + ".bias", b, (size_t)p.cout * sizeof(float));
+            if (op.wvec < 0 || op.beta < 0) return share ? -1 : -4;
+            g.ops.push_back(op);
+            g.named[p.name] = y;
+            g.macs += (double)p.cin * p.cout * 9 * y.P();
+        } else if (p.type == 0) {
+            std::vector<float> wm, bm;
+            const float *w = nullptr, *b = nullptr;
+            if (!share && p.level < 0) {
+                w = sd.get(p.name + ".weight", (size_t)p.cout * p.cin * p.k * p.k);
+                b = w ? sd.get(p.name + ".bias", p.cout) : nullptr;
+                if (!b) { g.err = sd.err; return -1; }
+            } else if (!share) {
+                const int nconf = p.maxout ? 4 : 2;
+                const size_t row = (size_t)p.cin * 9;
+                const float* wc = sd.get(p.name + "_conf.weight", nconf * row);
+                const float* bc = wc ? sd.get(p.name + "_conf.bias", nconf) : nullptr;
+                const float* wl = bc ? sd.get(p.name + "_loc.weight", 4 * row) : nullptr;
+                const float* bl = wl ? sd.get(p.name + "_loc.bias", 4) : nullptr;
+                if (!bl) { g.err = sd.err; return -1; }
+                wm.assign(16 * row, 0.f); bm.assign(16, 0.f);
+                memcpy(wm.data(), wc, nconf * row * sizeof(float)); memcpy(bm.data(), bc, nconf * sizeof(float));
+                memcpy(wm.data() + 4 * row, wl, 4 * row * sizeof(float)); memcpy(bm.data() + 4, bl, 4 * sizeof(float));
+                w = wm.data(); b = bm.data();
+            }
+            if (x.H != p.H || x.W != p.W || y.H != p.Ho || y.W != p.Wo) { g.err = p.name + ": the bound maps are not the op's"; return -1; }
+            if (g.add_conv(p.name, w, b, p.cin, p.cout, p.k, p.stride, p.pad, x, y, nullptr, p.relu ? 1 : 0, 0)) return -1;
+            g.ops.back().fp_type = 0;
+            g.ops.back().unet3x3 = false;           // conv3 under its own rule, as the conv planner is held to for every conv of the list
+            g.ops.back().own_split = true;          // an image's records must not depend on the images beside it
+        } else {
+            MtOp op;
+            op.fp_type = p.type; op.name = p.name; op.x = x; op.y = y;
+            if (p.type == 21) op.type = OP_FD_POOL;
+            else if (p.type == 22) {
+                op.type = OP_FD_L2NORM;
+                const float* w = share ? nullptr : sd.get(p.name + ".weight", p.cin);
+                if (!share && !w) { g.err = sd.err; return -1; }
+                op.gamma = g.add_named_vec(p.name + ".weight", w, (size_t)p.cin * sizeof(float));
+                if (op.gamma < 0) return share ? -1 : -4;
+            } else if (p.type == 23) {
+                op.type = OP_FD_DETECT; op.fd_level = p.level; op.fd_maxout = p.maxout;
+                op.y = MtTensor();                  // records in fd_rec_buf: no fp16 output tensor (nothing to scan, nothing to read back)
+                if (x.ld != 16 || x.coff || x.C != 16) { g.err = p.name + ": the head map must be a dense 16-channel tensor"; return -1; }
+            } else { g.err = p.name + ": unknown op type"; return -1; }
+            g.ops.push_back(op);
+            if (p.type != 23) g.named[p.name] = y;
+        }
+    }
+    return allocate ? mt_graph_alloc(g, max_images) : 0;
+}
+uint8_t* mt_face_detect_image_in(MtGraph* g) { return reinterpret_cast<uint8_t*>(g->bufs[g->fd_img_buf]); }
+uint8_t* mt_face_detect_records(MtGraph* g) { return reinterpret_cast<uint8_t*>(g->bufs[g->fd_rec_buf]); }
+bool mt_face_detect_thresh_is(const MtGraph* g, float thresh) { return g->fd_thresh == thresh; }
+void mt_face_detect_set_thresh(MtGraph* g, float thresh) { g->fd_thresh = thresh; }
+int mt_named_writers(MtGraph* g, const char* name) {
+    auto it = g->named.find(name);
+    if (it == g->named.end()) return 0;
+    int n = 0;
+    for (const MtOp& op : g->ops) n += op.y.buf == it->second.buf;
+    return n;
+}
 
 }  // namespace ltk

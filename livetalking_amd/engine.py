@@ -508,6 +508,59 @@ class Engine:
         return dict(ops=[dict(name=o.name.decode(), **{k: view(getattr(o, k)) for k in ("x", "y", "r", "a", "b")}) for o in ops[:n.value]],
                     buf_bytes=[int(b) for b in bufs[:nb.value]], image_buf=ib.value, label_buf=lb.value)
 
+    # ---- the face detector's own ops (include/ltk.h: "Standalone ops of the S3FD face detector"); views as above
+    def s3fd_stem_f16(self, d_bgr_ptr: int, N, H, W, weight: np.ndarray, bias=None, d_y_ptr: int = 0, views: Optional[dict] = None):
+        """conv1_1 + ReLU on device uint8 BGR [N][H][W][3], channel reversal and mean subtraction fused; weight (64,3,3,3)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        assert w.shape == (64, 3, 3, 3)
+        b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+        assert b is None or b.shape == (64,)
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_s3fd_stem_f16(self._h, C.c_void_p(d_bgr_ptr), int(N), int(H), int(W), w.ctypes.data,
+                                               b.ctypes.data if b is not None else None, C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def maxpool2x2s2_f16(self, d_x_ptr: int, N, H, W, C_, d_y_ptr: int, views: Optional[dict] = None):
+        """F.max_pool2d(x, 2, 2) on a CB16 tensor (floor mode)."""
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_maxpool2x2s2_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(H), int(W), int(C_), C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def l2norm_f16(self, d_x_ptr: int, N, P, C_, weight: np.ndarray, d_y_ptr: int, views: Optional[dict] = None):
+        """L2Norm over the C channels of each of P pixels of a CB16 tensor; weight (C,)."""
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        assert w.shape == (int(C_),)
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_l2norm_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(P), int(C_), w.ctypes.data, C.c_void_p(d_y_ptr), C.byref(o)))
+
+    def s3fd_detect_f16(self, d_x_ptr: int, N, H, W, maxout: bool, level: int, thresh: float, d_recs_ptr: int, cap: int, d_counts_ptr: int,
+                        views: Optional[dict] = None):
+        """One level's candidates of a merged head map appended to recs [N][cap][6 words] through counts [N] (not reset here)."""
+        o = _lib.ConvOpts(**{k: int(v) for k, v in (views or {}).items()})
+        _lib.check(self._lib.ltk_s3fd_detect_f16(self._h, C.c_void_p(d_x_ptr), int(N), int(H), int(W), 1 if maxout else 0, int(level),
+                                                 float(thresh), C.c_void_p(d_recs_ptr), int(cap), C.c_void_p(d_counts_ptr), C.byref(o)))
+
+    @staticmethod
+    def face_detect_program(H: int, W: int):
+        """The face detector's launch list at H x W, on the host alone (include/ltk.h: ltk_debug_face_detect_program): a dict per launch."""
+        ops = (_lib.FdOpInfo * 64)()
+        n = C.c_int()
+        _lib.check(_lib.load().ltk_debug_face_detect_program(int(H), int(W), ops, 64, C.byref(n)))
+        return [dict(name=o.name.decode(), **{f: getattr(o, f) for f, _ in _lib.FdOpInfo._fields_[1:]}) for o in ops[:n.value]]
+
+    @staticmethod
+    def face_detect_plan(H: int, W: int, max_images: int = 16):
+        """Where every launch of face_detect_program(H, W) reads and writes (include/ltk.h: ltk_debug_face_detect_plan), on the host
+        alone: dict(ops=[dict(name, x, y)], buf_bytes=[...], image_buf, total_bytes).  A view is dict(buf, ld, coff, C, H, W), or None."""
+        ops = (_lib.FdBind * 64)()
+        bufs = (C.c_ulonglong * 64)()
+        n, nb, ib, tot = C.c_int(), C.c_int(), C.c_int(), C.c_ulonglong()
+        _lib.check(_lib.load().ltk_debug_face_detect_plan(int(H), int(W), int(max_images), ops, 64, C.byref(n), bufs, 64, C.byref(nb),
+                                                          C.byref(ib), C.byref(tot)))
+
+        def view(v):
+            return None if v.buf < 0 else {f: int(getattr(v, f)) for f, _ in _lib.FpView._fields_}
+        return dict(ops=[dict(name=o.name.decode(), x=view(o.x), y=view(o.y)) for o in ops[:n.value]],
+                    buf_bytes=[int(b) for b in bufs[:nb.value]], image_buf=ib.value, total_bytes=int(tot.value))
+
     # ------------------------------------------------------------------ avatar preparation (face parser: blend-mask labels)
     def load_face_parser(self, sd: Dict[str, object], size: int = 512, max_images: int = 1):
         """face_parsing/__init__.py:44-56: `sd` = BiSeNet(n_classes=19).state_dict() (79999_iter.pth), tensors or arrays; the unused
@@ -531,6 +584,47 @@ class Engine:
         # (before a load the library refuses with LTK_E_STATE)
         _lib.check(self._lib.ltk_face_parse(self._h, rgb.ctypes.data, int(rgb.shape[0]), out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ avatar preparation (face detector: face boxes)
+    def load_face_detector(self, sd: Dict[str, object], max_images: int = 16):
+        """sfd_detector.py:26-29: `sd` = s3fd().state_dict() (s3fd.pth), tensors or arrays.  max_images: images per run of a program
+        (the reference's face_det_batch_size)."""
+        arr, n, keep = self._named_tensors(sd)
+        _lib.check(self._lib.ltk_face_detect_load(self._h, arr, n, int(max_images)))
+        del keep
+
+    def face_detect(self, frames_bgr: np.ndarray, thresh: float = 0.05, cap: int = 4096, return_keys: bool = False):
+        """uint8 BGR frames (n, H, W, 3) as cv2.imread gives them -> per image a float32 (k_i, 5) array of (x1, y1, x2, y2, score), the
+        positions whose score is above `thresh`, in key order (level, row, column) (include/ltk.h: ltk_face_detect).  Raises when an
+        image has more than `cap` candidates.  return_keys: also the uint32 keys, level << 28 | h << 14 | w."""
+        f = np.ascontiguousarray(frames_bgr)
+        if f.dtype != np.uint8 or f.ndim != 4 or f.shape[0] < 1 or f.shape[3] != 3:
+            raise ValueError(f"face_detect: uint8 (n, H, W, 3) expected, got {f.dtype} {f.shape}")
+        n = int(f.shape[0])
+        cand = np.zeros((n, int(cap), 6), dtype=np.uint32)
+        counts = np.zeros(n, dtype=np.int32)
+        _lib.check(self._lib.ltk_face_detect(self._h, f.ctypes.data, n, int(f.shape[1]), int(f.shape[2]), float(thresh), cand.ctypes.data,
+                                             int(cap), counts.ctypes.data))
+        over = [i for i in range(n) if counts[i] > cap]
+        if over:
+            raise RuntimeError(f"face_detect: image {over[0]} has {int(counts[over[0]])} candidates above {thresh}, the lists hold {cap}")
+        rows = [np.ascontiguousarray(cand[i, :counts[i], 1:]).view(np.float32) for i in range(n)]
+        if return_keys:
+            return rows, [cand[i, :counts[i], 0].copy() for i in range(n)]
+        return rows
+
+    def face_detect_debug_get(self, name: str, shape) -> np.ndarray:
+        """The output of the launch `name` as the last run left it: float32 (images, cout, Ho, Wo); a merged head has 16 channels."""
+        out = np.empty(shape, dtype=np.float32)
+        _lib.check(self._lib.ltk_face_detect_debug_get(self._h, name.encode(), int(shape[0]), out.ctypes.data, out.size))
+        return out
+
+    def face_detect_time(self, images: int, iters: int, per_op: bool = False):
+        """(ms per device pass of `images` images of the last call's frame size as ltk_face_detect replays it, per-launch ms or None)."""
+        ms = C.c_float()
+        ops = (C.c_float * 39)() if per_op else None
+        _lib.check(self._lib.ltk_debug_face_detect_time(self._h, int(images), int(iters), C.byref(ms), ops, 39 if per_op else 0))
+        return ms.value, (list(ops) if per_op else None)
 
     def face_parse_debug_get(self, name: str, shape) -> np.ndarray:
         """The output of the launch `name` as the last run left it: float32 (images, cout, Ho, Wo), real channels only."""

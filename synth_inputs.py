@@ -637,3 +637,49 @@ def faceparse_image(size: int = 512, seed: int = 0) -> np.ndarray:
     """A smooth low-pass RGB uint8 image (size, size, 3)."""
     rng = np.random.default_rng(9000 + seed)
     return _smooth_image(rng, size, size)
+
+
+# ---------------------------------------------------------------------------------------------- S3FD face detector
+S3FD_TRUNK = (("conv1_1", 3, 64, 3), ("conv1_2", 64, 64, 3), ("conv2_1", 64, 128, 3), ("conv2_2", 128, 128, 3), ("conv3_1", 128, 256, 3),
+              ("conv3_2", 256, 256, 3), ("conv3_3", 256, 256, 3), ("conv4_1", 256, 512, 3), ("conv4_2", 512, 512, 3), ("conv4_3", 512, 512, 3),
+              ("conv5_1", 512, 512, 3), ("conv5_2", 512, 512, 3), ("conv5_3", 512, 512, 3), ("fc6", 512, 1024, 3), ("fc7", 1024, 1024, 1),
+              ("conv6_1", 1024, 256, 1), ("conv6_2", 256, 512, 3), ("conv7_1", 512, 128, 1), ("conv7_2", 128, 256, 3))
+S3FD_NORMS = (("conv3_3_norm", 256, 10.0), ("conv4_3_norm", 512, 8.0), ("conv5_3_norm", 512, 5.0))
+S3FD_HEADS = (("conv3_3_norm_mbox", 256, 4), ("conv4_3_norm_mbox", 512, 2), ("conv5_3_norm_mbox", 512, 2), ("fc7_mbox", 1024, 2),
+              ("conv6_2_mbox", 512, 2), ("conv7_2_mbox", 256, 2))
+# per level, fitted once on seed 29 / s3fd_frame(64, 64, 0..7): the gain on the head's conf rows sets the spread of the (face - background)
+# logit over a map, the shift (half on the face bias, half against the background's) its mean: 1.2 around -5.0 at level 0, 0.7 around
+# -1.1 at the others.  Almost every position of levels 1..5 then scores above the 0.05 threshold, far from it (a score's fp16 error
+# cannot move it across), a few percent of them above 0.5, and level 0 with its 16 x more positions adds a handful
+S3FD_CONF_GAIN = (3.0, 1.6, 3.4, 1.3, 2.3, 3.4)
+S3FD_FACE_BIAS = (-6.2, -1.3, -0.5, -0.8, -0.7, -1.2)
+
+
+def s3fd_state_dict(seed: int = 29, shapes_only: bool = False) -> Dict[str, np.ndarray]:
+    """Reference-named fp32 state_dict of face_detection's s3fd() (detection/sfd/net_s3fd.py) as numpy arrays, in the module's key
+    order: fan-in scaled convs like `_conv` (gain sqrt 2 in the trunk, where a ReLU follows every conv), L2Norm weights around their
+    scales (10, 8, 5), and heads whose conf rows carry S3FD_CONF_GAIN and whose face logit carries S3FD_FACE_BIAS, so that the float64
+    network on s3fd_frame gives a usable score distribution (scripts/gen_golden_s3fd.py asserts it)."""
+    rng = np.random.default_rng(seed)
+    sd: Dict[str, np.ndarray] = {}
+    for name, cin, cout, k in S3FD_TRUNK:
+        # conv1_1 sees mean-subtracted bytes (rms about 64): its gain brings the trunk to unit scale
+        _conv(rng, sd, name, cin, cout, k, gain=float(np.sqrt(2.0)) / (64.0 if name == "conv1_1" else 1.0))
+    for name, c, scale in S3FD_NORMS:
+        sd[name + ".weight"] = (scale * rng.uniform(0.9, 1.1, c)).astype(np.float32)
+    for (name, cin, nconf), gain, bias in zip(S3FD_HEADS, S3FD_CONF_GAIN, S3FD_FACE_BIAS):
+        _conv(rng, sd, name + "_conf", cin, nconf, 3, gain=gain)
+        # zero-sum rows: the features are all positive, and their common mean times a row's sum would move every logit of the map by
+        # the same large amount - fp16 would then round the logits more coarsely than their difference, which is all the softmax reads
+        w = sd[name + "_conf.weight"]
+        sd[name + "_conf.weight"] = np.ascontiguousarray(w - w.mean(axis=(1, 2, 3), keepdims=True), dtype=np.float32)
+        sd[name + "_conf.bias"][:-1] -= np.float32(bias / 2)
+        sd[name + "_conf.bias"][-1] += np.float32(bias / 2)
+        _conv(rng, sd, name + "_loc", cin, 4, 3)
+    return _finish(sd, shapes_only)
+
+
+def s3fd_frame(H: int = 64, W: int = 64, seed: int = 0) -> np.ndarray:
+    """A smooth low-pass BGR uint8 frame (H, W, 3), as cv2.imread would hand it over."""
+    rng = np.random.default_rng(9500 + seed)
+    return np.ascontiguousarray(_smooth_image(rng, H, W, cells=6)[..., ::-1])
