@@ -24,10 +24,17 @@ Third-party leaves (none of them vendored in /root/reference or installed here):
     truncates instead and is at most 1 LSB lower).  Chroma is taken from the top-left pixel of each 2x2 quad in that
     shortcut's C routine (`chroma=0`) and from the 2x2 mean in the generic / SIMD paths (`chroma=1`).
 
-PARITY UNPINNED: neither OpenCV nor PyAV/FFmpeg exists in this container and the reference has no golden frames for
-these steps; the constants are checked against the BT.601 limited-range known answers (white 235/128/128, black
-16/128/128, red 81/90/240, green 145/54/34, blue 41/240/110) in tests/test_egress.py.  The HIP kernel must match THIS
-statement bit-exactly.
+What is known about these leaves:
+  * unpinned against the libraries: neither OpenCV nor PyAV/FFmpeg is available and the reference has no golden frames
+    for these steps; the constants are checked against the BT.601 limited-range known answers (white 235/128/128,
+    black 16/128/128, red 81/90/240, green 145/54/34, blue 41/240/110) in tests/test_egress.py.
+  * bounded against float64 (tests/test_delivery_host.py): the integer matrix is within 0.507 / 0.562 / 0.572 LSB
+    (Y / U / V) of the float64 BT.601 limited-range formulas over all 2^24 colours, the rounded 2x2 chroma mean within
+    0.5 of the exact mean, and float32 addWeighted within 0.500 LSB of the float64 weighted sum over all byte pairs at
+    the weights of tests/delivery_cases.py.
+  * bit-exact between kernel and restatement: tests/test_delivery_gpu.py holds egress_kernel and egress_batch_kernel
+    (dword and byte forms) to these functions byte for byte at every row / column tail, watermark overhang and weight of
+    that table (profiles/delivery_parity.txt).
 """
 from __future__ import annotations
 

@@ -16,11 +16,22 @@ half-pixel centres computed in float32, 11-bit fixed-point coefficients
 shrinking, and the exact-2x-shrink case redirected to the 2x2 box average
 (INTER_AREA fast path).
 
-PARITY UNPINNED for this leaf: no OpenCV build is available in this container
-and the reference holds no golden frames, so the restatement could not be
-checked against real cv2 output; the reference-side tolerance is therefore
-stated as +-1 LSB.  The HIP kernel is required to match THIS
-statement bit-exactly.
+What is known about this leaf (and about blend_linear_u8 below):
+  * unpinned against the library: no OpenCV build is available and the
+    reference holds no golden frames, so the restatement was never compared
+    with real cv2 output.
+  * bounded against float64: on the table of tests/delivery_cases.py (every
+    destination length 1..520 from 256 and 1..350 from 168 on both axes, the
+    shortcut boxes and their one-off neighbours, upscales past 2x)
+    resize_linear_u8 stays within 0.827 LSB (source 256) / 0.836 LSB (source
+    168) of the plain float64 half-pixel bilinear with replicated borders, and
+    float32 blendLinear within 0.502 LSB of the exact convex mix over all
+    (s1, s2, mask) triples (tests/test_delivery_host.py).  A mistake shared by
+    kernel and restatement would have to hide inside one rounding.
+  * bit-exact between kernel and restatement: tests/test_delivery_gpu.py holds
+    paste_kernel, paste_batch_kernel, paste_blend_kernel and the Ultralight
+    pair to these functions byte for byte on the same table
+    (profiles/delivery_parity.txt).
 """
 from __future__ import annotations
 
